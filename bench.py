@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — QP paths/sec of the batched solve (BASELINE.json metric) on N GPUs of one node.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,20 +11,23 @@ under torchrun with WORLD_SIZE != N it exits non-zero; the printed line is refus
 A "step" is one pass of the hot path over one batch of synthetic planning instances already resident in HBM, at the HEADLINE setting:
 equilibration + assembly + 25 ADMM iterations (the warm start) + the semismooth-Newton refinement of every path (factorisation, solve, line
 search per step; 13.9 steps on average on config 3), certified at OSQP's termination test with eps 1e-8 — hence also at the metric's 1e-4 —
-+ output map.  The OSQP-faithful solve ("ADMM to eps 1e-4", what the metric's words describe) is timed beside it: `value_osqp_faithful`.
++ output map.  The OSQP-faithful solve ("ADMM to eps 1e-4", what the metric's words describe) is timed beside it (--full): `value_osqp_faithful`.
   N=1   BASELINE config 3: B=4096 paths, N=200 points, KP, per-path random obstacle clearances
   N>1   BASELINE config 4: the same generator, 4096 paths per GPU (contiguous shard of path ids), no data-path collective
         (paths are independent); RCCL carries the barrier, the reduction of a few statistics and (--gather) the result gather.
 `value` is what SURVEY.md §8d prescribes: K single-batch solves issued one after the other on ONE stream, timed between two
 barriers (max over ranks), at the HEADLINE setting — the fastest setting at which EVERY path of the batch is within 1e-4 m (lateral-offset
-RMS) of its exact optimum AND satisfies OSQP's termination test at eps 1e-4 (`config.accuracy` carries the count, measured
-in the run against tests/golden/tight_full_c3.npz).  The OSQP-faithful default (no extension) is timed beside it as `osqp_default`.
-`single_batch` holds the per-step hipEvent figures (median of K).  Everything bulky (other configs, stage legs, the table of settings) goes
-to the details file (--details, default bench_details.json next to this script when writable); the printed line stays short enough for
-the driver's record.
+RMS) of its exact optimum AND satisfies OSQP's termination test at eps 1e-4 (with --full `config.accuracy` carries the count, measured
+in the run against tests/golden/tight_full_c3_part*.npz).  The OSQP-faithful default (no extension) is timed beside it as `osqp_default`.
+`single_batch` holds the per-step hipEvent figures (median of K).
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs DIR) and the line.  Every
+other leg (the OSQP-faithful figure, accuracy and parity, other configs, stage legs, the table of settings, live PMC passes, CPU baselines)
+runs only with --full; everything bulky goes to the details file (--details, default bench_details.json next to this script when writable),
+and the printed line stays short enough for the driver's record.
+--dump-outputs DIR writes what a caller of the timed path receives from its last timed step (states and po_info fields, float64 .npy).
 Rank 0 prints ONE JSON line.  `roofline` is the fp64 VALU issue roof (the solver state is LDS/register resident: HBM is not the
 binding resource); SURVEY §8d's algorithmic-bytes contract figure is kept as `roofline.algorithmic_hbm_equivalent`.
-`parity` is computed in the run: device vs the CPU oracle at identical settings on the CPU-baseline sample, and the lateral-offset
+`parity` (--full) is computed in the run: device vs the CPU oracle at identical settings on the CPU-baseline sample, and the lateral-offset
 RMS against the exact optimum (tests/golden/tight_c3.npz) with and without the opt-in polish step.
 """
 import argparse
@@ -220,10 +223,14 @@ def gold_for(batch, first_path=0):
         name = "k"
     elif batch.formulation == 0 and batch.N == 231 and batch.keep == 3:
         name = "keep3"
-    path = None if name is None else os.path.join(ROOT, "tests", "golden", f"tight_full_{name}.npz")
-    if path is None or not os.path.exists(path) or first_path != 0:
+    if name is None or first_path != 0:
         return None, None
-    return np.load(path)["e_y"].astype(np.float64), name
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from make_tight_full import fixture_files, load_tight_full
+
+    if not fixture_files(name):
+        return None, None
+    return load_tight_full(name)["e_y"].astype(np.float64), name
 
 
 def accuracy_of(x, info, batch, gold):
@@ -723,6 +730,25 @@ class _DryEngine:
         return info
 
 
+DUMP_BYTES_MAX = 63 * 10 ** 6  # --dump-outputs: budget of the array data (64 MB in all, less room for the .npy headers)
+
+
+def dump_outputs(dirname, states, info, first_path):
+    """What the timed path handed its caller in the last timed step: states [B][N][5] and the numeric po_info fields, as float64 .npy files.
+    path_ids.npy holds the global path id of every row; a batch beyond the budget is cut to a fixed, seeded sample of paths (the same rows in every file)."""
+    B = len(states)
+    fields = [f for f in info.dtype.names if f != "reserved"]
+    per_path = 8 * (states[0].size + len(fields) + 1)
+    rows = np.arange(B)
+    if B * per_path > DUMP_BYTES_MAX:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_BYTES_MAX // per_path, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "path_ids.npy"), (first_path + rows).astype(np.float64))
+    np.save(os.path.join(dirname, "states.npy"), np.ascontiguousarray(states[rows], dtype=np.float64))
+    for f in fields:
+        np.save(os.path.join(dirname, f"info_{f}.npy"), info[f][rows].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -730,6 +756,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4096, help="paths per GPU")
     ap.add_argument("--config", type=int, default=0, help="BASELINE config id (default: 3 at N=1, 4 at N>1)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline figure (the options below select among them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the outputs of the last timed step to DIR/<name>.npy (float64)")
     ap.add_argument("--streams", type=int, default=3, help="handles/HIP streams of the secondary `pipelined` leg (0 = skip it)")
     ap.add_argument("--no-stages", action="store_true", help="skip the legs for the stages around the QP (SURVEY.md §8f)")
     ap.add_argument("--no-configs", action="store_true", help="skip the quick legs for BASELINE configs 1, 2, 5 and the K formulation")
@@ -743,6 +771,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="no GPU: gloo backend, faked device times; exercises the shard split, reductions, gather and JSON "
                     "assembly of the N>1 branch (tests/test_multi_process.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
 
     # --gpus N means N GPUs.  Started WITHOUT torchrun (no WORLD_SIZE in the environment) and N > 1: re-run this very command under
     # `python -m torch.distributed.run --nproc-per-node N` (one process per GPU, rendezvous on 127.0.0.1) and hand its exit code back.  Started
@@ -824,7 +854,7 @@ def main():
         batch = synth.make_batch(cfg, B=hi - lo, first_path=lo)
         form, N, keep = batch.formulation, batch.N, batch.keep
         dbatch = binding.DeviceBatch(batch, device=dev)
-        S = max(1, args.streams)
+        S = max(1, args.streams) if args.full else 1  # the extra handles serve the `pipelined` leg of --full only
         engs, streams, dbs = [], [], []
         for i in range(S):
             e = binding.Engine(local_rank, make_params(binding, HEADLINE["params"]))
@@ -884,6 +914,18 @@ def main():
         if ranks_seen["rccl_ranks_seen"] != args.gpus or sorted(n["rank"] for n in names if n is not None) != list(range(args.gpus)):
             raise SystemExit(f"bench.py: --gpus {args.gpus} but the ranks that answered are {ranks_seen}")
 
+    if args.dump_outputs:  # before any leg of --full reuses the batch's output buffers
+        if world > 1:
+            from path_optimizer_amd.abi import INFO_DTYPE
+
+            info_t = torch.from_numpy(info.view(np.uint8).reshape(len(info), -1).copy()).to(dev) if dry else dbatch.out_info
+            all_states = gather_to_root(dbatch.out_states, world, rank)
+            all_info = gather_to_root(info_t, world, rank)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, all_states.cpu().numpy(), all_info.cpu().numpy().view(INFO_DTYPE).reshape(-1), 0)
+        else:
+            dump_outputs(args.dump_outputs, dbatch.out_states.cpu().numpy(), info, lo)
+
     out, details = None, {}
     if rank == 0:
         paths_per_s = world * B * args.steps / elapsed_max
@@ -900,7 +942,7 @@ def main():
             "metric": "QP paths/sec at N=200 pts, batch=4096; ADMM iters to 1e-4",
             "value": paths_per_s,
             # the figure that matches the metric's wording ("ADMM iters to 1e-4") and the library default: the OSQP-faithful leg (refine = 0), same batch, same K steps,
-            # timed the same way further down (rank 0, N = 1; `osqp_default` has its details).  `value` itself = 25 ADMM iterations + the Newton refinement (`config.setting`)
+            # timed the same way further down (--full, rank 0, N = 1; `osqp_default` has its details).  `value` itself = 25 ADMM iterations + the Newton refinement (`config.setting`)
             "value_osqp_faithful": None,
             "unit": "paths/s",
             "n_gpus": world,
@@ -945,9 +987,9 @@ def main():
         if gather is not None:
             out["gather"] = gather
 
-    # ---- secondary GPU legs (rank 0, N = 1) ----
+    # ---- secondary GPU legs (--full; rank 0, N = 1) ----
     dev_samples = {}
-    if not dry and world == 1:
+    if args.full and not dry and world == 1:
         gold, gold_name = gold_for(batch, lo)
         ns = max(1, min(args.cpu_sample if args.cpu_sample > 0 else 256, B))
         full_x = binding.DeviceBatch(batch, device=dev, want_x=True)
@@ -955,7 +997,7 @@ def main():
         hrow, hx, hinfo = run_setting(torch, binding, streams[0], full_x, HEADLINE["params"], steps=1)
         dev_samples["headline"] = (hx[:ns].copy(), hinfo[:ns].copy())
         if gold is not None:
-            out["config"]["accuracy"] = {"yardstick": f"exact optimum of every path (tests/golden/tight_full_{gold_name}.npz, KKT residuals <= 3e-14), lateral-offset RMS per path, bar 1e-4 m",
+            out["config"]["accuracy"] = {"yardstick": f"exact optimum of every path (tests/golden/tight_full_{gold_name}[_part<ii>].npz, KKT residuals <= 3e-14), lateral-offset RMS per path, bar 1e-4 m",
                                          **accuracy_of(hx, hinfo, batch, gold)}
             out["config"]["accuracy_clause_met"] = bool(out["config"]["accuracy"]["n_gt_1e-4_m"] == 0 and hrow["unsolved"] == 0 and len(gold) >= B)
         # the OSQP-faithful default (no extension), same batch, same K steps, timed the same way

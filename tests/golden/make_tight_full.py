@@ -12,10 +12,12 @@ Method (test infrastructure, CPU only; the same as make_tight_c3.py): oracle ADM
 with scipy's sparse LU (an algorithm independent of both ADMM implementations), accepted only when the active set reproduces itself, i.e. the point satisfies
 the KKT conditions; every point is then certified by the oracle's solver-independent po_oracle_kkt_check (stationarity, primal violation, complementarity:
 <= 2e-6 asserted; measured <= 3e-14 on KP / K, 4e-7 absolute on KPC, whose curvature-rate slack rows carry the weight 1e5).  Paths the active-set iteration does not settle fall back to ADMM at eps 1e-10.
-e_y is stored as float32 (|rounding| <= 1.2e-7 m for |e_y| < 2 m: three orders below the 1e-4 m bar) so that 4096 x 200 values stay a 3 MB fixture.
+e_y is stored as float32 (|rounding| <= 1.2e-7 m for |e_y| < 2 m: three orders below the 1e-4 m bar).  A set whose e_y exceeds FILE_BYTES is written
+as consecutive slices of paths, tight_full_<set>_part<ii>.npz, so that every committed fixture stays under 1 MiB; load_tight_full() reassembles either form.
 
     python tests/golden/make_tight_full.py [set ...]        (default: all sets; one worker process per host core)
 """
+import glob
 import multiprocessing as mp
 import os
 import sys
@@ -35,6 +37,24 @@ SETS = {
     "k": (3, {"formulation": 2}, 4096),
     "keep3": (3, {"N": 231, "ds": 0.3}, 1024),
 }
+FILE_BYTES = 960_000  # raw float32 e_y per fixture file: compressed, it stays under the 1 MiB limit of a committed file
+
+
+def fixture_files(name):
+    """The fixture file of set `name`, or its parts in path order."""
+    whole = os.path.join(HERE, f"tight_full_{name}.npz")
+    if os.path.exists(whole):
+        return [whole]
+    return sorted(glob.glob(os.path.join(HERE, f"tight_full_{name}_part[0-9][0-9].npz")))
+
+
+def load_tight_full(name):
+    """{"e_y", "kkt_max", "method", "note"} of set `name` over all of its paths, whether stored whole or in parts."""
+    parts = [np.load(f) for f in fixture_files(name)]
+    if not parts:
+        raise FileNotFoundError(f"no fixture tight_full_{name}*.npz in {HERE}")
+    return {"e_y": np.concatenate([g["e_y"] for g in parts]), "kkt_max": np.max([g["kkt_max"] for g in parts], axis=0),
+            "method": np.concatenate([g["method"] for g in parts]), "note": str(parts[0]["note"])}
 
 
 def batch_of(name, B=None, first=0):
@@ -88,6 +108,25 @@ def _work(arg):
     return lo, ey, cert, method
 
 
+def save(name, ey, kkt_max, method):
+    """Writes set `name` whole, or as parts of a power-of-two number of paths when its e_y exceeds FILE_BYTES (kkt_max of every part: the whole set's)."""
+    nb, N = ey.shape
+    b0 = batch_of(name, 1)
+    note = (f"exact optima of set '{name}' ({['KP', 'KPC', 'K'][b0.formulation]}, N = {b0.N}, keep = {b0.keep}, {nb} paths, path ids 0..{nb - 1}): "
+            "e_y[b, j] as float32; kkt_max = max over paths of (stationarity, primal violation, complementarity); method 1..3 = active set from ADMM at "
+            "1e-6 / 1e-7 / 1e-8, 9 = ADMM at 1e-10")
+    for f in glob.glob(os.path.join(HERE, f"tight_full_{name}.npz")) + glob.glob(os.path.join(HERE, f"tight_full_{name}_part[0-9][0-9].npz")):
+        os.remove(f)
+    if ey.nbytes <= FILE_BYTES:
+        np.savez_compressed(os.path.join(HERE, f"tight_full_{name}.npz"), e_y=ey, kkt_max=kkt_max, method=method, note=note)
+        return
+    per = 2 ** int(np.log2(FILE_BYTES // (4 * N)))
+    for i, lo in enumerate(range(0, nb, per)):
+        hi = min(nb, lo + per)
+        np.savez_compressed(os.path.join(HERE, f"tight_full_{name}_part{i:02d}.npz"), e_y=ey[lo:hi], kkt_max=kkt_max, method=method[lo:hi],
+                            note=note + f"; this part: paths {lo}..{hi - 1}")
+
+
 def main():
     names = sys.argv[1:] or list(SETS)
     nproc = int(os.environ.get("PO_GOLDEN_PROCS", os.cpu_count() or 1))
@@ -99,11 +138,7 @@ def main():
             parts = sorted(pool.map(_work, jobs, chunksize=1), key=lambda t: t[0])
         ey = np.concatenate([t[1] for t in parts]); cert = np.concatenate([t[2] for t in parts]); method = np.concatenate([t[3] for t in parts])
         assert len(ey) == nb and cert.max() < 2e-6, (len(ey), cert.max())  # (KPC: rows weighted 1e5 -> stationarity ~4e-7 absolute)
-        b0 = batch_of(name, 1)
-        np.savez_compressed(os.path.join(HERE, f"tight_full_{name}.npz"), e_y=ey.astype(np.float32), kkt_max=cert.max(axis=0), method=method,
-                            note=f"exact optima of set '{name}' ({['KP', 'KPC', 'K'][b0.formulation]}, N = {b0.N}, keep = {b0.keep}, {nb} paths, path ids 0..{nb - 1}): "
-                                 "e_y[b, j] as float32; kkt_max = max over paths of (stationarity, primal violation, complementarity); method 1..3 = active set from ADMM at "
-                                 "1e-6 / 1e-7 / 1e-8, 9 = ADMM at 1e-10")
+        save(name, ey.astype(np.float32), cert.max(axis=0), method)
         print(name, "paths", nb, "methods", np.bincount(method), "max kkt", cert.max(axis=0), flush=True)
 
 

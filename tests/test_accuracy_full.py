@@ -1,6 +1,6 @@
 """The accuracy clause of the metric on WHOLE batches (SURVEY.md §8d parity bar: per path, lateral-offset RMS against the tight solution <= 1e-4 m).
 
-Yardstick: tests/golden/tight_full_<set>.npz — the exact optimum of EVERY path of BASELINE config 3 (4096), config 2 (1024), config 5 (KPC, N = 400: all 4096 since
+Yardstick: tests/golden/tight_full_<set>[_part<ii>].npz — the exact optimum of EVERY path of BASELINE config 3 (4096), config 2 (1024), config 5 (KPC, N = 400: all 4096 since
 round 4), the K formulation (4096) and of 1024 paths of the keep-3 / N = 231 shape the reference's own pipeline hands the QP (generator make_tight_full.py: oracle
 ADMM to 1e-6, then a primal-dual active-set solve on the full KKT system, KKT residuals <= 3e-14; 4e-7 absolute on KPC).  Setting under test: the one bench.py
 reports as `value` (bench.HEADLINE) — since round 4 the Newton refinement (po_params.refine = 2) entered after the first termination check, refine_eps 1e-8 plus the final Newton correction steps (refine_newton_final), the
@@ -18,13 +18,13 @@ from path_optimizer_amd import synth
 HERE = os.path.dirname(os.path.abspath(__file__))
 import sys
 sys.path.insert(0, os.path.join(HERE, "golden"))
-from make_tight_full import SETS, batch_of, e_y_of  # noqa: E402
+from make_tight_full import SETS, batch_of, e_y_of, load_tight_full  # noqa: E402
 
 HEADLINE = dict(refine=2, refine_rounds=5, refine_extra_rounds=2, refine_eps=1e-8, refine_chain=2)
 
 
 def _gold(name):
-    return np.load(os.path.join(HERE, "golden", f"tight_full_{name}.npz"))["e_y"].astype(np.float64)
+    return load_tight_full(name)["e_y"].astype(np.float64)
 
 
 def _rms(b, xs, gold):
@@ -34,7 +34,7 @@ def _rms(b, xs, gold):
 
 def test_fixtures_cover_the_batches_the_metric_is_quoted_on():
     for name, (cfg, kw, nb) in SETS.items():
-        g = np.load(os.path.join(HERE, "golden", f"tight_full_{name}.npz"))
+        g = load_tight_full(name)
         b = batch_of(name, 2)
         assert g["e_y"].shape == (nb, b.N) and g["e_y"].dtype == np.float32
         assert float(g["kkt_max"].max()) < 2e-6  # solver-independent KKT certificate of every stored point (KP / K: 3e-14; KPC: 4e-7 absolute on rows weighted 1e5)

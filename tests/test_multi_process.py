@@ -113,6 +113,47 @@ def test_bench_gpus_flag_means_n_gpus_without_torchrun():
     assert [q["paths"] for q in rk["ranks"]] == [[0, 64], [64, 128]]
 
 
+def test_bench_dump_outputs_of_the_last_step_dry_run(tmp_path):
+    """--dump-outputs on the N>1 branch (dry run): the gathered states and po_info fields of every path, in global path order, as float64 .npy;
+    a plain run (no --full) prints the headline line without the secondary legs."""
+    import json
+    import subprocess
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "40", "--dry-run",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 3 and abs(d["ms_per_step"] - 12.5) < 1e-9 and "osqp_default" not in d and d["value_osqp_faithful"] is None
+    files = {f: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(v.dtype == np.float64 for v in files.values())
+    ids = np.arange(2 * 40)
+    assert np.array_equal(files["path_ids.npy"], ids)
+    assert files["states.npy"].shape == (80, 200, 5) and np.array_equal(files["states.npy"][:, 0, 0], ids)
+    assert np.array_equal(files["info_iters.npy"], 25 * (1 + (ids * 2654435761 % 61))) and (files["info_status.npy"] == 1).all()
+
+
+def test_bench_dump_outputs_samples_a_batch_beyond_the_budget(tmp_path, monkeypatch):
+    """Beyond the byte budget the dump keeps a fixed, seeded sample of paths: the same rows in every file, the same rows in every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from path_optimizer_amd.abi import INFO_DTYPE
+
+    B, N = 50, 7
+    states = np.arange(B * N * 5, dtype=np.float64).reshape(B, N, 5)
+    info = np.zeros(B, dtype=INFO_DTYPE)
+    info["iters"] = np.arange(B)
+    per_path = 8 * (N * 5 + 10)
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 20 * per_path)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), states, info, 100)
+    ids = np.load(tmp_path / "a" / "path_ids.npy")
+    assert len(ids) == 20 and np.array_equal(ids, np.load(tmp_path / "b" / "path_ids.npy")) and (np.diff(ids) > 0).all()
+    rows = (ids - 100).astype(int)
+    assert np.array_equal(np.load(tmp_path / "a" / "states.npy"), states[rows]) and np.array_equal(np.load(tmp_path / "a" / "info_iters.npy"), rows)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 20 * per_path + 11 * 128  # + the .npy headers
+
+
 def test_bench_refuses_a_world_that_is_not_gpus():
     """Under torchrun with WORLD_SIZE != --gpus the bench exits non-zero instead of printing a line labelled with the wrong GPU count."""
     import subprocess

@@ -14,7 +14,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-from make_tight_full import batch_of, e_y_of  # noqa: E402
+from make_tight_full import batch_of, e_y_of, load_tight_full  # noqa: E402
 
 # the setting `value` is quoted at (bench.py HEADLINE): the Newton phase is entered as soon as OSQP's test holds at 1e4 x eps (= the first check, 25 iterations)
 NEWTON = dict(refine=2, refine_rounds=5, refine_extra_rounds=2, refine_eps=1e-8, refine_chain=2)
@@ -27,7 +27,7 @@ def _set(p, **kw):
 
 
 def _gold(name, nb):
-    return np.load(os.path.join(HERE, "golden", f"tight_full_{name}.npz"))["e_y"].astype(np.float64)[:nb]
+    return load_tight_full(name)["e_y"].astype(np.float64)[:nb]
 
 
 def _rms(batch, xs, gold):
@@ -55,7 +55,7 @@ def test_oracle_newton_certifies_every_path_at_the_exact_optimum(oracle, name, B
 def test_oracle_newton_on_the_paths_the_activity_weighted_refinement_cycled_on(oracle):
     """BASELINE config 3, the paths on which round 3's refine = 1 cycled (1 500 - 1 900 iterations each; removed in round 5): tens of Newton steps."""
     hard = [2410, 3341, 2637, 539, 460, 3877, 1178, 3261, 1857]
-    gold = np.load(os.path.join(HERE, "golden", "tight_full_c3.npz"))["e_y"].astype(np.float64)
+    gold = load_tight_full("c3")["e_y"].astype(np.float64)
     p2 = _set(oracle.device_equivalent_params(), **NEWTON)
     for pid in hard:
         b = batch_of("c3", 1, pid)

@@ -11,7 +11,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-from make_tight_full import SETS, batch_of, e_y_of  # noqa: E402
+from make_tight_full import SETS, batch_of, e_y_of, load_tight_full  # noqa: E402
 
 
 def main():
@@ -37,7 +37,7 @@ def main():
     t0 = time.time()
     ost, oinfo, oxs = O.solve_batch(b, O.device_equivalent_params(p))
     print(f"oracle {time.time() - t0:.1f} s")
-    gold = np.load(os.path.join(ROOT, "tests", "golden", f"tight_full_{name}.npz"))["e_y"].astype(np.float64)
+    gold = load_tight_full(name)["e_y"].astype(np.float64)
     nb = min(B, len(gold))
     ey = np.stack([e_y_of(b.formulation, b.N, xs[i]) for i in range(nb)])
     rms = np.sqrt(np.mean((ey - gold[:nb]) ** 2, axis=1))
