@@ -222,7 +222,7 @@ template <int F> inline bool has_uni_variant(const Shape &s) { return s.two && (
         PO_KP_SHAPES_W1(X) PO_KP_SHAPES_W2(X) PO_KP_SHAPES_W3(X)                                                                    \
     }                                                                                                                               \
     if constexpr (F == F_K) {                                                                                                       \
-        if (s.nwx == 1 && s.spl == 2 && s.nt == 64) X(2, 64, 1); if (s.nwx == 1 && s.spl == 2) X(2, 128, 1);                        \
+        if (s.nwx == 1 && s.spl == 2 && s.nt == 64) X(2, 64, 1);  /* (SPL 2 only for N <= 128: one wave) */                        \
     }                                                                                                                               \
     if constexpr (F != F_KP) {                                                                                                      \
         if (s.nwx == 1 && s.spl == 4 && s.nt == 64) X(4, 64, 1); if (s.nwx == 1 && s.spl == 4) X(4, 128, 1);                        \

@@ -3,7 +3,8 @@ VGPRs, AccVGPRs and LDS are not cleared between waves / workgroups, so such a re
 one-line change moves the register allocation (round 6: a condition that is never true put NaNs into the fall-back rounds of the ragged test batch).
 tools/ubench/poison.hip fills every VGPR / AccVGPR of every lane and all 160 KB of LDS on every CU with a pattern; this tool solves each case after a NaN-payload poison and after
 a zero poison (and once more after the NaN poison): results must be BITWISE equal.  Cases: the headline shape (sliced, unsliced), the ragged batch whose infeasible paths go
-through the fall-back rounds, KPC, K, role-split and multi-group shapes, the OSQP-faithful solve, the polish.
+through the fall-back rounds, KPC, K, role-split and multi-group shapes, every two-wave two-level shape, the wide role-split shapes, the four-wave single-level block,
+the OSQP-faithful solve, the polish.
 What it can and cannot see (round 6, second session): the poison reaches the FIRST kernel of a solve only — every later kernel sees the leftovers of the kernels
 before it — so for the Newton / fall-back kernels the three runs differ by which hardware wave slot a path lands on (the poison launch shifts the dispatcher), not by the pattern.
 That was enough to expose the bug of section 13 (a wave-uniform scalar lost on the last lane of paths with n_points % 4 != 0: run 2 differed from runs 0 and 1), but a "SAME" is a
@@ -26,11 +27,12 @@ def cases():
     import np_twin as T
     from path_optimizer_amd import synth
 
-    def rand(keep, N, B, seed):
+    def rand(keep, N, B, seed, form=0):
         rng = np.random.default_rng(seed)
-        insts = [T.random_instance(rng, N, ds=1.2 / keep * 0.999) for _ in range(B)]
+        insts = [T.random_instance(rng, N, ds=1.2 / keep * 0.999 if form == 0 else 0.2997) for _ in range(B)]
         st = lambda k: np.ascontiguousarray(np.stack([i[k] for i in insts]))
-        return synth.Batch(0, B, N, keep, st("ref_x"), st("ref_y"), st("ref_z"), st("ref_k"), st("ref_s"), st("bounds"), st("x0"), np.array([i["goal_z"] for i in insts]))
+        return synth.Batch(form, B, N, keep, st("ref_x"), st("ref_y"), st("ref_z"), st("ref_k"), st("ref_s"), st("bounds"), st("x0"), np.array([i["goal_z"] for i in insts]),
+                           st("max_k") if form == 1 else None, st("max_kp") if form == 1 else None)
 
     rag = synth.make_batch(3, B=333)
     rag.n_points = np.random.default_rng(5).integers(60, 201, size=333).astype(np.int32)
@@ -50,6 +52,17 @@ def cases():
         yield f"keep {keep} headline sliced 8", rand(keep, 150, 64, 7 + keep), HEAD, 8
     yield "keep 12 headline unsliced", rand(12, 150, 64, 19), HEAD, 0
     yield "keep 17 (single-level chain) OSQP-faithful", rand(17, 120, 16, 40), {}, None
+    # every two-wave (NT = 128) shape of the two-level mapping through the Newton kernels, unsliced (what the engine runs on these shapes) and sliced (the parked state block);
+    # the wide role-split shapes not above; the four-wave (256, 4) single-level block (tests/shape_table.py)
+    for keep, N in ((1, 400), (2, 400), (4, 400), (6, 300), (7, 400), (8, 400)):
+        for sl in (0, 8):
+            yield f"two-wave keep {keep} N {N} headline " + ("unsliced" if sl == 0 else "sliced 8"), rand(keep, N, 48, 70 + keep), HEAD, sl
+    for sl in (0, 8):
+        yield "two-wave K N 300 headline " + ("unsliced" if sl == 0 else "sliced 8"), rand(1, 300, 48, 77, form=2), HEAD, sl
+    for keep in (9, 11, 13, 14, 16):
+        yield f"wide keep {keep} headline sliced 8", rand(keep, 150, 64, 7 + keep), HEAD, 8
+    yield "single-level (256, 4) keep 4 N 700 OSQP-faithful", rand(4, 700, 32, 84), {}, None
+    yield "single-level (256, 4) KPC N 600 OSQP-faithful", rand(4, 600, 32, 85, form=1), {}, None
 
 
 def main():
