@@ -132,7 +132,8 @@ typedef struct po_params {
                                            warm start, the Newton refinement of round 0 as a launch of its own, and a fallback launch that takes the paths it did not
                                            certify (rare) through their later rounds.  2: the fallback launch is issued only when a path needs it — the engine reads a
                                            4-byte count back, so the device-pointer entry returns when the Newton launch has FINISHED (it blocks; the launch it saves
-                                           costs 0.5 ms; a stream that is being captured is detected and treated as 3); 3: always issued, fully asynchronous. */
+                                           costs 0.5 ms; a stream that is being captured is detected and treated as 3 — warm the handle up with one eager call of the
+                                           same shape first: a handle does not allocate during capture); 3: always issued, fully asynchronous. */
     int    refine_extra_rounds;         /* 0.  E > 0: a path that the last regular round does not certify at refine_eps continues BELOW eps — type-based iteration at
                                            eps / 10, refinement again, eps / 100, ... — for up to E more rounds.  A path returned after them is certified, or satisfies
                                            OSQP's test at eps / 10^E — or ran out of max_iter in one of these rounds: then the point it ends on is tested against OSQP's
@@ -261,8 +262,15 @@ int po_keep_control_steps(int formulation, const double *ref_s, int N);
 /* Number of HIP devices visible to the process (0 when there is none, or no driver): one handle per device is how a batch is spread over the GPUs of a
  * node (host/include/path_optimizer_amd/solver.hpp: OsqpSolver::solveBatch over several PoEngine). */
 int po_device_count(void);
-/* One handle = one HIP device + one stream; calls on a handle are serialised; distinct handles (same device or not) may be used concurrently
- * from different host threads. */
+/* One handle = one HIP device + one stream.  Distinct handles (same device or not) may be used concurrently from different host threads.
+ * ONE handle may be called from several host threads too, on any of its entries: each call is atomic — a host-pointer entry (and po_plan_batch*) holds the handle's
+ * call lock from before it stages its inputs until its results have been read back, so no other call sees or reuses its staging blocks in between; a device-pointer
+ * entry takes the handle's inner lock while it enqueues, owns no staging, and its scratch is ordered by the stream.  The library orders the calls; every call returns
+ * what it would return in SOME serial order of the calls, i.e. what the same call returns on a handle nobody else uses (results do not depend on what a handle ran
+ * before: tests/test_handle_contract.py).  Two calls on one handle never overlap on the device — use two handles for that.
+ * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
+ * start afterwards use the new stream / map / switch, and the caller orders what is already enqueued on the old stream.  po_last_kernel_ms / po_last_phase_ms
+ * describe the handle's last solve, whichever thread made it.  po_destroy must not race with any call. */
 int po_create(int device, const po_params *params, po_handle *out);
 int po_destroy(po_handle h);
 /* Use an existing hipStream_t (e.g. torch's current stream); NULL = the handle's own stream. */

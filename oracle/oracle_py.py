@@ -73,16 +73,9 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-_KEEP = []
-
-
 def _i32(a):
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    _KEEP.append(a)
-    del _KEEP[:-4]
-    return a
+    """int32 view / copy of an optional index array; the caller holds it in a local until its C call has returned."""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
 
 
 def default_params() -> PoParams:
@@ -179,18 +172,19 @@ def device_equivalent_params(params=None):
 
 def _batch_structs(batch, want_x):
     n, m, _ = dims(batch.formulation, batch.N, batch.keep)
+    npts = _i32(getattr(batch, 'n_points', None))
     bi = PoBatchIn(batch.formulation, batch.B, batch.N, batch.keep, _p(batch.ref_x), _p(batch.ref_y), _p(batch.ref_z),
-                   _p(batch.ref_k), _p(batch.ref_s), _p(batch.bounds), _p(batch.x0), _p(batch.goal_z), _p(batch.max_k), _p(batch.max_kp), _p(_i32(getattr(batch, 'n_points', None))))
+                   _p(batch.ref_k), _p(batch.ref_s), _p(batch.bounds), _p(batch.x0), _p(batch.goal_z), _p(batch.max_k), _p(batch.max_kp), _p(npts))
     states = np.zeros((batch.B, batch.N, 5)); info = np.zeros(batch.B, dtype=INFO_DTYPE)
     xs = np.zeros((batch.B, n)) if want_x else None
     bo = PoBatchOut(_p(states), _p(info), _p(xs))
-    return bi, bo, states, info, xs
+    return bi, bo, states, info, xs, npts
 
 
 def solve_batch(batch, params=None, want_x=True):
     """Sequential CPU solve of a synth.Batch. Returns states [B,N,5], info (structured), x [B,n]."""
     params = params or default_params()
-    bi, bo, states, info, xs = _batch_structs(batch, want_x)
+    bi, bo, states, info, xs, _npts = _batch_structs(batch, want_x)  # (_npts: alive until the C call has returned)
     rc = lib().po_oracle_solve_batch(C.byref(params), C.byref(bi), C.byref(bo))
     if rc:
         raise RuntimeError(f"po_oracle_solve_batch rc={rc}")

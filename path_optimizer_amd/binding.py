@@ -107,16 +107,10 @@ def _np(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-_KEEP = []
-
-
 def _i32(a):
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    _KEEP.append(a)  # keep alive for the duration of the call
-    del _KEEP[:-4]
-    return a
+    """int32 view / copy of an optional index array.  The CALLER holds the result in a local until its C call has returned: the PoBatchIn / PoSplineIn ... structs
+    store the bare address only (no module-level parking: another thread's calls would drop an array this thread's C call is still reading)."""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
 
 
 class Engine:
@@ -169,9 +163,10 @@ class Engine:
     def solve_batch(self, batch, want_x: bool = False, order=None):
         """order: optional permutation of range(B) — scheduling hint (po_batch_in.order), results do not depend on it."""
         n, m, _ = problem_dims(batch.formulation, batch.N, batch.keep)
+        npts, ordr = _i32(getattr(batch, 'n_points', None)), _i32(order)  # (locals: alive until po_solve_batch has returned)
         bi = PoBatchIn(batch.formulation, batch.B, batch.N, batch.keep, _np(batch.ref_x), _np(batch.ref_y), _np(batch.ref_z),
-                       _np(batch.ref_k), _np(batch.ref_s), _np(batch.bounds), _np(batch.x0), _np(batch.goal_z), _np(batch.max_k), _np(batch.max_kp), _np(_i32(getattr(batch, 'n_points', None))),
-                       _np(_i32(order)))
+                       _np(batch.ref_k), _np(batch.ref_s), _np(batch.bounds), _np(batch.x0), _np(batch.goal_z), _np(batch.max_k), _np(batch.max_kp), _np(npts),
+                       _np(ordr))
         states = np.zeros((batch.B, batch.N, 5))
         info = np.zeros(batch.B, dtype=INFO_DTYPE)
         xs = np.zeros((batch.B, n)) if want_x else None
@@ -181,15 +176,17 @@ class Engine:
 
     def assemble_batch(self, batch):
         n, m, _ = problem_dims(batch.formulation, batch.N, batch.keep)
+        npts = _i32(getattr(batch, 'n_points', None))
         bi = PoBatchIn(batch.formulation, batch.B, batch.N, batch.keep, _np(batch.ref_x), _np(batch.ref_y), _np(batch.ref_z),
-                       _np(batch.ref_k), _np(batch.ref_s), _np(batch.bounds), _np(batch.x0), _np(batch.goal_z), _np(batch.max_k), _np(batch.max_kp), _np(_i32(getattr(batch, 'n_points', None))))
+                       _np(batch.ref_k), _np(batch.ref_s), _np(batch.bounds), _np(batch.x0), _np(batch.goal_z), _np(batch.max_k), _np(batch.max_kp), _np(npts))
         l = np.zeros((batch.B, m)); u = np.zeros((batch.B, m)); dyn = np.zeros((batch.B, batch.N - 1, 3))
         _check(lib().po_assemble_batch(self._h, C.byref(bi), _np(l), _np(u), _np(dyn)))
         return l, u, dyn
 
     def scaling_batch(self, batch):
+        npts = _i32(getattr(batch, 'n_points', None))
         bi = PoBatchIn(batch.formulation, batch.B, batch.N, batch.keep, _np(batch.ref_x), _np(batch.ref_y), _np(batch.ref_z),
-                       _np(batch.ref_k), _np(batch.ref_s), _np(batch.bounds), _np(batch.x0), _np(batch.goal_z), _np(batch.max_k), _np(batch.max_kp), _np(_i32(getattr(batch, 'n_points', None))))
+                       _np(batch.ref_k), _np(batch.ref_s), _np(batch.bounds), _np(batch.x0), _np(batch.goal_z), _np(batch.max_k), _np(batch.max_kp), _np(npts))
         out = np.zeros((batch.B, 64))
         _check(lib().po_scaling_batch(self._h, C.byref(bi), _np(out)))
         return out
@@ -217,7 +214,8 @@ class Engine:
         info = np.ascontiguousarray(info)
         B, N = states.shape[0], states.shape[1]
         nv = np.zeros(B, dtype=np.int32); ok = np.zeros(B, dtype=np.int32)
-        _check(lib().po_postcheck_batch(self._h, B, N, _np(_i32(n_points)), _np(states), _np(info), _np(nv), _np(ok)))
+        npts = _i32(n_points)
+        _check(lib().po_postcheck_batch(self._h, B, N, _np(npts), _np(states), _np(info), _np(nv), _np(ok)))
         return nv, ok
 
     def densify_batch(self, states, info, M: int, n_points=None):
@@ -226,7 +224,8 @@ class Engine:
         info = np.ascontiguousarray(info)
         B, N = states.shape[0], states.shape[1]
         out = np.zeros((B, M, 5)); n = np.zeros(B, dtype=np.int32); ok = np.zeros(B, dtype=np.int32)
-        _check(lib().po_densify_batch(self._h, B, N, _np(_i32(n_points)), _np(states), _np(info), M, _np(out), _np(n), _np(ok)))
+        npts = _i32(n_points)
+        _check(lib().po_densify_batch(self._h, B, N, _np(npts), _np(states), _np(info), M, _np(out), _np(n), _np(ok)))
         return out, n, ok
 
     def postcheck_batch_device(self, dev: "DeviceBatch", n_valid, ok):
@@ -245,8 +244,9 @@ class Engine:
         arr = {k: f(k) for k in ("ref_x", "ref_y", "ref_z", "ref_s", "knot_s", "knot_x", "knot_y")}
         B, N = arr["ref_x"].shape
         K = arr["knot_s"].shape[1]
-        bi = PoBoundsIn(B, N, K, _np(arr["ref_x"]), _np(arr["ref_y"]), _np(arr["ref_z"]), _np(arr["ref_s"]), _np(_i32(n_points)),
-                        _np(arr["knot_s"]), _np(arr["knot_x"]), _np(arr["knot_y"]), _np(_i32(n_knots)))
+        npts, nk = _i32(n_points), _i32(n_knots)
+        bi = PoBoundsIn(B, N, K, _np(arr["ref_x"]), _np(arr["ref_y"]), _np(arr["ref_z"]), _np(arr["ref_s"]), _np(npts),
+                        _np(arr["knot_s"]), _np(arr["knot_x"]), _np(arr["knot_y"]), _np(nk))
         bounds = np.zeros((B, N, 4, 2)); nv = np.zeros(B, dtype=np.int32)
         _check(lib().po_bounds_batch(self._h, C.byref(bi), _np(bounds), _np(nv)))
         return bounds, nv
@@ -270,7 +270,8 @@ class Engine:
         f = lambda k: None if inp.get(k) is None else np.ascontiguousarray(inp[k], dtype=np.float64)
         arr = {k: f(k) for k in ("x", "y", "angle", "k", "s", "lb", "ub", "l0")}
         B, P = arr["s"].shape
-        si = PoSmoothIn(kind, B, P, _np(_i32(inp.get("n_points"))), *[_np(arr[k]) for k in ("x", "y", "angle", "k", "s", "lb", "ub", "l0")])
+        npts = _i32(inp.get("n_points"))
+        si = PoSmoothIn(kind, B, P, _np(npts), *[_np(arr[k]) for k in ("x", "y", "angle", "k", "s", "lb", "ub", "l0")])
         ox = np.zeros((B, P)); oy = np.zeros((B, P)); os_ = np.zeros((B, P))
         info = np.zeros(B, dtype=INFO_DTYPE)
         raw = np.zeros((B, smooth_dims(kind, P)[0])) if want_raw else None
@@ -296,7 +297,7 @@ class Engine:
         arr = {k: np.ascontiguousarray(sp[k], dtype=np.float64) for k in ("knot_s", "knot_x", "knot_y")}
         arr["length"] = np.ascontiguousarray(length, dtype=np.float64)
         B, K = arr["knot_s"].shape
-        nk = _i32(n_knots)
+        nk = arr["n_knots"] = _i32(n_knots)  # (travels with `arr`, which the caller holds until its C call has returned)
         return PoSplineIn(B, K, _np(arr["knot_s"]), _np(arr["knot_x"]), _np(arr["knot_y"]), _np(nk), _np(arr["length"])), arr, B
 
     def resample_batch(self, sp: dict, length, ds_smaller: float, ds_larger: float, N: int, n_knots=None):
@@ -314,7 +315,8 @@ class Engine:
         v = np.ascontiguousarray(v, dtype=np.float64); a = np.ascontiguousarray(a, dtype=np.float64)
         B, N = v.shape
         mk = np.zeros((B, N)); mkp = np.zeros((B, N))
-        _check(lib().po_limits_batch(self._h, B, N, _np(_i32(n_points)), _np(v), _np(a), _np(mk), _np(mkp)))
+        npts = _i32(n_points)
+        _check(lib().po_limits_batch(self._h, B, N, _np(npts), _np(v), _np(a), _np(mk), _np(mkp)))
         return mk, mkp
 
     def dp_search_batch(self, sp: dict, length, start, L: int, n_knots=None):
@@ -353,7 +355,8 @@ class Engine:
         wx = np.ascontiguousarray(way_x, dtype=np.float64); wy = np.ascontiguousarray(way_y, dtype=np.float64)
         st = np.ascontiguousarray(start, dtype=np.float64); gl = np.ascontiguousarray(goal, dtype=np.float64)
         B, W = wx.shape
-        pi = PoPlanIn(B, W, _np(_i32(n_way)), _np(wx), _np(wy), _np(st), _np(gl), float(max_length), N)
+        nw = _i32(n_way)
+        pi = PoPlanIn(B, W, _np(nw), _np(wx), _np(wy), _np(st), _np(gl), float(max_length), N)
         states = np.zeros((B, N, 5)); n = np.zeros(B, dtype=np.int32); ok = np.zeros(B, dtype=np.int32); stage = np.zeros(B, dtype=np.int32)
         info = np.zeros(B, dtype=INFO_DTYPE)
         po = PoPlanOut(_np(states), _np(n), _np(ok), _np(stage), _np(info))

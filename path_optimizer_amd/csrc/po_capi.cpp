@@ -143,8 +143,12 @@ struct po_handle_s {
     int env_smooth_waves = 0;
     DevBuf in_buf, out_buf, asm_buf, scale_buf, dbg_buf, map_buf, post_buf, coef_buf, bnd_buf, smooth_buf, smooth_io, plan_coef, plan_io, plan_arena, plan_host;
     po::DevMap map{};  // obstacle-distance layer (po_set_map); map.d == nullptr until set
+    // Two locks, always taken in the order call_mu -> mu:
+    // mu       guards the handle's fields and grow-only blocks while a device-pointer entry reads them and enqueues its launches;
+    // call_mu  is the CALL lock: every host-pointer entry (and po_plan_batch*, whose stages share the plan arena) holds it from before its first ensure() until its
+    //          last read-back has been synchronised, so staging, launch and read-back of one call are atomic with respect to every other call on the handle.
     std::mutex mu;
-    std::mutex plan_mu;  // held for a whole po_plan_batch* call: its stages share the plan arena
+    std::mutex call_mu;
 };
 
 extern "C" {
@@ -583,6 +587,7 @@ int po_solve_batch(po_handle h, const po_batch_in *in, const po_batch_out *out) 
     }
     const size_t in_bytes = sizeof(double) * (B * N * per_pt + B * 4 + 2 * ((B + 1) / 2 + 1));
     const size_t out_bytes = sizeof(double) * (B * N * 5 + (out->x ? B * (size_t)n : 0)) + sizeof(po_info) * B;
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         if ((rc = h->in_buf.ensure(in_bytes)) || (rc = h->out_buf.ensure(out_bytes)) || (rc = h->pin_in.ensure(in_bytes)) || (rc = h->pin_out.ensure(out_bytes))) return rc;
@@ -693,6 +698,7 @@ int po_assemble_batch(po_handle h, const po_batch_in *in, double *l, double *u, 
     const size_t per_pt = 13 + (kpc ? 2 : 0);
     const size_t in_bytes = sizeof(double) * (B * N * per_pt + B * 4);
     const size_t a_bytes = sizeof(double) * (2 * B * (size_t)m + B * (N - 1) * 3);
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         if ((rc = h->in_buf.ensure(in_bytes)) || (rc = h->asm_buf.ensure(a_bytes))) return rc;
@@ -734,6 +740,7 @@ int po_scaling_batch(po_handle h, const po_batch_in *in, double *out) {
     if (in->B == 0) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = in->B, N = in->N;
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         if ((rc = h->in_buf.ensure(sizeof(double) * B * N)) || (rc = h->scale_buf.ensure(sizeof(double) * 64 * B))) return rc;
@@ -818,6 +825,7 @@ int po_densify_batch(po_handle h, int B, int N, const int *n_points, const doubl
     if (B == 0) return PO_OK;
     const size_t bs = sizeof(double) * 5 * (size_t)B * N, bo = sizeof(double) * 5 * (size_t)B * M, bi = sizeof(po_info) * (size_t)B, bn = sizeof(int) * (size_t)B;
     char *base = nullptr;
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
@@ -844,6 +852,7 @@ int po_postcheck_batch(po_handle h, int B, int N, const int *n_points, const dou
     if (B == 0) return PO_OK;
     const size_t bs = sizeof(double) * 5 * (size_t)B * N, bi = sizeof(po_info) * (size_t)B, bn = sizeof(int) * (size_t)B;
     char *base = nullptr;
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
@@ -892,6 +901,7 @@ int po_bounds_batch(po_handle h, const po_bounds_in *in, double *bounds, int *n_
     const size_t bn = sizeof(double) * (size_t)in->B * in->N, bk = sizeof(double) * (size_t)in->B * in->K, bi = sizeof(int) * (size_t)in->B;
     const size_t bo = sizeof(double) * (size_t)in->B * in->N * 8;
     char *base = nullptr;
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
@@ -999,6 +1009,7 @@ int po_smooth_batch(po_handle h, const po_smooth_in *in, const po_smooth_out *ou
     const size_t binfo = sizeof(po_info) * (size_t)in->B, braw = out->raw ? sizeof(double) * (size_t)in->B * nmax : 0;
     char *base = nullptr;
     const void *src[7] = {in->x, in->y, in->angle, in->k, in->s, in->lb, in->ub};
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
@@ -1114,6 +1125,7 @@ int po_resample_batch(po_handle h, const po_spline_in *in, double ds_smaller, do
     if (in->B == 0) return PO_OK;
     const size_t bn = sizeof(double) * (size_t)in->B * N, bi = sizeof(int) * (size_t)in->B;
     StagedSpline S{};
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
@@ -1136,6 +1148,7 @@ int po_limits_batch(po_handle h, int B, int N, const int *n_points, const double
     if (B == 0) return PO_OK;
     const size_t bn = sizeof(double) * (size_t)B * N, bi = sizeof(int) * (size_t)B;
     char *base = nullptr;
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
@@ -1161,6 +1174,7 @@ int po_dp_search_batch(po_handle h, const po_spline_in *in, const double *start,
     if (in->B == 0) return PO_OK;
     const size_t bl = sizeof(double) * (size_t)in->B * L, bs = sizeof(double) * 3 * (size_t)in->B, bb = sizeof(double) * (size_t)in->B, bi = sizeof(int) * (size_t)in->B;
     StagedSpline S{};
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
@@ -1185,6 +1199,7 @@ int po_dp_search_batch(po_handle h, const po_spline_in *in, const double *start,
 
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside) {
     if (!h || n < 0 || (n > 0 && (!xy || !dist || !inside))) return PO_ERR_INVALID;
+    std::lock_guard<std::mutex> call(h->call_mu);  // (post_buf is the staging block of po_postcheck_batch / po_densify_batch too)
     std::lock_guard<std::mutex> g(h->mu);
     if (!h->map.d) return PO_ERR_INVALID;
     if (n == 0) return PO_OK;
@@ -1210,7 +1225,7 @@ const po_params *po_internal_params(po_handle h) { return &h->params; }
 int po_internal_has_map(po_handle h) { return h->map.d != nullptr; }
 int po_internal_hip_fail(hipError_t e, const char *what) { return hip_ok(e, what) ? 0 : 1; }
 void *po_internal_plan_host(po_handle h, size_t bytes) { return h->plan_host.ensure(bytes) == PO_OK ? h->plan_host.p : nullptr; }
-std::mutex *po_internal_plan_mutex(po_handle h) { return &h->plan_mu; }
+std::mutex *po_internal_plan_mutex(po_handle h) { return &h->call_mu; }
 
 const char *po_strerror(int code) {
     switch (code) {
