@@ -268,7 +268,7 @@ int po_device_count(void);
  * entry takes the handle's inner lock while it enqueues, owns no staging, and its scratch is ordered by the stream.  The library orders the calls; every call returns
  * what it would return in SOME serial order of the calls, i.e. what the same call returns on a handle nobody else uses (results do not depend on what a handle ran
  * before: tests/test_handle_contract.py).  Two calls on one handle never overlap on the device — use two handles for that.
- * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
+ * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_set_map_occupancy* / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
  * start afterwards use the new stream / map / switch, and the caller orders what is already enqueued on the old stream.  po_last_kernel_ms / po_last_phase_ms
  * describe the handle's last solve, whichever thread made it.  po_destroy must not race with any call. */
 int po_create(int device, const po_params *params, po_handle *out);
@@ -285,7 +285,8 @@ int po_set_stream(po_handle h, void *hip_stream);
  * BASELINE KP / K shapes, <= 1e-10 elsewhere); BASELINE config 3: 4.76 -> 4.06 ms).  Unknown key: PO_ERR_INVALID. */
 int po_debug_set(po_handle h, const char *key, int value);
 /* Developer read-back (synchronises the stream): "fallback_paths" = how many paths the Newton launch of the last solve with refine = 2 did not certify and handed to
- * the fallback launch; "newton_parked" = how many went on into the second of the sliced Newton launches (-1: the last solve was not sliced). */
+ * the fallback launch; "newton_parked" = how many went on into the second of the sliced Newton launches (-1: the last solve was not sliced); "map_ptr" = the device
+ * address of the handle's map layer (0: no map; does not synchronise — po_set_map_occupancy_device with an unchanged size must leave it where it is). */
 int po_debug_get(po_handle h, const char *key, long long *value);
 
 /* Host-pointer entry: H2D, solve, D2H, synchronous. */
@@ -295,6 +296,37 @@ int po_solve_batch_device(po_handle h, const po_batch_in *in, const po_batch_out
 /* ---- post-solve step: PathOptimizer::optimizePath, src/path_optimizer/path_optimizer.cpp:183-200 ----
  * Upload the obstacle-distance layer (host pointer in `map->distance`) to the handle's device; kept until replaced. */
 int po_set_map(po_handle h, const po_map *map);
+/* ---- the obstacle-distance layer from an occupancy image, on the device (csrc/po_edt.hip) ----
+ * What a planner has is an occupancy image; the reference's callers turn it into the layer on the host (src/test/path_optimizer_benchmark.cpp:38-43, demo.cpp:108):
+ *     cv::distanceTransform(binary, distance, CV_DIST_L2, CV_DIST_MASK_PRECISE);  distance *= resolution;
+ * The entries below compute exactly that layer, the EXACT Euclidean distance transform:
+ *     d2(i, j)   = min over occupied cells (p, q) of (i - p)^2 + (j - q)^2                 (exact integer)
+ *     dist(i, j) = float32(sqrt(double(d2(i, j)))) * float32(resolution)                    (correctly rounded root, one float32 multiply; occupied cells: +0.0f)
+ * a function of exact integers: results are bit-identical to that definition, not merely close to it.
+ * An image WITHOUT any occupied cell has no distance; OpenCV's answer there is an artefact of its table initialisation that nothing in the reference pins.  This
+ * library's own choice: every cell gets float32(sqrt(double(size_x^2 + size_y^2))) * float32(resolution) — farther than any cell of the map can be from an
+ * obstacle inside it, and finite, so the bilinear sampler stays finite.
+ * `cells` is unsigned char, 0 = occupied, anything else free (cv::distanceTransform's convention, the reference's OCCUPY = 0), in po_map's layout:
+ * [size_y][size_x] in memory, x contiguous, image after image for a batch; layer(i, j) = image(i, j).
+ * Limits: 1 <= size_x, size_y <= 4096 and M <= 65535; beyond: PO_ERR_UNSUPPORTED.  Deterministic: integers and one rounding per cell, no atomics. */
+typedef struct po_occupancy {
+    const unsigned char *cells;  /* [M][size_y][size_x], 0 = occupied */
+    int    size_x, size_y;
+    double resolution, pos_x, pos_y;  /* as po_map (the raw transform reads resolution only) */
+} po_occupancy;
+/* The raw transform: M images of one size in, M float layers [M][size_y][size_x] out; the handle's map is not touched. */
+int po_distance_map_batch(po_handle h, int M, const po_occupancy *occ, float *distance);         /* host pointers, synchronous */
+int po_distance_map_batch_device(po_handle h, int M, const po_occupancy *occ, float *distance);  /* device pointers, on the stream */
+/* Build the handle's map from ONE image: what po_set_map does, minus the host transform.  Afterwards the handle's map is indistinguishable from one installed by
+ * po_set_map with the same layer.  Host entry: uploads 1 byte per cell, synchronous.  Device entry: `occ->cells` is a device pointer and the transform is enqueued on
+ * the handle's stream, straight into the handle's map buffer: with the size the handle already holds it allocates nothing and does not synchronise, so a per-cycle
+ * refresh followed by po_plan_batch_device is ordered by the stream alone (the image must stay valid until the stream has passed the call).  When a buffer has to
+ * grow, the entry first synchronises the stream — everything enqueued earlier that reads the old buffer has finished — and only then releases it. */
+int po_set_map_occupancy(po_handle h, const po_occupancy *occ);
+int po_set_map_occupancy_device(po_handle h, const po_occupancy *occ);
+/* Read the handle's current map back: geometry into *geometry_out (its `distance` is set to NULL) and, when distance_or_null is given, the layer
+ * [size_y][size_x] into that host buffer.  Synchronous.  PO_ERR_INVALID when no map is set. */
+int po_get_map(po_handle h, po_map *geometry_out, float *distance_or_null);
 /* For every path: walk the optimised states in order and stop at the first state that fails
  * CollisionChecker::isSingleStateCollisionFreeImproved (src/tools/collision_checker.cpp:42-59: bounding circle, then the
  * six footprint circles of src/tools/car_geometry.cpp:38-72; outside the map = collision).
@@ -485,9 +517,10 @@ int po_last_phase_ms(po_handle h, float *ms8);
 const char *po_strerror(int code);
 const char *po_last_hip_error(void);
 /* "po_hip <abi> (gfx950)"; PO_ABI_VERSION is bumped whenever a struct layout, an entry point or the meaning of a field changes (5: round 5, see po_params.refine;
- * 6: round 6, po_info.status_refine / status_polish may be PO_NOT_AVAILABLE; po_create refuses refine_rounds + refine_extra_rounds >= 32).  A binding should compare
+ * 6: round 6, po_info.status_refine / status_polish may be PO_NOT_AVAILABLE; po_create refuses refine_rounds + refine_extra_rounds >= 32; 7: po_occupancy,
+ * po_distance_map_batch*, po_set_map_occupancy*, po_get_map, po_debug_get "map_ptr").  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
-#define PO_ABI_VERSION 6
+#define PO_ABI_VERSION 7
 const char *po_version(void);
 
 #ifdef __cplusplus

@@ -1,5 +1,5 @@
 """ctypes mirror of include/po_hip.h (struct layouts and enums only; no behaviour)."""
-PO_ABI_VERSION = 6  # include/po_hip.h
+PO_ABI_VERSION = 7  # include/po_hip.h
 PO_NOT_AVAILABLE = -2  # po_info.status_refine / status_polish: asked for, no kernel for this shape
 import ctypes as C
 
@@ -37,6 +37,11 @@ class PoParams(C.Structure):
 
 class PoMap(C.Structure):
     _fields_ = [("distance", C.c_void_p), ("size_x", C.c_int), ("size_y", C.c_int), ("resolution", C.c_double),
+                ("pos_x", C.c_double), ("pos_y", C.c_double)]
+
+
+class PoOccupancy(C.Structure):
+    _fields_ = [("cells", C.c_void_p), ("size_x", C.c_int), ("size_y", C.c_int), ("resolution", C.c_double),
                 ("pos_x", C.c_double), ("pos_y", C.c_double)]
 
 

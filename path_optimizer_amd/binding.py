@@ -24,7 +24,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_bounds_batch_device", "po_map_sample", "po_smooth_dims", "po_smooth_batch", "po_smooth_batch_device",
            "po_resample_batch", "po_resample_batch_device", "po_limits_batch", "po_limits_batch_device", "po_dp_search_batch",
            "po_dp_search_batch_device", "po_bspline_batch_device", "po_segment_raw_batch_device", "po_post_project_batch_device",
-           "po_segment_init_batch_device", "po_plan_batch", "po_plan_batch_device", "po_densify_batch", "po_densify_batch_device"]
+           "po_segment_init_batch_device", "po_plan_batch", "po_plan_batch_device", "po_densify_batch", "po_densify_batch_device",
+           "po_distance_map_batch", "po_distance_map_batch_device", "po_set_map_occupancy", "po_set_map_occupancy_device", "po_get_map"]
 
 
 class PoError(RuntimeError):
@@ -64,6 +65,11 @@ def lib():
         L.po_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.po_last_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.po_debug_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_longlong)]
+        L.po_distance_map_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_distance_map_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_set_map_occupancy.argtypes = [C.c_void_p, C.c_void_p]
+        L.po_set_map_occupancy_device.argtypes = [C.c_void_p, C.c_void_p]
+        L.po_get_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -207,6 +213,64 @@ class Engine:
         d = np.asfortranarray(dist, dtype=np.float32)
         m = PoMap(d.ctypes.data_as(C.c_void_p), d.shape[0], d.shape[1], float(resolution), float(pos_x), float(pos_y))
         _check(lib().po_set_map(self._h, C.byref(m)))
+
+    # ---- the obstacle-distance layer from an occupancy image (po_edt.hip) ----
+    @staticmethod
+    def _occ_u8(occ):
+        """uint8 occupancy (0 = occupied, non-zero = free) of any array: other dtypes go through `!= 0`, never through a wrapping cast."""
+        a = np.asarray(occ)
+        return a if a.dtype == np.uint8 else (a != 0).astype(np.uint8)
+
+    def set_map_occupancy(self, occ, resolution, pos_x, pos_y):
+        """Build the handle's map from the occupancy image occ[size_x, size_y] (uint8, 0 = occupied, non-zero = free; same index convention as set_map's
+        `dist`): the exact Euclidean distance transform times `resolution` runs on the device, one byte per cell is uploaded."""
+        from .abi import PoOccupancy
+
+        o = np.asfortranarray(self._occ_u8(occ))
+        if o.ndim != 2:
+            raise ValueError("occ must be [size_x, size_y]")
+        oc = PoOccupancy(o.ctypes.data_as(C.c_void_p), o.shape[0], o.shape[1], float(resolution), float(pos_x), float(pos_y))
+        _check(lib().po_set_map_occupancy(self._h, C.byref(oc)))
+
+    def set_map_occupancy_device(self, occ, resolution, pos_x, pos_y):
+        """Device-pointer entry, enqueued on the handle's stream (no synchronisation; nothing is allocated when the size is the one the handle holds).
+        occ: torch uint8 tensor on the handle's device, indexed [size_x, size_y] like set_map's `dist` and laid out so that x is contiguous, i.e. with strides
+        (1, size_x): the transposed VIEW of a contiguous [size_y, size_x] image — `img_yx.t()`, or `torch.from_numpy(np.asfortranarray(occ_xy).T).to(dev).t()`.
+        The tensor must stay alive until the stream has passed the call."""
+        from .abi import PoOccupancy
+
+        if occ.dim() != 2 or str(occ.dtype) != "torch.uint8":
+            raise ValueError("occ must be a 2-d torch.uint8 tensor")
+        sx, sy = int(occ.shape[0]), int(occ.shape[1])
+        if (sx > 1 and occ.stride(0) != 1) or (sy > 1 and occ.stride(1) != sx):
+            raise ValueError("occ must be indexed [size_x, size_y] with strides (1, size_x): pass img_yx.t() of a contiguous [size_y, size_x] image")
+        oc = PoOccupancy(C.c_void_p(occ.data_ptr()), sx, sy, float(resolution), float(pos_x), float(pos_y))
+        _check(lib().po_set_map_occupancy_device(self._h, C.byref(oc)))
+
+    def distance_map_batch(self, occ, resolution):
+        """The raw transform (host-pointer entry; the handle's map is not touched): occ [M, size_x, size_y] (0 = occupied) -> float32 [M, size_x, size_y],
+        metres to the nearest occupied cell, bit-identical to float32(sqrt(d2)) * float32(resolution)."""
+        from .abi import PoOccupancy
+
+        o = self._occ_u8(occ)
+        if o.ndim != 3:
+            raise ValueError("occ must be [M, size_x, size_y]")
+        M, sx, sy = o.shape
+        img = np.ascontiguousarray(o.transpose(0, 2, 1))  # [M][size_y][size_x], x contiguous
+        out = np.empty((M, sy, sx), dtype=np.float32)
+        oc = PoOccupancy(img.ctypes.data_as(C.c_void_p), sx, sy, float(resolution), 0.0, 0.0)
+        _check(lib().po_distance_map_batch(self._h, M, C.byref(oc), _np(out)))
+        return out.transpose(0, 2, 1)
+
+    def get_map(self):
+        """The handle's current map, in set_map's argument order: (dist [size_x, size_y] float32, resolution, pos_x, pos_y) — eng2.set_map(*eng.get_map())."""
+        from .abi import PoMap
+
+        m = PoMap()
+        _check(lib().po_get_map(self._h, C.byref(m), None))
+        d = np.empty((m.size_x, m.size_y), dtype=np.float32, order="F")
+        _check(lib().po_get_map(self._h, C.byref(m), d.ctypes.data_as(C.c_void_p)))
+        return d, m.resolution, m.pos_x, m.pos_y
 
     def postcheck_batch(self, states, info, n_points=None):
         """Host-pointer entry: states [B,N,5], info structured array -> n_valid [B], ok [B]."""

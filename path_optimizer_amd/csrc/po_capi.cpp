@@ -5,6 +5,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -47,6 +48,10 @@ extern "C" hipError_t po_launch_limits(int B, int N, const int *n_points, const 
 extern "C" hipError_t po_launch_dp_search(const po::DevMap *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st);
 extern "C" size_t po_dp_lds_bytes(int K, int L);
 extern "C" size_t po_spline_lds_bytes(int K);
+extern "C" hipError_t po_launch_edt(const unsigned char *cells, int M, int sx, int sy, float res, void *scratch, float *out, hipStream_t st);
+extern "C" size_t po_edt_scratch_bytes(int M, int sx, int sy);
+extern "C" int po_edt_max_side(void);
+extern "C" int po_edt_max_images(void);
 extern "C" hipError_t po_launch_map_sample(const po::DevMap *m, int n, const double *xy, double *dist, int *inside, hipStream_t st);
 
 namespace {
@@ -142,6 +147,7 @@ struct po_handle_s {
     bool env_identity = false, env_cycles = false, env_smooth_seq = false, env_smooth_nopad = false, env_smooth_debug = false, env_dp_one_wave = false;
     int env_smooth_waves = 0;
     DevBuf in_buf, out_buf, asm_buf, scale_buf, dbg_buf, map_buf, post_buf, coef_buf, bnd_buf, smooth_buf, smooth_io, plan_coef, plan_io, plan_arena, plan_host;
+    DevBuf edt_buf, edt_io;  // occupancy -> distance transform: the 16-bit intermediate (2 bytes per cell); staging of the host-pointer entries (image + layers)
     po::DevMap map{};  // obstacle-distance layer (po_set_map); map.d == nullptr until set
     // Two locks, always taken in the order call_mu -> mu:
     // mu       guards the handle's fields and grow-only blocks while a device-pointer entry reads them and enqueues its launches;
@@ -273,6 +279,7 @@ int po_destroy(po_handle h) {
     h->fb_buf.release();
     h->nw_state_buf.release(); h->nw_idx_buf.release();
     h->in_buf.release(); h->out_buf.release(); h->asm_buf.release(); h->scale_buf.release(); h->dbg_buf.release(); h->map_buf.release(); h->post_buf.release(); h->coef_buf.release(); h->bnd_buf.release(); h->smooth_buf.release(); h->smooth_io.release(); h->plan_coef.release(); h->plan_io.release(); h->plan_arena.release(); h->plan_host.release();
+    h->edt_buf.release(); h->edt_io.release();
     h->pin_in.release(); h->pin_out.release(); h->fb_host.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -304,6 +311,10 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
     if (!h || !key || !value) return PO_ERR_INVALID;
     const std::string k(key);
     std::lock_guard<std::mutex> g(h->mu);
+    if (k == "map_ptr") {  // where the handle's map layer lives (0: none); no device call
+        *value = (long long)reinterpret_cast<uintptr_t>(h->map.d);
+        return PO_OK;
+    }
     if (k == "fallback_paths") {  // split scheduling of refine = 2: how many paths the last solve's Newton launch handed to the fallback launch
         *value = 0;
         if (!h->fb_buf.p) return PO_OK;
@@ -793,6 +804,97 @@ int po_set_map(po_handle h, const po_map *map) {
     HIP_TRY(hipMemcpyAsync(h->map_buf.p, map->distance, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->map = po::DevMap{static_cast<const float *>(h->map_buf.p), map->size_x, map->size_y, map->resolution, map->pos_x, map->pos_y};
+    return PO_OK;
+}
+
+// ---- the obstacle-distance layer from an occupancy image (po_edt.hip) ----------------------------------------------
+// Argument checks of every occupancy entry, before any device call (testable without a GPU)
+static int check_occupancy(po_handle h, int M, const po_occupancy *occ) {
+    if (!h || M < 1 || !occ || !occ->cells || occ->size_x < 1 || occ->size_y < 1 || !(occ->resolution > 0)) return PO_ERR_INVALID;
+    if (occ->size_x > po_edt_max_side() || occ->size_y > po_edt_max_side() || M > po_edt_max_images()) return PO_ERR_UNSUPPORTED;
+    return PO_OK;
+}
+// A grow-only block that launches already enqueued on the handle's stream may still read: they are finished before the old block is released.  (h->mu held.)
+static int grow_after_sync(po_handle h, DevBuf &buf, size_t bytes) {
+    if (bytes <= buf.cap) return PO_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return buf.ensure(bytes);
+}
+
+int po_distance_map_batch_device(po_handle h, int M, const po_occupancy *occ, float *distance) {
+    if (int rc = check_occupancy(h, M, occ)) return rc;
+    if (!distance) return PO_ERR_INVALID;
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = grow_after_sync(h, h->edt_buf, po_edt_scratch_bytes(M, occ->size_x, occ->size_y))) return rc;
+    HIP_TRY(po_launch_edt(occ->cells, M, occ->size_x, occ->size_y, (float)occ->resolution, h->edt_buf.p, distance, h->stream));
+    return PO_OK;
+}
+
+int po_distance_map_batch(po_handle h, int M, const po_occupancy *occ, float *distance) {
+    if (int rc = check_occupancy(h, M, occ)) return rc;
+    if (!distance) return PO_ERR_INVALID;
+    const size_t cells = (size_t)M * (size_t)occ->size_x * (size_t)occ->size_y, bo = sizeof(float) * cells, bc = (cells + 255) & ~(size_t)255;
+    char *base = nullptr;
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        HIP_TRY(hipSetDevice(h->device));
+        if (int rc = grow_after_sync(h, h->edt_io, bo + bc)) return rc;
+        base = static_cast<char *>(h->edt_io.p);
+        HIP_TRY(hipMemcpyAsync(base + bo, occ->cells, cells, hipMemcpyHostToDevice, h->stream));
+    }
+    po_occupancy dev = *occ;
+    dev.cells = reinterpret_cast<const unsigned char *>(base + bo);
+    if (int rc = po_distance_map_batch_device(h, M, &dev, reinterpret_cast<float *>(base))) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipMemcpyAsync(distance, base, bo, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return PO_OK;
+}
+
+int po_set_map_occupancy_device(po_handle h, const po_occupancy *occ) {
+    if (int rc = check_occupancy(h, 1, occ)) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    // same size as before: both blocks are large enough already — nothing is allocated, nothing waits; the transform overwrites the layer in stream order
+    const size_t layer_bytes = sizeof(float) * (size_t)occ->size_x * occ->size_y;
+    if (layer_bytes > h->map_buf.cap) h->map = po::DevMap{};  // the old layer is about to be released: no map until the new one is in place
+    if (int rc = grow_after_sync(h, h->map_buf, layer_bytes)) return rc;
+    if (int rc = grow_after_sync(h, h->edt_buf, po_edt_scratch_bytes(1, occ->size_x, occ->size_y))) return rc;
+    HIP_TRY(po_launch_edt(occ->cells, 1, occ->size_x, occ->size_y, (float)occ->resolution, h->edt_buf.p, static_cast<float *>(h->map_buf.p), h->stream));
+    h->map = po::DevMap{static_cast<const float *>(h->map_buf.p), occ->size_x, occ->size_y, occ->resolution, occ->pos_x, occ->pos_y};
+    return PO_OK;
+}
+
+int po_set_map_occupancy(po_handle h, const po_occupancy *occ) {
+    if (int rc = check_occupancy(h, 1, occ)) return rc;
+    const size_t cells = (size_t)occ->size_x * (size_t)occ->size_y;
+    po_occupancy dev = *occ;
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and the final synchronisation are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        HIP_TRY(hipSetDevice(h->device));
+        if (int rc = grow_after_sync(h, h->edt_io, cells)) return rc;
+        HIP_TRY(hipMemcpyAsync(h->edt_io.p, occ->cells, cells, hipMemcpyHostToDevice, h->stream));
+        dev.cells = static_cast<const unsigned char *>(h->edt_io.p);
+    }
+    if (int rc = po_set_map_occupancy_device(h, &dev)) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipStreamSynchronize(h->stream));  // like po_set_map: the caller's image may be reused, the map is in place
+    return PO_OK;
+}
+
+int po_get_map(po_handle h, po_map *geometry_out, float *distance_or_null) {
+    if (!h || !geometry_out) return PO_ERR_INVALID;
+    std::lock_guard<std::mutex> call(h->call_mu);
+    std::lock_guard<std::mutex> g(h->mu);
+    if (!h->map.d) return PO_ERR_INVALID;
+    *geometry_out = po_map{nullptr, h->map.sx, h->map.sy, h->map.res, h->map.px, h->map.py};
+    if (!distance_or_null) return PO_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(distance_or_null, h->map.d, sizeof(float) * (size_t)h->map.sx * h->map.sy, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return PO_OK;
 }
 

@@ -9,7 +9,8 @@
 //     (src/tools/collision_checker.cpp)                                   (po_postcheck_batch)
 //
 // The reference builds its Map from a grid_map::GridMap; here the caller hands over that layer's raw buffer
-// (gm["distance"].data(), gm.getSize(), gm.getResolution(), gm.getPosition()) — see INTEGRATION.md §C.
+// (gm["distance"].data(), gm.getSize(), gm.getResolution(), gm.getPosition()) — or, second constructor, the OCCUPANCY buffer the reference's callers already
+// compute as `binary` (gm["obstacle"] cast to unsigned char, 0 = occupied): the distance transform then runs on the device — see INTEGRATION.md §C.
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -28,6 +29,14 @@ class Map {
         po_map m{distance_col_major, size_x, size_y, resolution, pos_x, pos_y};
         const int rc = po_set_map(engine_->handle(), &m);
         if (rc != PO_OK) throw std::runtime_error(std::string("po_set_map: ") + po_strerror(rc));
+    }
+    // From the occupancy image (Eigen::Matrix<unsigned char, Dynamic, Dynamic>, column-major like the float layer; 0 = occupied): replaces
+    // cv::distanceTransform(binary, distance, CV_DIST_L2, CV_DIST_MASK_PRECISE) and `distance *= resolution` with po_set_map_occupancy (exact, on the device).
+    Map(const unsigned char *occupancy_col_major, int size_x, int size_y, double resolution, double pos_x, double pos_y, PoEngine *engine = nullptr)
+        : engine_(engine ? engine : &PoEngine::instance()) {
+        po_occupancy o{occupancy_col_major, size_x, size_y, resolution, pos_x, pos_y};
+        const int rc = po_set_map_occupancy(engine_->handle(), &o);
+        if (rc != PO_OK) throw std::runtime_error(std::string("po_set_map_occupancy: ") + po_strerror(rc));
     }
     double getObstacleDistance(double x, double y) const { double d; int in; sample(x, y, &d, &in); return d; }
     bool isInside(double x, double y) const { double d; int in; sample(x, y, &d, &in); return in != 0; }
