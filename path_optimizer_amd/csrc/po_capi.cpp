@@ -18,91 +18,13 @@
 
 #include "../../include/po_hip.h"
 #include "po_device.hpp"
+#include "po_handle.hpp"
+#include "po_launch.hpp"
 #include "po_map.hpp"
 #include "po_smooth.hpp"
 
-extern "C" hipError_t po_launch_solve(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out);
-extern "C" hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_t st);
-extern "C" hipError_t po_launch_mark_unavailable(po_info *info, int B, int refine, int polish, hipStream_t st);
-extern "C" hipError_t po_launch_polish(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
-extern "C" hipError_t po_launch_newton(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
-extern "C" hipError_t po_launch_newton_fallback(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
-extern "C" int po_polish_state_doubles(int form, int N, int C, int keep);
-extern "C" int po_newton_park_doubles(int form, int N, int C, int keep);
-extern "C" int po_shape_threads(int form, int N, int C, int keep);
-extern "C" hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipStream_t st);
-extern "C" int po_has_polish_kernel(int form, int N, int C, int keep);
-extern "C" hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, hipStream_t st);
-extern "C" hipError_t po_launch_assemble(int form, const po::DevBatch *in, const po::DevParams *P, double *l, double *u, double *dyn, hipStream_t st);
-extern "C" size_t po_lds_bytes(int form, int N, int C, int keep);
-extern "C" hipError_t po_launch_postcheck(const po::DevMap *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states,
-                                          const po_info *info, int *n_valid, int *ok, hipStream_t st);
-extern "C" hipError_t po_launch_densify(const po::DevMap *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info,
-                                        double spacing, int M, double *out, int *n_out, int *ok, hipStream_t st);
-extern "C" hipError_t po_launch_bounds(const po::DevMap *m, const po::DevBounds *in, double *bounds, int *n_valid, hipStream_t st);
-extern "C" hipError_t po_launch_smooth(const po::DevSmooth *a, hipStream_t st);
-extern "C" size_t po_smooth_lds_bytes(int kind, int P);
-extern "C" size_t po_smooth_scratch_doubles(int kind, int P);
-extern "C" hipError_t po_launch_resample(const po::DevSpline *in, const po::DevResample *r, hipStream_t st);
-extern "C" hipError_t po_launch_limits(int B, int N, const int *n_points, const double *v, const double *a, double *max_k, double *max_kp, double mu, double rate, hipStream_t st);
-extern "C" hipError_t po_launch_dp_search(const po::DevMap *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st);
-extern "C" size_t po_dp_lds_bytes(int K, int L);
-extern "C" size_t po_spline_lds_bytes(int K);
-extern "C" hipError_t po_launch_edt(const unsigned char *cells, int M, int sx, int sy, float res, void *scratch, float *out, hipStream_t st);
-extern "C" size_t po_edt_scratch_bytes(int M, int sx, int sy);
-extern "C" int po_edt_max_side(void);
-extern "C" int po_edt_max_images(void);
-extern "C" hipError_t po_launch_map_sample(const po::DevMap *m, int n, const double *xy, double *dist, int *inside, hipStream_t st);
-
 namespace {
 thread_local std::string g_hip_err;
-bool hip_ok(hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    g_hip_err = std::string(what) + ": " + hipGetErrorString(e);
-    return false;
-}
-#define HIP_TRY(x)                                   \
-    do {                                             \
-        if (!hip_ok((x), #x)) return PO_ERR_HIP;     \
-    } while (0)
-
-struct DevBuf {  // grow-only device buffer
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return PO_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        if (!hip_ok(hipMalloc(&p, bytes), "hipMalloc")) return PO_ERR_NOMEM;
-        cap = bytes;
-        return PO_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-struct HostBuf {  // grow-only PINNED host buffer (hipHostMalloc): the staging area of the host-pointer entry — DMA engines read / write it directly,
-                  // so the H2D / D2H copies run at PCIe speed and asynchronously (a copy from pageable memory is staged by the runtime, synchronously)
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return PO_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        if (!hip_ok(hipHostMalloc(&p, bytes, hipHostMallocDefault), "hipHostMalloc")) return PO_ERR_NOMEM;
-        cap = bytes;
-        return PO_OK;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 struct CopySeg { char *dst; const char *src; size_t bytes; };
 // memcpy of a list of segments on `nthr` host threads (pieces of <= 2 MB handed out round-robin: every thread streams through every array)
 void parallel_copy(const std::vector<CopySeg> &segs, int nthr) {
@@ -123,39 +45,11 @@ void parallel_copy(const std::vector<CopySeg> &segs, int nthr) {
 }
 }  // namespace
 
-struct po_handle_s {
-    int device = 0;
-    po_params params{};
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t evh[4] = {nullptr, nullptr, nullptr, nullptr};  // host-pointer entry: start, H2D done, (ev0 .. ev1 = the solve), D2H done; evh[3]: solve phase mark (po_last_phase_ms)
-    hipEvent_t evp[2] = {nullptr, nullptr};                    // split scheduling (refine = 2): end of the warm-start launches, end of the Newton launch
-    bool timed = false, timed_host = false, timed_phases = false;
-    double host_pack_ms = 0.0, host_unpack_ms = 0.0;
-    HostBuf pin_in, pin_out;   // pinned staging of the host-pointer entry
-    int host_threads = 0;      // pack / unpack threads (0: min(8, hardware threads); po_debug_set "host_threads")
-    DevBuf pol_buf;  // per-lane ADMM state handed from the solve kernels to newton_kernel / polish_kernel (po_params.refine / polish)
-    DevBuf fb_buf;   // refine = 2: the work list of newton_fallback_kernel
-    DevBuf nw_state_buf, nw_idx_buf;  // sliced Newton launches: the parked paths' blocks; keys [B] + list [B + 1]
-    bool nw_slice_forced = false;
-    int nw_last_B = 0;  // ... and the batch size of the last sliced solve (po_debug_get "newton_parked")
-    int wave_slots = 1024;  // paths the device runs at a time (one wave per SIMD: 4 per CU); batches below two rounds of that are not sliced (no queueing tail to remove)
-    int nw_slice = 8;  // steps of the first of the two Newton launches (po_debug_set "newton_slice"; 0: one launch).  Scheduling only.
-    HostBuf fb_host; // ... and the pinned word its count is read back into (refine_chain = 2)
-    // developer switches (po_debug_set; the library reads no environment variable): identity_order (block i solves path i), debug_cycles (per-phase shader
-    // clocks of path 0 on stderr; synchronises), smoothing / DP-search A/B switches
-    bool env_identity = false, env_cycles = false, env_smooth_seq = false, env_smooth_nopad = false, env_smooth_debug = false, env_dp_one_wave = false;
-    int env_smooth_waves = 0;
-    DevBuf in_buf, out_buf, asm_buf, scale_buf, dbg_buf, map_buf, post_buf, coef_buf, bnd_buf, smooth_buf, smooth_io, plan_coef, plan_io, plan_arena, plan_host;
-    DevBuf edt_buf, edt_io;  // occupancy -> distance transform: the 16-bit intermediate (2 bytes per cell); staging of the host-pointer entries (image + layers)
-    po::DevMap map{};  // obstacle-distance layer (po_set_map); map.d == nullptr until set
-    // Two locks, always taken in the order call_mu -> mu:
-    // mu       guards the handle's fields and grow-only blocks while a device-pointer entry reads them and enqueues its launches;
-    // call_mu  is the CALL lock: every host-pointer entry (and po_plan_batch*, whose stages share the plan arena) holds it from before its first ensure() until its
-    //          last read-back has been synchronised, so staging, launch and read-back of one call are atomic with respect to every other call on the handle.
-    std::mutex mu;
-    std::mutex call_mu;
-};
+bool hip_ok(hipError_t e, const char *what) {
+    if (e == hipSuccess) return true;
+    g_hip_err = std::string(what) + ": " + hipGetErrorString(e);
+    return false;
+}
 
 extern "C" {
 
@@ -259,14 +153,14 @@ int po_create(int device, const po_params *params, po_handle *out) {
     h->device = device;
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->wave_slots = 4 * cus; }
     h->params = *params;
-    if (!hip_ok(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking), "hipStreamCreate") ||
-        !hip_ok(hipEventCreate(&h->ev0), "hipEventCreate") || !hip_ok(hipEventCreate(&h->ev1), "hipEventCreate")) {
-        delete h;
+    if (!hip_ok(hipStreamCreateWithFlags(&h->own_stream.s, hipStreamNonBlocking), "hipStreamCreate") ||
+        !hip_ok(hipEventCreate(&h->ev0.e), "hipEventCreate") || !hip_ok(hipEventCreate(&h->ev1.e), "hipEventCreate")) {
+        delete h;  // (the handle destroys what had been created)
         return PO_ERR_HIP;
     }
-    for (hipEvent_t &e : h->evh) if (!hip_ok(hipEventCreate(&e), "hipEventCreate")) { delete h; return PO_ERR_HIP; }
-    for (hipEvent_t &e : h->evp) if (!hip_ok(hipEventCreate(&e), "hipEventCreate")) { delete h; return PO_ERR_HIP; }
-    h->stream = h->own_stream;
+    for (Event &e : h->evh) if (!hip_ok(hipEventCreate(&e.e), "hipEventCreate")) { delete h; return PO_ERR_HIP; }
+    for (Event &e : h->evp) if (!hip_ok(hipEventCreate(&e.e), "hipEventCreate")) { delete h; return PO_ERR_HIP; }
+    h->stream = h->own_stream.s;
     *out = h;
     return PO_OK;
 }
@@ -275,18 +169,7 @@ int po_destroy(po_handle h) {
     if (!h) return PO_ERR_INVALID;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    h->pol_buf.release();
-    h->fb_buf.release();
-    h->nw_state_buf.release(); h->nw_idx_buf.release();
-    h->in_buf.release(); h->out_buf.release(); h->asm_buf.release(); h->scale_buf.release(); h->dbg_buf.release(); h->map_buf.release(); h->post_buf.release(); h->coef_buf.release(); h->bnd_buf.release(); h->smooth_buf.release(); h->smooth_io.release(); h->plan_coef.release(); h->plan_io.release(); h->plan_arena.release(); h->plan_host.release();
-    h->edt_buf.release(); h->edt_io.release();
-    h->pin_in.release(); h->pin_out.release(); h->fb_host.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    for (hipEvent_t e : h->evh) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->evp) if (e) (void)hipEventDestroy(e);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h;  // buffers, then events, then the stream (po_handle_s, po_handle.hpp)
     return PO_OK;
 }
 
@@ -365,7 +248,7 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
 int po_set_stream(po_handle h, void *hip_stream) {
     if (!h) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
-    h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+    h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream.s;
     return PO_OK;
 }
 
@@ -706,40 +589,27 @@ int po_assemble_batch(po_handle h, const po_batch_in *in, double *l, double *u, 
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = in->B, N = in->N;
     const bool kpc = in->formulation == PO_KPC;
-    const size_t per_pt = 13 + (kpc ? 2 : 0);
-    const size_t in_bytes = sizeof(double) * (B * N * per_pt + B * 4);
-    const size_t a_bytes = sizeof(double) * (2 * B * (size_t)m + B * (N - 1) * 3);
+    Stage I, O;  // the inputs in in_buf, the three outputs in asm_buf
+    const Slot<double> rx = I.in(in->ref_x, B * N), ry = I.in(in->ref_y, B * N), rz = I.in(in->ref_z, B * N), rk = I.in(in->ref_k, B * N), rs = I.in(in->ref_s, B * N);
+    const Slot<double> bd = I.in(in->bounds, B * N * 8), x0 = I.in(in->x0, B * 3), gz = I.in(in->goal_z, B);
+    const Slot<double> mk = I.in(kpc ? in->max_k : nullptr, B * N), mkp = I.in(kpc ? in->max_kp : nullptr, B * N);
+    const Slot<double> dl = O.out(l, B * (size_t)m), du = O.out(u, B * (size_t)m), dd = O.out(dyn, B * (N - 1) * 3);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
-        if ((rc = h->in_buf.ensure(in_bytes)) || (rc = h->asm_buf.ensure(a_bytes))) return rc;
+        if ((rc = I.reserve(h, h->in_buf)) || (rc = O.reserve(h, h->asm_buf))) return rc;
     }
-    double *d = static_cast<double *>(h->in_buf.p);
+    PO_TRY(I.copy_in(h));
     po_batch_in din = *in;
-    size_t o = 0;
-    auto up = [&](const double *src, size_t cnt, const double **dst) -> int {
-        *dst = d + o;
-        if (!hip_ok(hipMemcpyAsync(d + o, src, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream), "H2D")) return PO_ERR_HIP;
-        o += cnt;
-        return PO_OK;
-    };
-    if ((rc = up(in->ref_x, B * N, &din.ref_x)) || (rc = up(in->ref_y, B * N, &din.ref_y)) || (rc = up(in->ref_z, B * N, &din.ref_z)) ||
-        (rc = up(in->ref_k, B * N, &din.ref_k)) || (rc = up(in->ref_s, B * N, &din.ref_s)) || (rc = up(in->bounds, B * N * 8, &din.bounds)) ||
-        (rc = up(in->x0, B * 3, &din.x0)) || (rc = up(in->goal_z, B, &din.goal_z)))
-        return rc;
-    if (kpc && ((rc = up(in->max_k, B * N, &din.max_k)) || (rc = up(in->max_kp, B * N, &din.max_kp)))) return rc;
-    double *dl = static_cast<double *>(h->asm_buf.p), *du = dl + B * (size_t)m, *dd = du + B * (size_t)m;
-    HIP_TRY(hipMemsetAsync(dl, 0, a_bytes, h->stream));
+    din.ref_x = rx; din.ref_y = ry; din.ref_z = rz; din.ref_k = rk; din.ref_s = rs; din.bounds = bd; din.x0 = x0; din.goal_z = gz;
+    if (kpc) { din.max_k = mk; din.max_kp = mkp; }
+    HIP_TRY(hipMemsetAsync(dl, 0, O.bytes(), h->stream));
     po::DevParams P;
     make_dev_params(h, in->formulation, in->keep, &P);
     po::DevBatch D;
     fill_dev_batch(h, &D, &din, nullptr, n, m, C);
     HIP_TRY(po_launch_assemble(in->formulation, &D, &P, dl, du, dd, h->stream));
-    HIP_TRY(hipMemcpyAsync(l, dl, sizeof(double) * B * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(u, du, sizeof(double) * B * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(dyn, dd, sizeof(double) * B * (N - 1) * 3, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return O.copy_out(h);
 }
 
 int po_scaling_batch(po_handle h, const po_batch_in *in, double *out) {
@@ -751,22 +621,22 @@ int po_scaling_batch(po_handle h, const po_batch_in *in, double *out) {
     if (in->B == 0) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = in->B, N = in->N;
+    Stage I, O;  // ref_s in in_buf, the factors in scale_buf
+    const Slot<double> rs = I.in(in->ref_s, B * N), sc = O.out(out, 64 * B);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
-        if ((rc = h->in_buf.ensure(sizeof(double) * B * N)) || (rc = h->scale_buf.ensure(sizeof(double) * 64 * B))) return rc;
+        if ((rc = I.reserve(h, h->in_buf)) || (rc = O.reserve(h, h->scale_buf))) return rc;
     }
+    PO_TRY(I.copy_in(h));
     po_batch_in din = *in;
-    HIP_TRY(hipMemcpyAsync(h->in_buf.p, in->ref_s, sizeof(double) * B * N, hipMemcpyHostToDevice, h->stream));
-    din.ref_s = static_cast<const double *>(h->in_buf.p);
+    din.ref_s = rs;
     po::DevParams P;
     make_dev_params(h, in->formulation, in->keep, &P);
     po::DevBatch D;
     fill_dev_batch(h, &D, &din, nullptr, n, m, C);
-    HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, static_cast<double *>(h->scale_buf.p), h->stream));
-    HIP_TRY(hipMemcpyAsync(out, h->scale_buf.p, sizeof(double) * 64 * B, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, sc, h->stream));
+    return O.copy_out(h);
 }
 
 int po_last_kernel_ms(po_handle h, float *ms) {
@@ -814,12 +684,6 @@ static int check_occupancy(po_handle h, int M, const po_occupancy *occ) {
     if (occ->size_x > po_edt_max_side() || occ->size_y > po_edt_max_side() || M > po_edt_max_images()) return PO_ERR_UNSUPPORTED;
     return PO_OK;
 }
-// A grow-only block that launches already enqueued on the handle's stream may still read: they are finished before the old block is released.  (h->mu held.)
-static int grow_after_sync(po_handle h, DevBuf &buf, size_t bytes) {
-    if (bytes <= buf.cap) return PO_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return buf.ensure(bytes);
-}
 
 int po_distance_map_batch_device(po_handle h, int M, const po_occupancy *occ, float *distance) {
     if (int rc = check_occupancy(h, M, occ)) return rc;
@@ -834,23 +698,21 @@ int po_distance_map_batch_device(po_handle h, int M, const po_occupancy *occ, fl
 int po_distance_map_batch(po_handle h, int M, const po_occupancy *occ, float *distance) {
     if (int rc = check_occupancy(h, M, occ)) return rc;
     if (!distance) return PO_ERR_INVALID;
-    const size_t cells = (size_t)M * (size_t)occ->size_x * (size_t)occ->size_y, bo = sizeof(float) * cells, bc = (cells + 255) & ~(size_t)255;
-    char *base = nullptr;
+    const size_t cells = (size_t)M * (size_t)occ->size_x * (size_t)occ->size_y;
+    Stage S;
+    const Slot<float> d_dist = S.out(distance, cells);
+    const Slot<unsigned char> d_cells = S.in(occ->cells, cells);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = grow_after_sync(h, h->edt_io, bo + bc)) return rc;
-        base = static_cast<char *>(h->edt_io.p);
-        HIP_TRY(hipMemcpyAsync(base + bo, occ->cells, cells, hipMemcpyHostToDevice, h->stream));
+        PO_TRY(S.upload(h, h->edt_io, true));
     }
     po_occupancy dev = *occ;
-    dev.cells = reinterpret_cast<const unsigned char *>(base + bo);
-    if (int rc = po_distance_map_batch_device(h, M, &dev, reinterpret_cast<float *>(base))) return rc;
+    dev.cells = d_cells;
+    PO_TRY(po_distance_map_batch_device(h, M, &dev, d_dist));
     std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipMemcpyAsync(distance, base, bo, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return S.copy_out(h);
 }
 
 int po_set_map_occupancy_device(po_handle h, const po_occupancy *occ) {
@@ -869,20 +731,19 @@ int po_set_map_occupancy_device(po_handle h, const po_occupancy *occ) {
 
 int po_set_map_occupancy(po_handle h, const po_occupancy *occ) {
     if (int rc = check_occupancy(h, 1, occ)) return rc;
-    const size_t cells = (size_t)occ->size_x * (size_t)occ->size_y;
-    po_occupancy dev = *occ;
+    Stage S;
+    const Slot<unsigned char> d_cells = S.in(occ->cells, (size_t)occ->size_x * (size_t)occ->size_y);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and the final synchronisation are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = grow_after_sync(h, h->edt_io, cells)) return rc;
-        HIP_TRY(hipMemcpyAsync(h->edt_io.p, occ->cells, cells, hipMemcpyHostToDevice, h->stream));
-        dev.cells = static_cast<const unsigned char *>(h->edt_io.p);
+        PO_TRY(S.upload(h, h->edt_io, true));
     }
-    if (int rc = po_set_map_occupancy_device(h, &dev)) return rc;
+    po_occupancy dev = *occ;
+    dev.cells = d_cells;
+    PO_TRY(po_set_map_occupancy_device(h, &dev));
     std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipStreamSynchronize(h->stream));  // like po_set_map: the caller's image may be reused, the map is in place
-    return PO_OK;
+    return S.copy_out(h);  // (no output: the synchronise alone) like po_set_map: the caller's image may be reused, the map is in place
 }
 
 int po_get_map(po_handle h, po_map *geometry_out, float *distance_or_null) {
@@ -898,8 +759,16 @@ int po_get_map(po_handle h, po_map *geometry_out, float *distance_or_null) {
     return PO_OK;
 }
 
+// One argument check per stage, shared by its device-pointer entry and its host-pointer twin
+static bool postcheck_args_ok(po_handle h, int B, int N, const double *states, const po_info *info, const int *n_valid, const int *ok) {
+    return h && B >= 0 && N >= 1 && (B == 0 || (states && info && n_valid && ok));
+}
+static bool densify_args_ok(po_handle h, int B, int N, const double *states, const po_info *info, int M, const double *out_states, const int *n_out, const int *ok) {
+    return h && B >= 0 && N >= 3 && M >= 1 && (B == 0 || (states && info && out_states && n_out && ok));
+}
+
 int po_postcheck_batch_device(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid, int *ok) {
-    if (!h || B < 0 || N < 1 || (B > 0 && (!states || !info || !n_valid || !ok))) return PO_ERR_INVALID;
+    if (!postcheck_args_ok(h, B, N, states, info, n_valid, ok)) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
     if (!h->map.d && h->params.enable_collision_check) return PO_ERR_INVALID;  // no map set
     if (B == 0) return PO_OK;
@@ -910,7 +779,7 @@ int po_postcheck_batch_device(po_handle h, int B, int N, const int *n_points, co
 }
 
 int po_densify_batch_device(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int M, double *out_states, int *n_out, int *ok) {
-    if (!h || B < 0 || N < 3 || M < 1 || (B > 0 && (!states || !info || !out_states || !n_out || !ok))) return PO_ERR_INVALID;
+    if (!densify_args_ok(h, B, N, states, info, M, out_states, n_out, ok)) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
     if (!h->map.d && h->params.enable_collision_check) return PO_ERR_INVALID;  // no map set
     if (!(h->params.output_spacing > 0)) return PO_ERR_INVALID;
@@ -923,62 +792,49 @@ int po_densify_batch_device(po_handle h, int B, int N, const int *n_points, cons
 }
 
 int po_densify_batch(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int M, double *out_states, int *n_out, int *ok) {
-    if (!h || B < 0 || N < 3 || M < 1 || (B > 0 && (!states || !info || !out_states || !n_out || !ok))) return PO_ERR_INVALID;
+    if (!densify_args_ok(h, B, N, states, info, M, out_states, n_out, ok)) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
-    const size_t bs = sizeof(double) * 5 * (size_t)B * N, bo = sizeof(double) * 5 * (size_t)B * M, bi = sizeof(po_info) * (size_t)B, bn = sizeof(int) * (size_t)B;
-    char *base = nullptr;
+    Stage S;
+    const Slot<double> d_states = S.in(states, 5 * (size_t)B * N), d_out = S.out(out_states, 5 * (size_t)B * M);
+    const Slot<po_info> d_info = S.in(info, B);
+    const Slot<int> d_np = S.in(n_points, B), d_nout = S.out(n_out, B), d_ok = S.out(ok, B);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = h->post_buf.ensure(bs + bo + bi + 3 * bn + 64)) return rc;
-        base = static_cast<char *>(h->post_buf.p);
-        HIP_TRY(hipMemcpyAsync(base, states, bs, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(base + bs + bo, info, bi, hipMemcpyHostToDevice, h->stream));
-        if (n_points) HIP_TRY(hipMemcpyAsync(base + bs + bo + bi, n_points, bn, hipMemcpyHostToDevice, h->stream));
+        PO_TRY(S.upload(h, h->post_buf));
     }
-    int *dn = reinterpret_cast<int *>(base + bs + bo + bi);
-    const int rc = po_densify_batch_device(h, B, N, n_points ? dn : nullptr, reinterpret_cast<const double *>(base), reinterpret_cast<const po_info *>(base + bs + bo), M,
-                                           reinterpret_cast<double *>(base + bs), dn + B, dn + 2 * B);
-    if (rc) return rc;
+    PO_TRY(po_densify_batch_device(h, B, N, d_np, d_states, d_info, M, d_out, d_nout, d_ok));
     std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipMemcpyAsync(out_states, base + bs, bo, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(n_out, dn + B, bn, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(ok, dn + 2 * B, bn, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return S.copy_out(h);
 }
 
 int po_postcheck_batch(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid, int *ok) {
-    if (!h || B < 0 || N < 1 || (B > 0 && (!states || !info || !n_valid || !ok))) return PO_ERR_INVALID;
+    if (!postcheck_args_ok(h, B, N, states, info, n_valid, ok)) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
-    const size_t bs = sizeof(double) * 5 * (size_t)B * N, bi = sizeof(po_info) * (size_t)B, bn = sizeof(int) * (size_t)B;
-    char *base = nullptr;
+    Stage S;
+    const Slot<double> d_states = S.in(states, 5 * (size_t)B * N);
+    const Slot<po_info> d_info = S.in(info, B);
+    const Slot<int> d_np = S.in(n_points, B), d_nvalid = S.out(n_valid, B), d_ok = S.out(ok, B);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = h->post_buf.ensure(bs + bi + 3 * bn + 64)) return rc;
-        base = static_cast<char *>(h->post_buf.p);
-        HIP_TRY(hipMemcpyAsync(base, states, bs, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(base + bs, info, bi, hipMemcpyHostToDevice, h->stream));
-        if (n_points) HIP_TRY(hipMemcpyAsync(base + bs + bi, n_points, bn, hipMemcpyHostToDevice, h->stream));
+        PO_TRY(S.upload(h, h->post_buf));
     }
-    int *dn = reinterpret_cast<int *>(base + bs + bi);
-    const int rc = po_postcheck_batch_device(h, B, N, n_points ? dn : nullptr, reinterpret_cast<const double *>(base),
-                                             reinterpret_cast<const po_info *>(base + bs), dn + B, dn + 2 * B);
-    if (rc) return rc;
+    PO_TRY(po_postcheck_batch_device(h, B, N, d_np, d_states, d_info, d_nvalid, d_ok));
     std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipMemcpyAsync(n_valid, dn + B, bn, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(ok, dn + 2 * B, bn, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return S.copy_out(h);
 }
 
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------
+static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bounds, const int *n_valid) {
+    if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return false;
+    return in->B == 0 || (in->ref_x && in->ref_y && in->ref_z && in->ref_s && in->knot_s && in->knot_x && in->knot_y && bounds && n_valid);
+}
+
 int po_bounds_batch_device(po_handle h, const po_bounds_in *in, double *bounds, int *n_valid) {
-    if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return PO_ERR_INVALID;
-    if (in->B > 0 && (!in->ref_x || !in->ref_y || !in->ref_z || !in->ref_s || !in->knot_s || !in->knot_x || !in->knot_y || !bounds || !n_valid)) return PO_ERR_INVALID;
+    if (!bounds_args_ok(h, in, bounds, n_valid)) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
     if (!h->map.d) return PO_ERR_INVALID;  // po_set_map first
     if (in->B == 0) return PO_OK;
@@ -997,40 +853,25 @@ int po_bounds_batch_device(po_handle h, const po_bounds_in *in, double *bounds, 
 }
 
 int po_bounds_batch(po_handle h, const po_bounds_in *in, double *bounds, int *n_valid) {
-    if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return PO_ERR_INVALID;
-    if (in->B > 0 && (!in->ref_x || !in->ref_y || !in->ref_z || !in->ref_s || !in->knot_s || !in->knot_x || !in->knot_y || !bounds || !n_valid)) return PO_ERR_INVALID;
+    if (!bounds_args_ok(h, in, bounds, n_valid)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;
-    const size_t bn = sizeof(double) * (size_t)in->B * in->N, bk = sizeof(double) * (size_t)in->B * in->K, bi = sizeof(int) * (size_t)in->B;
-    const size_t bo = sizeof(double) * (size_t)in->B * in->N * 8;
-    char *base = nullptr;
+    const size_t B = in->B, bn = B * in->N, bk = B * in->K;
+    Stage S;
+    const Slot<double> rx = S.in(in->ref_x, bn), ry = S.in(in->ref_y, bn), rz = S.in(in->ref_z, bn), rs = S.in(in->ref_s, bn);
+    const Slot<double> ks = S.in(in->knot_s, bk), kx = S.in(in->knot_x, bk), ky = S.in(in->knot_y, bk);
+    const Slot<int> np = S.in(in->n_points, B), nk = S.in(in->n_knots, B);
+    const Slot<double> d_bounds = S.out(bounds, 8 * bn);
+    const Slot<int> d_nvalid = S.out(n_valid, B);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = h->bnd_buf.ensure(4 * bn + 3 * bk + 3 * bi + bo + 64)) return rc;
-        base = static_cast<char *>(h->bnd_buf.p);
-        const void *src[7] = {in->ref_x, in->ref_y, in->ref_z, in->ref_s, in->knot_s, in->knot_x, in->knot_y};
-        size_t off = 0;
-        for (int i = 0; i < 7; ++i) { const size_t sz = i < 4 ? bn : bk; HIP_TRY(hipMemcpyAsync(base + off, src[i], sz, hipMemcpyHostToDevice, h->stream)); off += sz; }
-        if (in->n_points) HIP_TRY(hipMemcpyAsync(base + off, in->n_points, bi, hipMemcpyHostToDevice, h->stream));
-        if (in->n_knots) HIP_TRY(hipMemcpyAsync(base + off + bi, in->n_knots, bi, hipMemcpyHostToDevice, h->stream));
+        PO_TRY(S.upload(h, h->bnd_buf));
     }
-    po_bounds_in d = *in;
-    const double *pd = reinterpret_cast<const double *>(base);
-    d.ref_x = pd; d.ref_y = pd + (size_t)in->B * in->N; d.ref_z = pd + 2 * (size_t)in->B * in->N; d.ref_s = pd + 3 * (size_t)in->B * in->N;
-    const double *pk = pd + 4 * (size_t)in->B * in->N;
-    d.knot_s = pk; d.knot_x = pk + (size_t)in->B * in->K; d.knot_y = pk + 2 * (size_t)in->B * in->K;
-    int *pi = reinterpret_cast<int *>(base + 4 * bn + 3 * bk);
-    d.n_points = in->n_points ? pi : nullptr;
-    d.n_knots = in->n_knots ? pi + in->B : nullptr;
-    double *dout = reinterpret_cast<double *>(base + 4 * bn + 3 * bk + 3 * bi + (8 - (3 * bi) % 8) % 8);
-    const int rc = po_bounds_batch_device(h, &d, dout, pi + 2 * in->B);
-    if (rc) return rc;
+    const po_bounds_in d{in->B, in->N, in->K, rx, ry, rz, rs, np, ks, kx, ky, nk};
+    PO_TRY(po_bounds_batch_device(h, &d, d_bounds, d_nvalid));
     std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipMemcpyAsync(bounds, dout, bo, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(n_valid, pi + 2 * in->B, bi, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return S.copy_out(h);
 }
 
 // ---- reference-smoothing QPs -----------------------------------------------------------------------
@@ -1107,73 +948,57 @@ int po_smooth_batch(po_handle h, const po_smooth_in *in, const po_smooth_out *ou
     if (in->B == 0) return PO_OK;
     int nmax = 0;
     po_smooth_dims(in->kind, in->P, &nmax, nullptr);
-    const size_t bp = sizeof(double) * (size_t)in->B * in->P, bb = sizeof(double) * (size_t)in->B, bi = sizeof(int) * (size_t)in->B;
-    const size_t binfo = sizeof(po_info) * (size_t)in->B, braw = out->raw ? sizeof(double) * (size_t)in->B * nmax : 0;
-    char *base = nullptr;
-    const void *src[7] = {in->x, in->y, in->angle, in->k, in->s, in->lb, in->ub};
+    const size_t B = in->B, np = B * in->P;
+    Stage S;
+    const Slot<double> x = S.in(in->x, np), y = S.in(in->y, np), angle = S.in(in->angle, np), k = S.in(in->k, np), s = S.in(in->s, np);
+    const Slot<double> lb = S.in(in->lb, np), ub = S.in(in->ub, np), l0 = S.in(in->l0, B);
+    const Slot<int> n_points = S.in(in->n_points, B);
+    // y / s: the device arrays always exist and the kernel writes them (a null host pointer only skips the copy back); raw: not wanted = not declared, the kernel skips it
+    const Slot<double> ox = S.out(out->x, np), oy = S.out(out->y, np), os = S.out(out->s, np);
+    const Slot<po_info> oinfo = S.out(out->info, B);
+    const Slot<double> oraw = out->raw ? S.out(out->raw, B * (size_t)nmax) : Slot<double>{};
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = h->smooth_io.ensure(10 * bp + bb + bi + binfo + braw + 64)) return rc;
-        base = static_cast<char *>(h->smooth_io.p);
-        for (int i = 0; i < 7; ++i)
-            if (src[i]) HIP_TRY(hipMemcpyAsync(base + i * bp, src[i], bp, hipMemcpyHostToDevice, h->stream));
-        if (in->l0) HIP_TRY(hipMemcpyAsync(base + 10 * bp, in->l0, bb, hipMemcpyHostToDevice, h->stream));
-        if (in->n_points) HIP_TRY(hipMemcpyAsync(base + 10 * bp + bb + binfo + braw, in->n_points, bi, hipMemcpyHostToDevice, h->stream));
+        PO_TRY(S.upload(h, h->smooth_io));
     }
-    po_smooth_in d = *in;
-    const double *pd = reinterpret_cast<const double *>(base);
-    const size_t np = (size_t)in->B * in->P;
-    d.x = in->x ? pd : nullptr; d.y = in->y ? pd + np : nullptr; d.angle = in->angle ? pd + 2 * np : nullptr; d.k = in->k ? pd + 3 * np : nullptr;
-    d.s = pd + 4 * np; d.lb = in->lb ? pd + 5 * np : nullptr; d.ub = in->ub ? pd + 6 * np : nullptr;
-    d.l0 = in->l0 ? reinterpret_cast<const double *>(base + 10 * bp) : nullptr;
-    d.n_points = in->n_points ? reinterpret_cast<const int *>(base + 10 * bp + bb + binfo + braw) : nullptr;
-    po_smooth_out dout{};
-    double *po_ = reinterpret_cast<double *>(base + 7 * bp);
-    dout.x = po_; dout.y = po_ + np; dout.s = po_ + 2 * np;
-    dout.info = reinterpret_cast<po_info *>(base + 10 * bp + bb);
-    dout.raw = out->raw ? reinterpret_cast<double *>(base + 10 * bp + bb + binfo) : nullptr;
-    const int rc = po_smooth_batch_device(h, &d, &dout);
-    if (rc) return rc;
+    const po_smooth_in d{in->kind, in->B, in->P, n_points, x, y, angle, k, s, lb, ub, l0};
+    const po_smooth_out dout{ox, oy, os, oinfo, oraw};
+    PO_TRY(po_smooth_batch_device(h, &d, &dout));
     std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipMemcpyAsync(out->x, dout.x, bp, hipMemcpyDeviceToHost, h->stream));
-    if (out->y) HIP_TRY(hipMemcpyAsync(out->y, dout.y, bp, hipMemcpyDeviceToHost, h->stream));
-    if (out->s) HIP_TRY(hipMemcpyAsync(out->s, dout.s, bp, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(out->info, dout.info, binfo, hipMemcpyDeviceToHost, h->stream));
-    if (out->raw) HIP_TRY(hipMemcpyAsync(out->raw, dout.raw, braw, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return S.copy_out(h);
 }
 
 // ---- reference re-sampling, limits, DP lattice search -----------------------------------------------
-static int spline_args_ok(const po_spline_in *in) {
-    return in && in->B >= 0 && in->K >= 3 && (in->B == 0 || (in->knot_s && in->knot_x && in->knot_y && in->length));
+static bool resample_args_ok(po_handle h, const po_spline_in *in, int N, const double *ref_x, const double *ref_y, const double *ref_z, const double *ref_k,
+                             const double *ref_s, const int *n_points) {
+    return h && spline_args_ok(in) && N >= 1 && (in->B == 0 || (ref_x && ref_y && ref_z && ref_k && ref_s && n_points));
 }
-static int make_dev_spline(po_handle h, const po_spline_in *in, po::DevSpline *D) {
-    (void)h;  // the spline coefficients are fitted in LDS by each consumer kernel
-    D->B = in->B; D->K = in->K; D->knot_s = in->knot_s; D->knot_x = in->knot_x; D->knot_y = in->knot_y; D->n_knots = in->n_knots;
-    D->length = in->length; D->coef = nullptr;
-    return PO_OK;
+static bool limits_args_ok(po_handle h, int B, int N, const double *v, const double *a, const double *max_k, const double *max_kp) {
+    return h && B >= 0 && N >= 1 && (B == 0 || (v && a && max_k && max_kp));
+}
+static bool dp_search_args_ok(po_handle h, const po_spline_in *in, const double *start, int L, const double *layer_s, const double *lb, const double *ub,
+                              const double *l0, const int *n_layers) {
+    return h && spline_args_ok(in) && L >= 1 && (in->B == 0 || (start && layer_s && lb && ub && l0 && n_layers));
 }
 
 int po_resample_batch_device(po_handle h, const po_spline_in *in, double ds_smaller, double ds_larger, int N, double *ref_x, double *ref_y,
                              double *ref_z, double *ref_k, double *ref_s, int *n_points) {
-    if (!h || !spline_args_ok(in) || N < 1 || !(ds_smaller <= ds_larger) || !(ds_smaller > 0)) return PO_ERR_INVALID;  // CHECK_LE(delta_s_smaller, delta_s_larger)
-    if (in->B > 0 && (!ref_x || !ref_y || !ref_z || !ref_k || !ref_s || !n_points)) return PO_ERR_INVALID;
+    if (!resample_args_ok(h, in, N, ref_x, ref_y, ref_z, ref_k, ref_s, n_points)) return PO_ERR_INVALID;
+    if (!(ds_smaller <= ds_larger) || !(ds_smaller > 0)) return PO_ERR_INVALID;  // CHECK_LE(delta_s_smaller, delta_s_larger)
     if (in->B == 0) return PO_OK;
     if (po_spline_lds_bytes(in->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
-    po::DevSpline D{};
-    if (int rc = make_dev_spline(h, in, &D)) return rc;
+    const po::DevSpline D = make_dev_spline(in);
     po::DevResample R{ds_smaller, ds_larger, h->params.enable_dynamic_segmentation, N, ref_x, ref_y, ref_z, ref_k, ref_s, n_points};
     HIP_TRY(po_launch_resample(&D, &R, h->stream));
     return PO_OK;
 }
 
 int po_limits_batch_device(po_handle h, int B, int N, const int *n_points, const double *v, const double *a, double *max_k, double *max_kp) {
-    if (!h || B < 0 || N < 1 || (B > 0 && (!v || !a || !max_k || !max_kp))) return PO_ERR_INVALID;
+    if (!limits_args_ok(h, B, N, v, a, max_k, max_kp)) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
     std::lock_guard<std::mutex> g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
@@ -1183,8 +1008,7 @@ int po_limits_batch_device(po_handle h, int B, int N, const int *n_points, const
 
 int po_dp_search_batch_device(po_handle h, const po_spline_in *in, const double *start, int L, double *layer_s, double *lb, double *ub, double *l0,
                               int *n_layers) {
-    if (!h || !spline_args_ok(in) || L < 1) return PO_ERR_INVALID;
-    if (in->B > 0 && (!start || !layer_s || !lb || !ub || !l0 || !n_layers)) return PO_ERR_INVALID;
+    if (!dp_search_args_ok(h, in, start, L, layer_s, lb, ub, l0, n_layers)) return PO_ERR_INVALID;
     const po_params &p = h->params;
     if (!(p.search_lat_spacing > 0) || !(p.search_long_spacing > 0) || !(p.search_lateral_range > 0) ||
         2 * p.search_lateral_range / p.search_lat_spacing + 1 > 64) return PO_ERR_UNSUPPORTED;  // one wave per path: <= 64 lateral samples
@@ -1193,8 +1017,7 @@ int po_dp_search_batch_device(po_handle h, const po_spline_in *in, const double 
     if (in->B == 0) return PO_OK;
     if (po_dp_lds_bytes(in->K, L) > 160 * 1024) return PO_ERR_UNSUPPORTED;
     HIP_TRY(hipSetDevice(h->device));
-    po::DevSpline D{};
-    if (int rc = make_dev_spline(h, in, &D)) return rc;
+    const po::DevSpline D = make_dev_spline(in);
     po::DevSearch Q{p.search_lateral_range, p.search_long_spacing, p.search_lat_spacing, start, L, layer_s, lb, ub, l0, n_layers};
     HIP_TRY(po_launch_dp_search(&h->map, &D, &Q, h->env_dp_one_wave ? 1 : 0, h->stream));
     return PO_OK;
@@ -1202,101 +1025,77 @@ int po_dp_search_batch_device(po_handle h, const po_spline_in *in, const double 
 
 // host-pointer wrappers: stage the spline batch, run the device entry, copy back
 namespace {
-struct StagedSpline { po_spline_in d; char *next; };
-int stage_spline_batch(po_handle h, const po_spline_in *in, size_t extra_bytes, StagedSpline *out) {
-    const size_t bk = sizeof(double) * (size_t)in->B * in->K, bb = sizeof(double) * (size_t)in->B, bi = sizeof(int) * (size_t)in->B;
-    if (int rc = h->plan_io.ensure(3 * bk + bb + bi + 8 + extra_bytes + 64)) return rc;
-    char *base = static_cast<char *>(h->plan_io.p);
-    const void *src[3] = {in->knot_s, in->knot_x, in->knot_y};
-    for (int i = 0; i < 3; ++i) HIP_TRY(hipMemcpyAsync(base + i * bk, src[i], bk, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(base + 3 * bk, in->length, bb, hipMemcpyHostToDevice, h->stream));
-    if (in->n_knots) HIP_TRY(hipMemcpyAsync(base + 3 * bk + bb, in->n_knots, bi, hipMemcpyHostToDevice, h->stream));
-    out->d = *in;
-    out->d.knot_s = reinterpret_cast<const double *>(base); out->d.knot_x = reinterpret_cast<const double *>(base + bk);
-    out->d.knot_y = reinterpret_cast<const double *>(base + 2 * bk); out->d.length = reinterpret_cast<const double *>(base + 3 * bk);
-    out->d.n_knots = in->n_knots ? reinterpret_cast<const int *>(base + 3 * bk + bb) : nullptr;
-    out->next = base + ((3 * bk + bb + bi + 7) & ~(size_t)7);
-    return PO_OK;
+struct StagedSpline {
+    Slot<double> s, x, y, length;
+    Slot<int> n_knots;
+    po_spline_in dev(const po_spline_in *in) const { return po_spline_in{in->B, in->K, s, x, y, n_knots, length}; }  // (once the block is reserved)
+};
+void stage_spline_batch(Stage &S, const po_spline_in *in, StagedSpline *q) {  // declares the arrays of a po_spline_in on S
+    const size_t B = in->B, bk = B * in->K;
+    q->s = S.in(in->knot_s, bk); q->x = S.in(in->knot_x, bk); q->y = S.in(in->knot_y, bk); q->length = S.in(in->length, B); q->n_knots = S.in(in->n_knots, B);
 }
 }  // namespace
 
 int po_resample_batch(po_handle h, const po_spline_in *in, double ds_smaller, double ds_larger, int N, double *ref_x, double *ref_y, double *ref_z,
                       double *ref_k, double *ref_s, int *n_points) {
-    if (!h || !spline_args_ok(in) || N < 1) return PO_ERR_INVALID;
-    if (in->B > 0 && (!ref_x || !ref_y || !ref_z || !ref_k || !ref_s || !n_points)) return PO_ERR_INVALID;
+    if (!resample_args_ok(h, in, N, ref_x, ref_y, ref_z, ref_k, ref_s, n_points)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;
-    const size_t bn = sizeof(double) * (size_t)in->B * N, bi = sizeof(int) * (size_t)in->B;
-    StagedSpline S{};
+    const size_t B = in->B, bn = B * N;
+    Stage S;
+    StagedSpline sp;
+    stage_spline_batch(S, in, &sp);
+    const Slot<double> x = S.out(ref_x, bn), y = S.out(ref_y, bn), z = S.out(ref_z, bn), k = S.out(ref_k, bn), s = S.out(ref_s, bn);
+    const Slot<int> np = S.out(n_points, B);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = stage_spline_batch(h, in, 5 * bn + bi, &S)) return rc;
+        PO_TRY(S.upload(h, h->plan_io));
     }
-    double *o = reinterpret_cast<double *>(S.next);
-    int *on = reinterpret_cast<int *>(S.next + 5 * bn);
-    const size_t n1 = (size_t)in->B * N;
-    if (int rc = po_resample_batch_device(h, &S.d, ds_smaller, ds_larger, N, o, o + n1, o + 2 * n1, o + 3 * n1, o + 4 * n1, on)) return rc;
+    const po_spline_in d = sp.dev(in);
+    PO_TRY(po_resample_batch_device(h, &d, ds_smaller, ds_larger, N, x, y, z, k, s, np));
     std::lock_guard<std::mutex> g(h->mu);
-    double *dst[5] = {ref_x, ref_y, ref_z, ref_k, ref_s};
-    for (int i = 0; i < 5; ++i) HIP_TRY(hipMemcpyAsync(dst[i], o + i * n1, bn, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(n_points, on, bi, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return S.copy_out(h);
 }
 
 int po_limits_batch(po_handle h, int B, int N, const int *n_points, const double *v, const double *a, double *max_k, double *max_kp) {
-    if (!h || B < 0 || N < 1 || (B > 0 && (!v || !a || !max_k || !max_kp))) return PO_ERR_INVALID;
+    if (!limits_args_ok(h, B, N, v, a, max_k, max_kp)) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
-    const size_t bn = sizeof(double) * (size_t)B * N, bi = sizeof(int) * (size_t)B;
-    char *base = nullptr;
+    const size_t bn = (size_t)B * N;
+    Stage S;
+    const Slot<double> d_v = S.in(v, bn), d_a = S.in(a, bn), d_k = S.out(max_k, bn), d_kp = S.out(max_kp, bn);
+    const Slot<int> d_np = S.in(n_points, B);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = h->plan_io.ensure(4 * bn + bi + 64)) return rc;
-        base = static_cast<char *>(h->plan_io.p);
-        HIP_TRY(hipMemcpyAsync(base, v, bn, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(base + bn, a, bn, hipMemcpyHostToDevice, h->stream));
-        if (n_points) HIP_TRY(hipMemcpyAsync(base + 4 * bn, n_points, bi, hipMemcpyHostToDevice, h->stream));
+        PO_TRY(S.upload(h, h->plan_io));
     }
-    double *d = reinterpret_cast<double *>(base);
-    const size_t n1 = (size_t)B * N;
-    if (int rc = po_limits_batch_device(h, B, N, n_points ? reinterpret_cast<const int *>(base + 4 * bn) : nullptr, d, d + n1, d + 2 * n1, d + 3 * n1)) return rc;
+    PO_TRY(po_limits_batch_device(h, B, N, d_np, d_v, d_a, d_k, d_kp));
     std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipMemcpyAsync(max_k, d + 2 * n1, bn, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(max_kp, d + 3 * n1, bn, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return S.copy_out(h);
 }
 
 int po_dp_search_batch(po_handle h, const po_spline_in *in, const double *start, int L, double *layer_s, double *lb, double *ub, double *l0, int *n_layers) {
-    if (!h || !spline_args_ok(in) || L < 1) return PO_ERR_INVALID;
-    if (in->B > 0 && (!start || !layer_s || !lb || !ub || !l0 || !n_layers)) return PO_ERR_INVALID;
+    if (!dp_search_args_ok(h, in, start, L, layer_s, lb, ub, l0, n_layers)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;
-    const size_t bl = sizeof(double) * (size_t)in->B * L, bs = sizeof(double) * 3 * (size_t)in->B, bb = sizeof(double) * (size_t)in->B, bi = sizeof(int) * (size_t)in->B;
-    StagedSpline S{};
+    const size_t B = in->B, bl = B * L;
+    Stage S;
+    StagedSpline sp;
+    stage_spline_batch(S, in, &sp);
+    const Slot<double> d_start = S.in(start, 3 * B);
+    const Slot<double> d_s = S.out(layer_s, bl), d_lb = S.out(lb, bl), d_ub = S.out(ub, bl), d_l0 = S.out(l0, B);
+    const Slot<int> d_n = S.out(n_layers, B);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = stage_spline_batch(h, in, 3 * bl + bs + bb + bi, &S)) return rc;
-        HIP_TRY(hipMemcpyAsync(S.next, start, bs, hipMemcpyHostToDevice, h->stream));
+        PO_TRY(S.upload(h, h->plan_io));
     }
-    double *dstart = reinterpret_cast<double *>(S.next);
-    double *o = dstart + 3 * (size_t)in->B;
-    const size_t n1 = (size_t)in->B * L;
-    double *dl0 = o + 3 * n1;
-    int *dn = reinterpret_cast<int *>(dl0 + in->B);
-    if (int rc = po_dp_search_batch_device(h, &S.d, dstart, L, o, o + n1, o + 2 * n1, dl0, dn)) return rc;
+    const po_spline_in d = sp.dev(in);
+    PO_TRY(po_dp_search_batch_device(h, &d, d_start, L, d_s, d_lb, d_ub, d_l0, d_n));
     std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipMemcpyAsync(layer_s, o, bl, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(lb, o + n1, bl, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(ub, o + 2 * n1, bl, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(l0, dl0, bb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(n_layers, dn, bi, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    return S.copy_out(h);
 }
 
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside) {
@@ -1306,28 +1105,13 @@ int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *insid
     if (!h->map.d) return PO_ERR_INVALID;
     if (n == 0) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t bx = sizeof(double) * 2 * (size_t)n, bd = sizeof(double) * (size_t)n, bi = sizeof(int) * (size_t)n;
-    if (int rc = h->post_buf.ensure(bx + bd + bi)) return rc;
-    char *base = static_cast<char *>(h->post_buf.p);
-    HIP_TRY(hipMemcpyAsync(base, xy, bx, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(po_launch_map_sample(&h->map, n, reinterpret_cast<const double *>(base), reinterpret_cast<double *>(base + bx),
-                                 reinterpret_cast<int *>(base + bx + bd), h->stream));
-    HIP_TRY(hipMemcpyAsync(dist, base + bx, bd, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(inside, base + bx + bd, bi, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PO_OK;
+    Stage S;
+    const Slot<double> d_xy = S.in(xy, 2 * (size_t)n), d_dist = S.out(dist, n);
+    const Slot<int> d_inside = S.out(inside, n);
+    PO_TRY(S.upload(h, h->post_buf));
+    HIP_TRY(po_launch_map_sample(&h->map, n, d_xy, d_dist, d_inside, h->stream));
+    return S.copy_out(h);
 }
-
-// internal accessors for po_plan.cpp (not part of include/po_hip.h)
-void *po_internal_arena(po_handle h, size_t bytes) { return h->plan_arena.ensure(bytes) == PO_OK ? h->plan_arena.p : nullptr; }
-void *po_internal_plan_coef(po_handle h, size_t bytes) { return h->plan_coef.ensure(bytes) == PO_OK ? h->plan_coef.p : nullptr; }
-hipStream_t po_internal_stream(po_handle h) { return h->stream; }
-int po_internal_device(po_handle h) { return h->device; }
-const po_params *po_internal_params(po_handle h) { return &h->params; }
-int po_internal_has_map(po_handle h) { return h->map.d != nullptr; }
-int po_internal_hip_fail(hipError_t e, const char *what) { return hip_ok(e, what) ? 0 : 1; }
-void *po_internal_plan_host(po_handle h, size_t bytes) { return h->plan_host.ensure(bytes) == PO_OK ? h->plan_host.p : nullptr; }
-std::mutex *po_internal_plan_mutex(po_handle h) { return &h->call_mu; }
 
 const char *po_strerror(int code) {
     switch (code) {

@@ -23,6 +23,7 @@ constexpr int kStatusDeferred = -100;  // po_info.status while a solve is in fli
 constexpr double kRhoMin = 1e-6, kRhoMax = 1e6, kRhoEqOverIneq = 1e3, kRhoTol = 1e-4;
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kPi2 = 1.57079632679489661923;
+constexpr int kNwKeys = 32;  // sliced Newton launches: buckets of the park key (written by the refinement in po_fast.inc, counted by nw_sort_kernel in po_kernels.hip)
 
 enum { F_KP = 0, F_KPC = 1, F_K = 2 };
 enum { M_EY = 1, M_EPHI = 2, M_C = 4, M_S1 = 8, M_S2 = 16 };

@@ -26,6 +26,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "po_launch.hpp"
+
 namespace {
 
 constexpr int kMaxSide = 4096;      // LDS row of edt_rows_kernel, range of the 16-bit intermediate and of the int32 sentinel arithmetic

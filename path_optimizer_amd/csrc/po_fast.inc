@@ -4332,7 +4332,7 @@ __device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, 
             // round 5's 4-bit key: first-inner flag + short steps, else 7 - updates).  kNwKeys = 32 buckets.
             const float kf = (nouter == 0 ? (float)nsmall : 0.0f) + 2.0f * __log10f((float)fmax(R.rp, 1e-30)) + 14.0f;
             const int ki = (int)floorf(1.5f * kf);
-            *park_key = ki < 0 ? 0 : (ki > 31 ? 31 : ki);
+            *park_key = ki < 0 ? 0 : (ki > kNwKeys - 1 ? kNwKeys - 1 : ki);
         }
 #pragma unroll
         for (int q = 0; q < SPL; ++q) st.pc[q] = clsf[q];

@@ -1,0 +1,186 @@
+// po_handle.hpp — what the two host files of libpo_hip.so (po_capi.cpp, po_plan.cpp) share: error plumbing, the owning buffers, the handle, the staging helper of
+// the host-pointer entries (Stage) and the spline argument check.  Private: not part of include/po_hip.h, and nothing here is exported (hidden visibility).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <vector>
+
+#include "../../include/po_hip.h"
+#include "po_launch.hpp"
+#include "po_map.hpp"
+
+#pragma GCC visibility push(hidden)
+
+bool hip_ok(hipError_t e, const char *what);  // po_capi.cpp: false + the text po_last_hip_error() returns
+#define HIP_TRY(x)                                   \
+    do {                                             \
+        if (!hip_ok((x), #x)) return PO_ERR_HIP;     \
+    } while (0)
+#define PO_TRY(x)                     \
+    do {                              \
+        const int rc_ = (x);          \
+        if (rc_ != PO_OK) return rc_; \
+    } while (0)
+
+// The handle's resources own what they hold and are not copyable: po_handle_s releases them member by member, in reverse order of declaration.
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+struct Stream : NoCopy {
+    hipStream_t s = nullptr;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+};
+struct Event : NoCopy {
+    hipEvent_t e = nullptr;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+struct DevBuf : NoCopy {  // grow-only device buffer
+    void *p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return PO_OK;
+        release();
+        if (!hip_ok(hipMalloc(&p, bytes), "hipMalloc")) return PO_ERR_NOMEM;
+        cap = bytes;
+        return PO_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    ~DevBuf() { release(); }
+};
+struct HostBuf : NoCopy {  // grow-only PINNED host buffer (hipHostMalloc): the staging area of the host-pointer entry — DMA engines read / write it directly,
+                           // so the H2D / D2H copies run at PCIe speed and asynchronously (a copy from pageable memory is staged by the runtime, synchronously)
+    void *p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return PO_OK;
+        release();
+        if (!hip_ok(hipHostMalloc(&p, bytes, hipHostMallocDefault), "hipHostMalloc")) return PO_ERR_NOMEM;
+        cap = bytes;
+        return PO_OK;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    ~HostBuf() { release(); }
+};
+
+struct po_handle_s {
+    int device = 0;
+    po_params params{};
+    // Declared AHEAD of every buffer: members are destroyed in reverse order, so the buffers are freed first, then the events, the stream last
+    // (po_destroy has set the device and synchronised the stream before).
+    Stream own_stream;
+    hipStream_t stream = nullptr;
+    Event ev0, ev1;
+    Event evh[4];  // host-pointer entry: start, H2D done, (ev0 .. ev1 = the solve), D2H done; evh[3]: solve phase mark (po_last_phase_ms)
+    Event evp[2];  // split scheduling (refine = 2): end of the warm-start launches, end of the Newton launch
+    bool timed = false, timed_host = false, timed_phases = false;
+    double host_pack_ms = 0.0, host_unpack_ms = 0.0;
+    HostBuf pin_in, pin_out;   // pinned staging of the host-pointer entry
+    int host_threads = 0;      // pack / unpack threads (0: min(8, hardware threads); po_debug_set "host_threads")
+    DevBuf pol_buf;  // per-lane ADMM state handed from the solve kernels to newton_kernel / polish_kernel (po_params.refine / polish)
+    DevBuf fb_buf;   // refine = 2: the work list of newton_fallback_kernel
+    DevBuf nw_state_buf, nw_idx_buf;  // sliced Newton launches: the parked paths' blocks; keys [B] + list [B + 1]
+    bool nw_slice_forced = false;
+    int nw_last_B = 0;  // ... and the batch size of the last sliced solve (po_debug_get "newton_parked")
+    int wave_slots = 1024;  // paths the device runs at a time (one wave per SIMD: 4 per CU); batches below two rounds of that are not sliced (no queueing tail to remove)
+    int nw_slice = 8;  // steps of the first of the two Newton launches (po_debug_set "newton_slice"; 0: one launch).  Scheduling only.
+    HostBuf fb_host; // ... and the pinned word its count is read back into (refine_chain = 2)
+    // developer switches (po_debug_set; the library reads no environment variable): identity_order (block i solves path i), debug_cycles (per-phase shader
+    // clocks of path 0 on stderr; synchronises), smoothing / DP-search A/B switches
+    bool env_identity = false, env_cycles = false, env_smooth_seq = false, env_smooth_nopad = false, env_smooth_debug = false, env_dp_one_wave = false;
+    int env_smooth_waves = 0;
+    DevBuf in_buf, out_buf, asm_buf, scale_buf, dbg_buf, map_buf, post_buf, coef_buf, bnd_buf, smooth_buf, smooth_io, plan_io, plan_arena, plan_host;
+    DevBuf edt_buf, edt_io;  // occupancy -> distance transform: the 16-bit intermediate (2 bytes per cell); staging of the host-pointer entries (image + layers)
+    po::DevMap map{};  // obstacle-distance layer (po_set_map); map.d == nullptr until set
+    // Two locks, always taken in the order call_mu -> mu:
+    // mu       guards the handle's fields and grow-only blocks while a device-pointer entry reads them and enqueues its launches;
+    // call_mu  is the CALL lock: every host-pointer entry (and po_plan_batch*, whose stages share the plan arena) holds it from before its first ensure() until its
+    //          last read-back has been synchronised, so staging, launch and read-back of one call are atomic with respect to every other call on the handle.
+    std::mutex mu;
+    std::mutex call_mu;
+};
+
+// A grow-only block that launches already enqueued on the handle's stream may still read: they are finished before the old block is released.  (h->mu held.)
+inline int grow_after_sync(po_handle h, DevBuf &buf, size_t bytes) {
+    if (bytes <= buf.cap) return PO_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return buf.ensure(bytes);
+}
+
+// ---- Stage: the format of one staging block of a host-pointer entry.  The entry DECLARES its arrays, in any order, and gets a slot for each; reserve() sizes the
+// block from those declarations and grows the DevBuf it lives in, copy_in() enqueues one H2D copy per declared input, copy_out() one D2H copy per wanted output and
+// synchronises.  A slot converts to its device pointer once the block is reserved, so no entry computes an offset.  Every slot is aligned to 16 bytes.
+//   in(host, n)      n elements copied from host; host == nullptr: the array is absent, takes no room, and the slot is a null pointer
+//   out(host, n)     n elements the kernel writes, copied to host by copy_out(); host == nullptr: the device array exists all the same, only the copy is skipped
+//                    (an output the kernel must not write at all is simply not declared: a default-constructed Slot is a null pointer)
+//   scratch(n)       n elements that travel in neither direction
+// Copies go from / to the caller's own memory on the handle's stream.  The caller holds the locks the entry's contract asks for.
+class Stage;
+template <typename T> struct Slot {
+    const Stage *stage = nullptr;
+    size_t item = 0;
+    T *ptr() const;
+    operator T *() const { return ptr(); }
+};
+class Stage : NoCopy {
+    struct Item { size_t off, bytes; const void *src; void *dst; };
+    std::vector<Item> items_;
+    size_t bytes_ = 0;
+    char *base_ = nullptr;
+    template <typename T> friend struct Slot;
+    template <typename T> Slot<T> add(size_t n, const void *src, void *dst) {
+        bytes_ = (bytes_ + 15) & ~(size_t)15;
+        items_.push_back({bytes_, sizeof(T) * n, src, dst});
+        bytes_ += sizeof(T) * n;
+        return {this, items_.size() - 1};
+    }
+
+public:
+    template <typename T> Slot<T> in(const T *host, size_t n) { return host ? add<T>(n, host, nullptr) : Slot<T>{}; }
+    template <typename T> Slot<T> out(T *host, size_t n) { return add<T>(n, nullptr, host); }
+    template <typename T> Slot<T> scratch(size_t n) { return add<T>(n, nullptr, nullptr); }
+    size_t bytes() const { return bytes_; }
+    int reserve(po_handle h, DevBuf &buf, bool after_sync = false) {
+        PO_TRY(after_sync ? grow_after_sync(h, buf, bytes_) : buf.ensure(bytes_));
+        base_ = static_cast<char *>(buf.p);
+        return PO_OK;
+    }
+    int copy_in(po_handle h) const {
+        for (const Item &it : items_)
+            if (it.src) HIP_TRY(hipMemcpyAsync(base_ + it.off, it.src, it.bytes, hipMemcpyHostToDevice, h->stream));
+        return PO_OK;
+    }
+    int upload(po_handle h, DevBuf &buf, bool after_sync = false) {  // reserve + copy_in: what an entry does under h->mu before it calls its device twin
+        PO_TRY(reserve(h, buf, after_sync));
+        return copy_in(h);
+    }
+    int copy_out(po_handle h) const {
+        for (const Item &it : items_)
+            if (it.dst) HIP_TRY(hipMemcpyAsync(it.dst, base_ + it.off, it.bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return PO_OK;
+    }
+};
+template <typename T> T *Slot<T>::ptr() const { return stage ? reinterpret_cast<T *>(stage->base_ + stage->items_[item].off) : nullptr; }
+
+// ---- a batch of splines (po_spline_in): one argument check, one DevSpline.  `length` is what ReferencePath attaches to the spline; segmentRawReference and the
+// post-smoothing projection do not read it (need_length = false).
+inline bool spline_args_ok(const po_spline_in *in, bool need_length = true) {
+    return in && in->B >= 0 && in->K >= 3 && (in->B == 0 || (in->knot_s && in->knot_x && in->knot_y && (in->length || !need_length)));
+}
+inline po::DevSpline make_dev_spline(const po_spline_in *in) {  // (coef = nullptr: the spline coefficients are fitted in LDS by each consumer kernel)
+    return po::DevSpline{in->B, in->K, in->knot_s, in->knot_x, in->knot_y, in->n_knots, in->length, nullptr};
+}
+
+#pragma GCC visibility pop

@@ -9,6 +9,7 @@
 // Replaces, per path, the work behind /root/reference/src/solver/solver.cpp:46-77 (setHessianMatrix,
 // setConstraintMatrix, osqp_setup, osqp_solve, getOptimizedPath).
 #include "po_solve_common.hpp"
+#include "po_launch.hpp"
 
 namespace po {
 
@@ -51,13 +52,7 @@ template <int F> __global__ __launch_bounds__(64) void assemble_kernel(DevBatch 
 
 }  // namespace po
 
-// the solve kernels of one formulation and one loop variant live in their own object (po_solve_form.hip)
-#define PO_DECL(name) extern "C" hipError_t name(const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out)
-PO_DECL(po_launch_solve_kp); PO_DECL(po_launch_solve_kp_uni);
-PO_DECL(po_launch_solve_kp_w); PO_DECL(po_launch_solve_kp_w_uni);  // the wide role-split shapes of keep 9 .. 16 (objects of their own)
-PO_DECL(po_launch_solve_kpc); PO_DECL(po_launch_solve_kpc_uni);
-PO_DECL(po_launch_solve_k); PO_DECL(po_launch_solve_k_uni);
-#undef PO_DECL
+// the solve kernels of one formulation and one loop variant live in their own object (po_solve_form.hip; its entries are declared in po_launch.hpp)
 
 namespace po {
 // After the launches of a solve that hands paths from launch to launch (the Newton refinement's rounds): no internal "in flight" status may reach the caller
@@ -103,16 +98,6 @@ extern "C" hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_
     return hipGetLastError();
 }
 
-#define PO_DECLP(name) extern "C" hipError_t name(const po::DevBatch *in, const po::DevParams *P, hipStream_t st)
-PO_DECLP(po_launch_polish_kp); PO_DECLP(po_launch_polish_kpc); PO_DECLP(po_launch_polish_k);
-#undef PO_DECLP
-#define PO_DECLP(name) extern "C" hipError_t name(const po::DevBatch *in, const po::DevParams *P, hipStream_t st)
-PO_DECLP(po_launch_newton_kp); PO_DECLP(po_launch_newton_kpc); PO_DECLP(po_launch_newton_k);
-PO_DECLP(po_launch_newton_kp_fb); PO_DECLP(po_launch_newton_kpc_fb); PO_DECLP(po_launch_newton_k_fb);
-PO_DECLP(po_launch_newton_kp_b); PO_DECLP(po_launch_newton_kp_b_fb);  // KP's role-split shapes (second Newton object)
-PO_DECLP(po_launch_newton_kp_c); PO_DECLP(po_launch_newton_kp_c_fb);  // KP's multi-group shapes (third)
-PO_DECLP(po_launch_newton_kp_w1); PO_DECLP(po_launch_newton_kp_w1_fb); PO_DECLP(po_launch_newton_kp_w2); PO_DECLP(po_launch_newton_kp_w2_fb); PO_DECLP(po_launch_newton_kp_w3); PO_DECLP(po_launch_newton_kp_w3_fb);  // keep 9 .. 16
-#undef PO_DECLP
 // the Newton refinement of round 0 as its own launch (po_params.refine = 2), and the fallback launch for what it hands back
 extern "C" hipError_t po_launch_newton(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
     using namespace po;
@@ -138,19 +123,11 @@ extern "C" hipError_t po_launch_newton_fallback(int form, const po::DevBatch *in
     }
     return form == F_KPC ? po_launch_newton_kpc_fb(in, P, st) : po_launch_newton_k_fb(in, P, st);
 }
-extern "C" int po_polish_state_doubles_kp(int N, int C, int keep);
-extern "C" int po_polish_state_doubles_kpc(int N, int C, int keep);
-extern "C" int po_polish_state_doubles_k(int N, int C, int keep);
 // OSQP's polish (po_params.polish) on the paths the two solve launches reported solved; same stream, after them
 extern "C" hipError_t po_launch_polish(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
     using namespace po;
     return form == F_KP ? po_launch_polish_kp(in, P, st) : (form == F_KPC ? po_launch_polish_kpc(in, P, st) : po_launch_polish_k(in, P, st));
 }
-extern "C" int po_polish_state_doubles_kp_park(int N, int C, int keep);
-extern "C" int po_polish_state_doubles_kp_w(int N, int C, int keep);
-extern "C" int po_polish_state_doubles_kp_w_park(int N, int C, int keep);
-extern "C" int po_polish_state_doubles_kpc_park(int N, int C, int keep);
-extern "C" int po_polish_state_doubles_k_park(int N, int C, int keep);
 extern "C" int po_newton_park_doubles(int form, int N, int C, int keep) {
     using namespace po;
     if (form == F_KP) { const int d = po_polish_state_doubles_kp_park(N, C, keep); return d ? d : po_polish_state_doubles_kp_w_park(N, C, keep); }
@@ -159,7 +136,7 @@ extern "C" int po_newton_park_doubles(int form, int N, int C, int keep) {
 namespace po {
 // the parked paths (keys[b] >= 0) in descending key order, ties in path order (a stable counting sort: deterministic): list[0] = count, list[1 ..] = path ids.
 // One workgroup of kNwSortThreads threads, thread t owns the contiguous range of paths [t * per, (t + 1) * per).
-constexpr int kNwKeys = 32, kNwSortThreads = 256;  // (32 keys x 257 counters = 33 KB of LDS)
+constexpr int kNwSortThreads = 256;  // (kNwKeys = 32 keys x 257 counters = 33 KB of LDS)
 __global__ __launch_bounds__(kNwSortThreads) void nw_sort_kernel(const int *keys, int B, int *list) {
     // (round 6) a thread's counters live in its own COLUMN of the LDS table (no conflicts, one read-modify-write per path instead of a 32-way compare over registers), its
     // first 16 keys are loaded at once and kept for the scatter pass, and the rows are scanned by whole waves: 22 -> ~10 us for 4 096 paths
@@ -237,9 +214,6 @@ extern "C" int po_shape_threads(int form, int N, int C, int keep) {
     po::Shape s;
     return po::resolve_shape(form, N, form == po::F_K ? 0 : C, keep, &s) ? s.nt : 0;
 }
-extern "C" int po_has_polish_kernel_kp(int N, int C, int keep);
-extern "C" int po_has_polish_kernel_kpc(int N, int C, int keep);
-extern "C" int po_has_polish_kernel_k(int N, int C, int keep);
 // does the shape of this batch have a polish kernel?  (the role-split shapes of keep 6 .. 16 and the single-level mapping do not)
 extern "C" int po_has_polish_kernel(int form, int N, int C, int keep) {
     using namespace po;

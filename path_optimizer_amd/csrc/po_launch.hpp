@@ -1,0 +1,92 @@
+// po_launch.hpp — every internal entry of libpo_hip.so that one translation unit defines and another calls, declared ONCE.  These functions have C linkage: no
+// name mangling, so a prototype that drifts from its definition would link and pass garbage.  Both sides include this header — the file that defines an entry and
+// every file that calls it — which turns such a drift into a compile error (conflicting declaration).  A new entry gets its prototype here and nowhere else.
+// Declarations only (forward-declared structs): po_edt.hip, which shares no header with the solve kernels, includes it too.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/po_hip.h"
+
+namespace po {
+struct DevBatch; struct DevParams;                                                   // po_device.hpp
+struct DevMap; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
+struct DevResample; struct PlanGate; struct PlanRows;
+struct DevSmooth;                                                                    // po_smooth.hpp
+}  // namespace po
+
+extern "C" {
+// ---- po_kernels.hip: the solve, by formulation ----
+hipError_t po_launch_solve(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out);
+hipError_t po_launch_newton(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+hipError_t po_launch_newton_fallback(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+hipError_t po_launch_polish(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_t st);
+hipError_t po_launch_mark_unavailable(po_info *info, int B, int refine, int polish, hipStream_t st);
+hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipStream_t st);
+hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, hipStream_t st);
+hipError_t po_launch_assemble(int form, const po::DevBatch *in, const po::DevParams *P, double *l, double *u, double *dyn, hipStream_t st);
+size_t po_lds_bytes(int form, int N, int C, int keep);
+int po_shape_threads(int form, int N, int C, int keep);
+int po_polish_state_doubles(int form, int N, int C, int keep);
+int po_newton_park_doubles(int form, int N, int C, int keep);
+int po_has_polish_kernel(int form, int N, int C, int keep);
+
+// ---- po_solve_form.hip: one object per formulation, loop variant and shape group; the names are pasted together there (PO_G / PO_CAT) ----
+#define PO_DECL_SOLVE(name) hipError_t name(const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out)
+#define PO_DECL_LAUNCH(name) hipError_t name(const po::DevBatch *in, const po::DevParams *P, hipStream_t st)
+#define PO_DECL_NEWTON(name) PO_DECL_LAUNCH(name); PO_DECL_LAUNCH(name##_fb)
+#define PO_DECL_SIZES(name) int name(int N, int C, int keep); int name##_park(int N, int C, int keep)
+PO_DECL_SOLVE(po_launch_solve_kp); PO_DECL_SOLVE(po_launch_solve_kp_uni);
+PO_DECL_SOLVE(po_launch_solve_kp_w); PO_DECL_SOLVE(po_launch_solve_kp_w_uni);  // the wide role-split shapes of keep 9 .. 16
+PO_DECL_SOLVE(po_launch_solve_kpc); PO_DECL_SOLVE(po_launch_solve_kpc_uni);
+PO_DECL_SOLVE(po_launch_solve_k); PO_DECL_SOLVE(po_launch_solve_k_uni);
+PO_DECL_NEWTON(po_launch_newton_kp); PO_DECL_NEWTON(po_launch_newton_kpc); PO_DECL_NEWTON(po_launch_newton_k);
+PO_DECL_NEWTON(po_launch_newton_kp_b);  // KP's role-split shapes (second Newton object)
+PO_DECL_NEWTON(po_launch_newton_kp_c);  // KP's multi-group shapes (third)
+PO_DECL_NEWTON(po_launch_newton_kp_w1); PO_DECL_NEWTON(po_launch_newton_kp_w2); PO_DECL_NEWTON(po_launch_newton_kp_w3);  // keep 9 .. 16
+PO_DECL_LAUNCH(po_launch_polish_kp); PO_DECL_LAUNCH(po_launch_polish_kpc); PO_DECL_LAUNCH(po_launch_polish_k);
+PO_DECL_SIZES(po_polish_state_doubles_kp); PO_DECL_SIZES(po_polish_state_doubles_kp_w);
+PO_DECL_SIZES(po_polish_state_doubles_kpc); PO_DECL_SIZES(po_polish_state_doubles_k);
+int po_has_polish_kernel_kp(int N, int C, int keep);
+int po_has_polish_kernel_kpc(int N, int C, int keep);
+int po_has_polish_kernel_k(int N, int C, int keep);
+#undef PO_DECL_SOLVE
+#undef PO_DECL_LAUNCH
+#undef PO_DECL_NEWTON
+#undef PO_DECL_SIZES
+
+// ---- po_post.hip: map stages, spline stages, the glue of po_plan ----
+hipError_t po_launch_postcheck(const po::DevMap *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid,
+                               int *ok, hipStream_t st);
+hipError_t po_launch_densify(const po::DevMap *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info, double spacing,
+                             int M, double *out, int *n_out, int *ok, hipStream_t st);
+hipError_t po_launch_map_sample(const po::DevMap *m, int n, const double *xy, double *dist, int *inside, hipStream_t st);
+hipError_t po_launch_bounds(const po::DevMap *m, const po::DevBounds *in, double *bounds, int *n_valid, hipStream_t st);
+hipError_t po_launch_resample(const po::DevSpline *in, const po::DevResample *r, hipStream_t st);
+hipError_t po_launch_limits(int B, int N, const int *n_points, const double *v, const double *a, double *max_k, double *max_kp, double mu, double rate, hipStream_t st);
+hipError_t po_launch_dp_search(const po::DevMap *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st);
+size_t po_dp_lds_bytes(int K, int L);
+size_t po_spline_lds_bytes(int K);
+hipError_t po_launch_bspline(int B, int W, const int *n_way, const double *wx, const double *wy, int M, double *x, double *y, double *s, int *n_samples, hipStream_t st);
+hipError_t po_launch_segment_raw(const po::DevSpline *in, int P, double *x, double *y, double *s, double *angle, double *k, int *n_points, hipStream_t st);
+hipError_t po_launch_post_project(const po::DevSpline *in, int L, const int *n_layers, const double *layer_s, const double *off, double *x, double *y, double *s,
+                                  double *length_out, hipStream_t st);
+hipError_t po_launch_segment_init(const po::DevSpline *in, const double *start, int start_stride, const double *goal, int goal_stride, int exact, double *init, int *ok,
+                                  hipStream_t st);
+hipError_t po_launch_plan_gate(const po::PlanGate *g, hipStream_t st);
+hipError_t po_launch_plan_gather(const po::PlanRows *r, hipStream_t st);
+hipError_t po_launch_plan_scatter(const po::PlanRows *r, hipStream_t st);
+hipError_t po_launch_plan_clear(int B, int N, const int *stage, double *states, po_info *info, hipStream_t st);
+
+// ---- po_smooth.hip: the reference-smoothing QPs ----
+hipError_t po_launch_smooth(const po::DevSmooth *a, hipStream_t st);
+size_t po_smooth_lds_bytes(int kind, int P);
+size_t po_smooth_scratch_doubles(int kind, int P);
+int po_smooth_blocked(int kind, int P);
+
+// ---- po_edt.hip: occupancy image -> distance layer ----
+hipError_t po_launch_edt(const unsigned char *cells, int M, int sx, int sy, float res, void *scratch, float *out, hipStream_t st);
+size_t po_edt_scratch_bytes(int M, int sx, int sy);
+int po_edt_max_side(void);
+int po_edt_max_images(void);
+}  // extern "C"

@@ -11,62 +11,9 @@
 #include <vector>
 
 #include "../../include/po_hip.h"
+#include "po_handle.hpp"
+#include "po_launch.hpp"
 #include "po_map.hpp"
-
-// po_capi.cpp
-extern "C" void *po_internal_arena(po_handle h, size_t bytes);
-extern "C" void *po_internal_plan_coef(po_handle h, size_t bytes);
-extern "C" hipStream_t po_internal_stream(po_handle h);
-extern "C" int po_internal_device(po_handle h);
-extern "C" const po_params *po_internal_params(po_handle h);
-extern "C" int po_internal_has_map(po_handle h);
-extern "C" int po_internal_hip_fail(hipError_t e, const char *what);
-extern "C" void *po_internal_plan_host(po_handle h, size_t bytes);
-#include <mutex>
-extern "C" std::mutex *po_internal_plan_mutex(po_handle h);
-// po_post.hip
-extern "C" size_t po_spline_lds_bytes(int K);
-extern "C" hipError_t po_launch_bspline(int B, int W, const int *n_way, const double *wx, const double *wy, int M, double *x, double *y, double *s, int *n_samples, hipStream_t st);
-extern "C" hipError_t po_launch_segment_raw(const po::DevSpline *in, int P, double *x, double *y, double *s, double *angle, double *k, int *n_points, hipStream_t st);
-extern "C" hipError_t po_launch_post_project(const po::DevSpline *in, int L, const int *n_layers, const double *layer_s, const double *off, double *x, double *y, double *s,
-                                             double *length_out, hipStream_t st);
-extern "C" hipError_t po_launch_segment_init(const po::DevSpline *in, const double *start, int start_stride, const double *goal, int goal_stride, int exact, double *init,
-                                             int *ok, hipStream_t st);
-extern "C" hipError_t po_launch_plan_gate(const po::PlanGate *g, hipStream_t st);
-extern "C" hipError_t po_launch_plan_gather(const po::PlanRows *r, hipStream_t st);
-extern "C" hipError_t po_launch_plan_scatter(const po::PlanRows *r, hipStream_t st);
-extern "C" hipError_t po_launch_plan_clear(int B, int N, const int *stage, double *states, po_info *info, hipStream_t st);
-
-#define HIP_TRY(x)                                               \
-    do {                                                         \
-        if (po_internal_hip_fail((x), #x)) return PO_ERR_HIP;    \
-    } while (0)
-#define PO_TRY(x)                    \
-    do {                             \
-        const int rc_ = (x);         \
-        if (rc_ != PO_OK) return rc_; \
-    } while (0)
-
-namespace {
-int dev_spline(po_handle h, const po_spline_in *in, po::DevSpline *D) {
-    if (!in || in->B < 0 || in->K < 3 || (in->B > 0 && (!in->knot_s || !in->knot_x || !in->knot_y))) return PO_ERR_INVALID;
-    if (po_spline_lds_bytes(in->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
-    (void)h;  // the spline coefficients are fitted in LDS by each consumer kernel
-    D->B = in->B; D->K = in->K; D->knot_s = in->knot_s; D->knot_x = in->knot_x; D->knot_y = in->knot_y; D->n_knots = in->n_knots; D->length = in->length;
-    D->coef = nullptr;
-    return PO_OK;
-}
-struct Arena {  // bump allocator over the handle's plan arena
-    char *p = nullptr;
-    size_t off = 0, cap = 0;
-    template <typename T> T *take(size_t n) {
-        off = (off + 15) & ~(size_t)15;
-        T *r = reinterpret_cast<T *>(p + off);
-        off += sizeof(T) * n;
-        return r;
-    }
-};
-}  // namespace
 
 extern "C" {
 
@@ -74,84 +21,92 @@ int po_bspline_batch_device(po_handle h, int B, int W, const int *n_way, const d
     if (!h || B < 0 || W < 1 || M < 2 || (B > 0 && (!way_x || !way_y || !x || !y || !s || !n_samples))) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
     if (sizeof(double) * 2 * (size_t)W > 64 * 1024) return PO_ERR_UNSUPPORTED;
-    HIP_TRY(hipSetDevice(po_internal_device(h)));
-    HIP_TRY(po_launch_bspline(B, W, n_way, way_x, way_y, M, x, y, s, n_samples, po_internal_stream(h)));
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(po_launch_bspline(B, W, n_way, way_x, way_y, M, x, y, s, n_samples, h->stream));
     return PO_OK;
 }
 
 int po_segment_raw_batch_device(po_handle h, const po_spline_in *raw, int P, double *x, double *y, double *s, double *angle, double *k, int *n_points) {
-    if (!h || P < 1 || !raw || (raw->B > 0 && (!x || !y || !s || !angle || !k || !n_points))) return PO_ERR_INVALID;
-    po::DevSpline D{};
-    PO_TRY(dev_spline(h, raw, &D));
+    if (!h || P < 1 || !spline_args_ok(raw, false) || (raw->B > 0 && (!x || !y || !s || !angle || !k || !n_points))) return PO_ERR_INVALID;
+    if (po_spline_lds_bytes(raw->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
     if (raw->B == 0) return PO_OK;
-    HIP_TRY(hipSetDevice(po_internal_device(h)));
-    HIP_TRY(po_launch_segment_raw(&D, P, x, y, s, angle, k, n_points, po_internal_stream(h)));
+    const po::DevSpline D = make_dev_spline(raw);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(po_launch_segment_raw(&D, P, x, y, s, angle, k, n_points, h->stream));
     return PO_OK;
 }
 
 int po_post_project_batch_device(po_handle h, const po_spline_in *spline, int L, const int *n_layers, const double *layer_s, const double *offsets, double *x, double *y,
                                  double *s, double *length) {
-    if (!h || L < 1 || !spline || (spline->B > 0 && (!layer_s || !offsets || !x || !y || !s))) return PO_ERR_INVALID;
-    po::DevSpline D{};
-    PO_TRY(dev_spline(h, spline, &D));
+    if (!h || L < 1 || !spline_args_ok(spline, false) || (spline->B > 0 && (!layer_s || !offsets || !x || !y || !s))) return PO_ERR_INVALID;
+    if (po_spline_lds_bytes(spline->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
     if (spline->B == 0) return PO_OK;
-    HIP_TRY(hipSetDevice(po_internal_device(h)));
-    HIP_TRY(po_launch_post_project(&D, L, n_layers, layer_s, offsets, x, y, s, length, po_internal_stream(h)));
+    const po::DevSpline D = make_dev_spline(spline);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(po_launch_post_project(&D, L, n_layers, layer_s, offsets, x, y, s, length, h->stream));
     return PO_OK;
 }
 
 int po_segment_init_batch_device(po_handle h, const po_spline_in *spline, const double *start, int start_stride, const double *goal, int goal_stride, double *init, int *ok) {
-    if (!h || !spline || start_stride < 3 || goal_stride < 2 || (spline->B > 0 && (!spline->length || !start || !goal || !init || !ok))) return PO_ERR_INVALID;
-    po::DevSpline D{};
-    PO_TRY(dev_spline(h, spline, &D));
+    if (!h || start_stride < 3 || goal_stride < 2 || !spline_args_ok(spline) || (spline->B > 0 && (!start || !goal || !init || !ok))) return PO_ERR_INVALID;
+    if (po_spline_lds_bytes(spline->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
     if (spline->B == 0) return PO_OK;
-    HIP_TRY(hipSetDevice(po_internal_device(h)));
-    HIP_TRY(po_launch_segment_init(&D, start, start_stride, goal, goal_stride, po_internal_params(h)->enable_exact_position, init, ok, po_internal_stream(h)));
+    const po::DevSpline D = make_dev_spline(spline);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(po_launch_segment_init(&D, start, start_stride, goal, goal_stride, h->params.enable_exact_position, init, ok, h->stream));
     return PO_OK;
 }
 
+// The argument check of po_plan_batch and po_plan_batch_device
+static bool plan_args_ok(po_handle h, const po_plan_in *in, const po_plan_out *out) {
+    if (!h || !in || !out || in->B < 0 || in->W < 4 || in->N < 2) return false;
+    return in->B == 0 || (in->way_x && in->way_y && in->start && in->goal && out->states && out->n_states && out->ok);
+}
+
 static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_out *out) {
-    if (!h || !in || !out || in->B < 0 || in->W < 4 || in->N < 2) return PO_ERR_INVALID;
-    if (in->B > 0 && (!in->way_x || !in->way_y || !in->start || !in->goal || !out->states || !out->n_states || !out->ok)) return PO_ERR_INVALID;
+    if (!plan_args_ok(h, in, out)) return PO_ERR_INVALID;
     if (!(in->max_length > 0)) return PO_ERR_INVALID;  // the device entry cannot look at the waypoints
-    if (!po_internal_has_map(h)) return PO_ERR_INVALID;
+    if (!h->map.d) return PO_ERR_INVALID;
     const int B = in->B;
     if (B == 0) return PO_OK;
-    const po_params *prm = po_internal_params(h);
-    hipStream_t st = po_internal_stream(h);
-    HIP_TRY(hipSetDevice(po_internal_device(h)));
+    const po_params *prm = &h->params;
+    hipStream_t st = h->stream;
+    HIP_TRY(hipSetDevice(h->device));
     // capacities from the waypoint polyline length: a B-spline is never longer than its control polygon
     const double Lmax = in->max_length;
     const int M = (int)std::ceil(Lmax) + 6, P = (int)std::ceil(Lmax) + 6;
     const int Lc = std::min(512, std::max((int)std::ceil((Lmax + 3) / prm->search_long_spacing), 14) + 8);  // layers every search_long_spacing (0.5 m when <= 6 m long)
     const int N = in->N;
     const size_t bM = (size_t)B * M, bP = (size_t)B * P, bL = (size_t)B * Lc, bN = (size_t)B * N;
-    size_t need = sizeof(double) * (3 * bM + 8 * bP + 7 * bL + 13 * bN + 5 * bN + 16 * (size_t)B) + sizeof(po_info) * 3 * (size_t)B + sizeof(int) * 16 * (size_t)B + 4096;
-    need += sizeof(double) * (20 * bN + 8 * (size_t)B) + sizeof(po_info) * (size_t)B;  // group staging + KPC limits (worst case: one group of everything)
     const bool raw_out = prm->enable_raw_output != 0;
-    if (!raw_out) need += sizeof(double) * 5 * bN + 64;  // QP states before the densifying output branch
-    Arena A;
-    A.p = static_cast<char *>(po_internal_arena(h, need));
-    if (!A.p) return PO_ERR_NOMEM;
-    A.cap = need;
-    double *bs_x = A.take<double>(bM), *bs_y = A.take<double>(bM), *bs_s = A.take<double>(bM);
-    double *rw_x = A.take<double>(bP), *rw_y = A.take<double>(bP), *rw_s = A.take<double>(bP), *rw_a = A.take<double>(bP), *rw_k = A.take<double>(bP);
-    double *t2_x = A.take<double>(bP), *t2_y = A.take<double>(bP), *t2_s = A.take<double>(bP);
-    double *ly_s = A.take<double>(bL), *ly_lb = A.take<double>(bL), *ly_ub = A.take<double>(bL), *ly_off = A.take<double>(bL);
-    double *k2_x = A.take<double>(bL), *k2_y = A.take<double>(bL), *k2_s = A.take<double>(bL);
-    double *rf_x = A.take<double>(bN), *rf_y = A.take<double>(bN), *rf_z = A.take<double>(bN), *rf_k = A.take<double>(bN), *rf_s = A.take<double>(bN);
-    double *bnd = A.take<double>(8 * bN);
-    double *len1 = A.take<double>(B), *len2 = A.take<double>(B), *len3 = A.take<double>(B), *l0 = A.take<double>(B), *start3 = A.take<double>(3 * (size_t)B);
-    double *init = A.take<double>(3 * (size_t)B), *x0 = A.take<double>(3 * (size_t)B), *goal_z = A.take<double>(B);
-    po_info *info1 = A.take<po_info>(B), *info2 = A.take<po_info>(B), *info3 = out->info ? out->info : A.take<po_info>(B);
-    int *n_bs = A.take<int>(B), *n_raw = A.take<int>(B), *n_lay = A.take<int>(B), *n_ref = A.take<int>(B), *n_val = A.take<int>(B), *okseg = A.take<int>(B);
-    int *keep = A.take<int>(B), *stage = out->stage ? out->stage : A.take<int>(B), *gidx = A.take<int>(B), *g_n = A.take<int>(B);
-    double *g_x = A.take<double>(bN), *g_y = A.take<double>(bN), *g_z = A.take<double>(bN), *g_k = A.take<double>(bN), *g_s = A.take<double>(bN);
-    double *g_b = A.take<double>(8 * bN), *g_x0 = A.take<double>(3 * (size_t)B), *g_goal = A.take<double>(B), *g_states = A.take<double>(5 * bN);
-    po_info *g_info = A.take<po_info>(B);
-    double *lim_k = A.take<double>(bN), *lim_kp = A.take<double>(bN);
-    double *qp_states = raw_out ? out->states : A.take<double>(5 * bN);  // optimizePath's two output branches (path_optimizer.cpp:191 / :201)
-    if (A.off > A.cap) return PO_ERR_NOMEM;
+    // every intermediate is a slot of the handle's plan arena: declared here, sized from the declarations, resolved when the arena is reserved
+    Stage A;
+    auto D = [&A](size_t n) { return A.scratch<double>(n); };
+    auto I = [&A](size_t n) { return A.scratch<int>(n); };
+    auto Q = [&A](size_t n) { return A.scratch<po_info>(n); };
+    const size_t nB = B;
+    Slot<double> bs_x = D(bM), bs_y = D(bM), bs_s = D(bM);
+    Slot<double> rw_x = D(bP), rw_y = D(bP), rw_s = D(bP), rw_a = D(bP), rw_k = D(bP);
+    Slot<double> t2_x = D(bP), t2_y = D(bP), t2_s = D(bP);
+    Slot<double> ly_s = D(bL), ly_lb = D(bL), ly_ub = D(bL), ly_off = D(bL);
+    Slot<double> k2_x = D(bL), k2_y = D(bL), k2_s = D(bL);
+    Slot<double> rf_x = D(bN), rf_y = D(bN), rf_z = D(bN), rf_k = D(bN), rf_s = D(bN);
+    Slot<double> bnd = D(8 * bN);
+    Slot<double> len1 = D(nB), len2 = D(nB), len3 = D(nB), l0 = D(nB), start3 = D(3 * nB);
+    Slot<double> init = D(3 * nB), x0 = D(3 * nB), goal_z = D(nB);
+    Slot<po_info> info1 = Q(nB), info2 = Q(nB), own_info3 = out->info ? Slot<po_info>{} : Q(nB);
+    Slot<int> n_bs = I(nB), n_raw = I(nB), n_lay = I(nB), n_ref = I(nB), n_val = I(nB), okseg = I(nB);
+    Slot<int> keep = I(nB), own_stage = out->stage ? Slot<int>{} : I(nB), gidx = I(nB), g_n = I(nB);
+    // group staging + KPC limits (worst case: one group of everything)
+    Slot<double> g_x = D(bN), g_y = D(bN), g_z = D(bN), g_k = D(bN), g_s = D(bN);
+    Slot<double> g_b = D(8 * bN), g_x0 = D(3 * nB), g_goal = D(nB), g_states = D(5 * bN);
+    Slot<po_info> g_info = Q(nB);
+    Slot<double> lim_k = D(bN), lim_kp = D(bN);
+    Slot<double> own_states = raw_out ? Slot<double>{} : D(5 * bN);  // QP states before the densifying output branch
+    PO_TRY(A.reserve(h, h->plan_arena));
+    po_info *info3 = out->info ? out->info : own_info3.ptr();
+    int *stage = out->stage ? out->stage : own_stage.ptr();
+    double *qp_states = raw_out ? out->states : own_states.ptr();  // optimizePath's two output branches (path_optimizer.cpp:191 / :201)
 
     po::PlanGate G{};
     G.B = B; G.stage = stage; G.start = in->start; G.goal = in->goal;
@@ -226,7 +181,8 @@ static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_o
         HIP_TRY(po_launch_plan_gather(&R, st));
         // KPC with a spline-built reference: updateLimits() has no speed profile ("Reference states must be given directly!") and falls back to
         // max_k = tan(max_steering_angle) / wheel_base, max_kp = DBL_MAX (reference_path_impl.cpp:214-222)
-        po_batch_in qi{form, Gn, Ng, kv.first, g_x, g_y, g_z, g_k, g_s, g_b, g_x0, g_goal, form == PO_KPC ? lim_k : nullptr, form == PO_KPC ? lim_kp : nullptr, g_n};
+        const double *gk = form == PO_KPC ? lim_k.ptr() : nullptr, *gkp = form == PO_KPC ? lim_kp.ptr() : nullptr;
+        po_batch_in qi{form, Gn, Ng, kv.first, g_x, g_y, g_z, g_k, g_s, g_b, g_x0, g_goal, gk, gkp, g_n};
         po_batch_out qo{g_states, g_info, nullptr};
         const int rc = po_solve_batch_device(h, &qi, &qo);
         if (rc == PO_ERR_UNSUPPORTED) {  // does not fit the on-chip tile: flagged per instance, the others go on
@@ -253,13 +209,12 @@ static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_o
 
 int po_plan_batch_device(po_handle h, const po_plan_in *in, const po_plan_out *out) {
     if (!h) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(*po_internal_plan_mutex(h));
+    std::lock_guard<std::mutex> g(h->call_mu);
     return plan_device_locked(h, in, out);
 }
 
 int po_plan_batch(po_handle h, const po_plan_in *in, const po_plan_out *out) {
-    if (!h || !in || !out || in->B < 0 || in->W < 4 || in->N < 2) return PO_ERR_INVALID;
-    if (in->B > 0 && (!in->way_x || !in->way_y || !in->start || !in->goal || !out->states || !out->n_states || !out->ok)) return PO_ERR_INVALID;
+    if (!plan_args_ok(h, in, out)) return PO_ERR_INVALID;
     const int B = in->B;
     if (B == 0) return PO_OK;
     double Lmax = in->max_length;
@@ -272,37 +227,22 @@ int po_plan_batch(po_handle h, const po_plan_in *in, const po_plan_out *out) {
             Lmax = std::max(Lmax, len);
         }
     }
-    hipStream_t st = po_internal_stream(h);
-    HIP_TRY(hipSetDevice(po_internal_device(h)));
-    const size_t bw = sizeof(double) * (size_t)B * in->W, bstates = sizeof(double) * (size_t)B * in->N * 5;
-    const size_t total = 2 * bw + sizeof(double) * 7 * (size_t)B + sizeof(int) * 4 * (size_t)B + bstates + sizeof(po_info) * (size_t)B + 256;
-    std::lock_guard<std::mutex> g(*po_internal_plan_mutex(h));
-    void *raw = po_internal_plan_host(h, total);  // staging block of the host-pointer entry (the arena belongs to the device entry)
-    if (!raw) return PO_ERR_NOMEM;
-    Arena A; A.p = static_cast<char *>(raw); A.cap = total;
-    double *wx = A.take<double>((size_t)B * in->W), *wy = A.take<double>((size_t)B * in->W), *d_start = A.take<double>(4 * (size_t)B), *d_goal = A.take<double>(3 * (size_t)B);
-    double *d_states = A.take<double>((size_t)B * in->N * 5);
-    po_info *d_info = A.take<po_info>(B);
-    int *d_nway = A.take<int>(B), *d_n = A.take<int>(B), *d_ok = A.take<int>(B), *d_stage = A.take<int>(B);
-    int rc = PO_OK;
-    auto fail = [&](int code) { return code; };
-    if (po_internal_hip_fail(hipMemcpyAsync(wx, in->way_x, bw, hipMemcpyHostToDevice, st), "H2D way_x")) return fail(PO_ERR_HIP);
-    if (po_internal_hip_fail(hipMemcpyAsync(wy, in->way_y, bw, hipMemcpyHostToDevice, st), "H2D way_y")) return fail(PO_ERR_HIP);
-    if (po_internal_hip_fail(hipMemcpyAsync(d_start, in->start, sizeof(double) * 4 * B, hipMemcpyHostToDevice, st), "H2D start")) return fail(PO_ERR_HIP);
-    if (po_internal_hip_fail(hipMemcpyAsync(d_goal, in->goal, sizeof(double) * 3 * B, hipMemcpyHostToDevice, st), "H2D goal")) return fail(PO_ERR_HIP);
-    if (in->n_way && po_internal_hip_fail(hipMemcpyAsync(d_nway, in->n_way, sizeof(int) * B, hipMemcpyHostToDevice, st), "H2D n_way")) return fail(PO_ERR_HIP);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t nB = B, bw = nB * in->W;
+    Stage S;  // the staging block of the host-pointer entry (the arena belongs to the device entry)
+    const Slot<double> wx = S.in(in->way_x, bw), wy = S.in(in->way_y, bw), d_start = S.in(in->start, 4 * nB), d_goal = S.in(in->goal, 3 * nB);
+    const Slot<int> d_nway = S.in(in->n_way, nB);
+    // stage / info: the device arrays always exist and the stages write them; a null host pointer only skips the copy back
+    const Slot<double> d_states = S.out(out->states, nB * in->N * 5);
+    const Slot<int> d_n = S.out(out->n_states, nB), d_ok = S.out(out->ok, nB), d_stage = S.out(out->stage, nB);
+    const Slot<po_info> d_info = S.out(out->info, nB);
+    std::lock_guard<std::mutex> g(h->call_mu);
+    PO_TRY(S.upload(h, h->plan_host));
     po_plan_in din = *in;
-    din.way_x = wx; din.way_y = wy; din.start = d_start; din.goal = d_goal; din.n_way = in->n_way ? d_nway : nullptr; din.max_length = Lmax;
-    po_plan_out dout{d_states, d_n, d_ok, d_stage, d_info};
-    rc = plan_device_locked(h, &din, &dout);
-    if (rc != PO_OK) return fail(rc);
-    if (po_internal_hip_fail(hipMemcpyAsync(out->states, d_states, bstates, hipMemcpyDeviceToHost, st), "D2H states")) return fail(PO_ERR_HIP);
-    if (po_internal_hip_fail(hipMemcpyAsync(out->n_states, d_n, sizeof(int) * B, hipMemcpyDeviceToHost, st), "D2H n")) return fail(PO_ERR_HIP);
-    if (po_internal_hip_fail(hipMemcpyAsync(out->ok, d_ok, sizeof(int) * B, hipMemcpyDeviceToHost, st), "D2H ok")) return fail(PO_ERR_HIP);
-    if (out->stage && po_internal_hip_fail(hipMemcpyAsync(out->stage, d_stage, sizeof(int) * B, hipMemcpyDeviceToHost, st), "D2H stage")) return fail(PO_ERR_HIP);
-    if (out->info && po_internal_hip_fail(hipMemcpyAsync(out->info, d_info, sizeof(po_info) * B, hipMemcpyDeviceToHost, st), "D2H info")) return fail(PO_ERR_HIP);
-    if (po_internal_hip_fail(hipStreamSynchronize(st), "sync")) return fail(PO_ERR_HIP);
-    return PO_OK;
+    din.way_x = wx; din.way_y = wy; din.start = d_start; din.goal = d_goal; din.n_way = d_nway; din.max_length = Lmax;
+    const po_plan_out dout{d_states, d_n, d_ok, d_stage, d_info};
+    PO_TRY(plan_device_locked(h, &din, &dout));
+    return S.copy_out(h);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "../../include/po_hip.h"
 #include "../../include/po_pmath.h"  // portable sin / cos / atan2: the same IEEE operation sequence as the oracle's portable-math mode (bit-exact map stages)
 #define PO_MAP_DEVICE_CODE
+#include "po_launch.hpp"
 #include "po_map.hpp"
 
 namespace po {

@@ -24,6 +24,7 @@
 #include "../../include/po_hip.h"
 #define PO_MAP_DEVICE_CODE
 #include "po_device.hpp"
+#include "po_launch.hpp"
 #include "po_map.hpp"
 #include "po_smooth.hpp"
 

@@ -3,6 +3,7 @@
 //   -DPO_UNI=0 -DPO_REF=3     the Newton refinement (po_params.refine = 2): newton_kernel + newton_fallback_kernel, nothing else.
 // Sixteen objects that build in parallel (KP: its shapes in groups — keep 1 .. 8 / the wide role-split shapes of keep 9 .. 16 — and the Newton refinement of each group by kind of shape).  -DPO_DEV_HEADLINE (dev builds only) keeps just one shape (po_solve_common.hpp).
 #include "po_solve_common.hpp"
+#include "po_launch.hpp"
 
 #if !defined(PO_FORM) || !defined(PO_UNI)
 #error "compile with -DPO_FORM=0|1|2 -DPO_UNI=0|1"
