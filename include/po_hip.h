@@ -268,7 +268,7 @@ int po_device_count(void);
  * entry takes the handle's inner lock while it enqueues, owns no staging, and its scratch is ordered by the stream.  The library orders the calls; every call returns
  * what it would return in SOME serial order of the calls, i.e. what the same call returns on a handle nobody else uses (results do not depend on what a handle ran
  * before: tests/test_handle_contract.py).  Two calls on one handle never overlap on the device — use two handles for that.
- * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_set_map_occupancy* / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
+ * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_set_map_occupancy* / po_set_map_stack* / po_set_map_assignment* / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
  * start afterwards use the new stream / map / switch, and the caller orders what is already enqueued on the old stream.  po_last_kernel_ms / po_last_phase_ms
  * describe the handle's last solve, whichever thread made it.  po_destroy must not race with any call. */
 int po_create(int device, const po_params *params, po_handle *out);
@@ -286,7 +286,8 @@ int po_set_stream(po_handle h, void *hip_stream);
 int po_debug_set(po_handle h, const char *key, int value);
 /* Developer read-back (synchronises the stream): "fallback_paths" = how many paths the Newton launch of the last solve with refine = 2 did not certify and handed to
  * the fallback launch; "newton_parked" = how many went on into the second of the sliced Newton launches (-1: the last solve was not sliced); "map_ptr" = the device
- * address of the handle's map layer (0: no map; does not synchronise — po_set_map_occupancy_device with an unchanged size must leave it where it is). */
+ * address of the handle's map layer — layer 0 of the stack (0: no map; does not synchronise — po_set_map_occupancy_device / po_set_map_stack_occupancy_device with
+ * an unchanged size and layer count must leave it where it is); "map_layers" = M, the number of layers the handle holds (0: no map; does not synchronise). */
 int po_debug_get(po_handle h, const char *key, long long *value);
 
 /* Host-pointer entry: H2D, solve, D2H, synchronous. */
@@ -327,6 +328,33 @@ int po_set_map_occupancy_device(po_handle h, const po_occupancy *occ);
 /* Read the handle's current map back: geometry into *geometry_out (its `distance` is set to NULL) and, when distance_or_null is given, the layer
  * [size_y][size_x] into that host buffer.  Synchronous.  PO_ERR_INVALID when no map is set. */
 int po_get_map(po_handle h, po_map *geometry_out, float *distance_or_null);
+/* ---- per-instance maps: a STACK of layers and an ASSIGNMENT of instances to layers ----
+ * A handle holds M >= 1 layers of one size_x, size_y and resolution (what po_distance_map_batch produces), each with its own map-centre position, and optionally a
+ * table layer_of[n] that says which layer instance b of a batch reads.
+ *   Single-map entries.  po_set_map and po_set_map_occupancy* install a stack with M = 1.  po_get_map, po_map_sample and po_debug_get "map_ptr" mean layer 0.
+ *   Reading the assignment.  With no assignment every instance reads layer 0.  With an assignment of length n, instance b of ANY map-reading batch entry
+ *     (po_bounds_batch*, po_dp_search_batch*, po_smooth_batch* with PO_SMOOTH_TENSION, po_postcheck_batch*, po_densify_batch*, and every map stage inside
+ *     po_plan_batch*) reads layer layer_of[b].  A batch with B > n returns PO_ERR_INVALID.
+ *   Validation.  po_set_map_assignment (host pointer) checks the table: any value outside [0, M) returns PO_ERR_INVALID and leaves the handle unchanged (the previous
+ *     table stays in force); so does a table given before any map.  po_set_map_assignment_device cannot look at the table: every kernel clamps the index into
+ *     [0, M - 1] where it reads it, so a bad table selects a wrong layer, never an address outside the stack.
+ *   Lifetime.  An install that changes M clears the assignment; an install with the same M keeps it (a per-cycle refresh of M local grids does not re-send the table).
+ *     n = 0 or layer_of = NULL clears it.
+ *   Stack entries.  `layers->distance` / `occ->cells` hold M layers / images [M][size_y][size_x], one after the other; pos_xy is [M][2], the centre (x, y) of each
+ *     layer, or NULL = every layer at layers->pos_x / pos_y (occ->pos_x / pos_y).  po_set_map_stack and po_set_map_stack_occupancy take host pointers and are
+ *     synchronous.  po_set_map_stack_occupancy_device: `occ->cells` AND pos_xy are device pointers and everything is enqueued on the handle's stream (both must stay
+ *     valid until the stream has passed the call); it keeps the contract of po_set_map_occupancy_device — with the M and size the handle already holds it allocates
+ *     nothing and does not synchronise, and "map_ptr" stays where it is; when a block has to grow it synchronises the stream first.  The layers are bit for bit
+ *     what po_distance_map_batch returns for the same images.
+ *   Limits: those of po_distance_map_batch — 1 .. 4096 cells per side, M <= 65535, beyond: PO_ERR_UNSUPPORTED (po_set_map_stack too).
+ *   po_get_map_layer / po_map_sample_layer: po_get_map / po_map_sample for layer k; k outside [0, M): PO_ERR_INVALID. */
+int po_set_map_stack(po_handle h, int M, const po_map *layers, const double *pos_xy);                      /* host pointers, synchronous */
+int po_set_map_stack_occupancy(po_handle h, int M, const po_occupancy *occ, const double *pos_xy);         /* host pointers, synchronous */
+int po_set_map_stack_occupancy_device(po_handle h, int M, const po_occupancy *occ, const double *pos_xy);  /* cells and pos_xy are device pointers; on the stream */
+int po_set_map_assignment(po_handle h, int n, const int *layer_of);          /* host pointer; n = 0 or NULL clears */
+int po_set_map_assignment_device(po_handle h, int n, const int *layer_of);   /* device pointer, copied on the stream */
+int po_get_map_layer(po_handle h, int k, po_map *geometry_out, float *distance_or_null);
+int po_map_sample_layer(po_handle h, int k, int n, const double *xy, double *dist, int *inside);
 /* For every path: walk the optimised states in order and stop at the first state that fails
  * CollisionChecker::isSingleStateCollisionFreeImproved (src/tools/collision_checker.cpp:42-59: bounding circle, then the
  * six footprint circles of src/tools/car_geometry.cpp:38-72; outside the map = collision).
@@ -518,7 +546,9 @@ const char *po_strerror(int code);
 const char *po_last_hip_error(void);
 /* "po_hip <abi> (gfx950)"; PO_ABI_VERSION is bumped whenever a struct layout, an entry point or the meaning of a field changes (5: round 5, see po_params.refine;
  * 6: round 6, po_info.status_refine / status_polish may be PO_NOT_AVAILABLE; po_create refuses refine_rounds + refine_extra_rounds >= 32; 7: po_occupancy,
- * po_distance_map_batch*, po_set_map_occupancy*, po_get_map, po_debug_get "map_ptr").  A binding should compare
+ * po_distance_map_batch*, po_set_map_occupancy*, po_get_map, po_debug_get "map_ptr").  The map-stack entries
+ * (po_set_map_stack*, po_set_map_assignment*, po_get_map_layer, po_map_sample_layer, po_debug_get "map_layers") were ADDED under 7: no struct layout, no existing
+ * entry and no field's meaning changed, so a binding written against 7 drives this library unchanged; one that needs the new entries looks the symbols up.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7
 const char *po_version(void);

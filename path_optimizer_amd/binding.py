@@ -25,7 +25,9 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_resample_batch", "po_resample_batch_device", "po_limits_batch", "po_limits_batch_device", "po_dp_search_batch",
            "po_dp_search_batch_device", "po_bspline_batch_device", "po_segment_raw_batch_device", "po_post_project_batch_device",
            "po_segment_init_batch_device", "po_plan_batch", "po_plan_batch_device", "po_densify_batch", "po_densify_batch_device",
-           "po_distance_map_batch", "po_distance_map_batch_device", "po_set_map_occupancy", "po_set_map_occupancy_device", "po_get_map"]
+           "po_distance_map_batch", "po_distance_map_batch_device", "po_set_map_occupancy", "po_set_map_occupancy_device", "po_get_map",
+           "po_set_map_stack", "po_set_map_stack_occupancy", "po_set_map_stack_occupancy_device", "po_set_map_assignment", "po_set_map_assignment_device",
+           "po_get_map_layer", "po_map_sample_layer"]
 
 
 class PoError(RuntimeError):
@@ -70,6 +72,13 @@ def lib():
         L.po_set_map_occupancy.argtypes = [C.c_void_p, C.c_void_p]
         L.po_set_map_occupancy_device.argtypes = [C.c_void_p, C.c_void_p]
         L.po_get_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_set_map_stack.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_set_map_stack_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_set_map_stack_occupancy_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_set_map_assignment.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.po_set_map_assignment_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.po_get_map_layer.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_map_sample_layer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -271,6 +280,88 @@ class Engine:
         d = np.empty((m.size_x, m.size_y), dtype=np.float32, order="F")
         _check(lib().po_get_map(self._h, C.byref(m), d.ctypes.data_as(C.c_void_p)))
         return d, m.resolution, m.pos_x, m.pos_y
+
+    # ---- per-instance maps: a stack of layers and an assignment of instances to layers ----
+    @staticmethod
+    def _pos_xy(pos_xy, M):
+        if pos_xy is None:
+            return None
+        p = np.ascontiguousarray(pos_xy, dtype=np.float64)
+        if p.shape != (M, 2):
+            raise ValueError("pos_xy must be [M, 2]")
+        return p
+
+    def set_map_stack(self, dists, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0):
+        """Install M distance layers dists[M, size_x, size_y] (float32, each indexed like set_map's `dist`).  pos_xy [M, 2]: the centre of each layer; None: every
+        layer at (pos_x, pos_y)."""
+        from .abi import PoMap
+
+        d = np.asarray(dists, dtype=np.float32)
+        if d.ndim != 3:
+            raise ValueError("dists must be [M, size_x, size_y]")
+        M, sx, sy = d.shape
+        mem = np.ascontiguousarray(d.transpose(0, 2, 1))  # [M][size_y][size_x], x contiguous
+        pos = self._pos_xy(pos_xy, M)
+        m = PoMap(mem.ctypes.data_as(C.c_void_p), sx, sy, float(resolution), float(pos_x), float(pos_y))
+        _check(lib().po_set_map_stack(self._h, M, C.byref(m), _np(pos)))
+
+    def set_map_stack_occupancy(self, occ, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0):
+        """Build the stack from M occupancy images occ[M, size_x, size_y] (0 = occupied) on the device; layers bit-identical to distance_map_batch(occ)."""
+        from .abi import PoOccupancy
+
+        o = self._occ_u8(occ)
+        if o.ndim != 3:
+            raise ValueError("occ must be [M, size_x, size_y]")
+        M, sx, sy = o.shape
+        img = np.ascontiguousarray(o.transpose(0, 2, 1))
+        pos = self._pos_xy(pos_xy, M)
+        oc = PoOccupancy(img.ctypes.data_as(C.c_void_p), sx, sy, float(resolution), float(pos_x), float(pos_y))
+        _check(lib().po_set_map_stack_occupancy(self._h, M, C.byref(oc), _np(pos)))
+
+    def set_map_stack_occupancy_device(self, occ, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0):
+        """Device-pointer entry, enqueued on the handle's stream (no synchronisation and no allocation when M and the size are those the handle holds).
+        occ: CONTIGUOUS torch uint8 tensor [M, size_y, size_x] on the handle's device (x contiguous, image after image); pos_xy: contiguous torch float64 tensor
+        [M, 2] on the device, or None.  Both must stay alive until the stream has passed the call."""
+        from .abi import PoOccupancy
+
+        if occ.dim() != 3 or str(occ.dtype) != "torch.uint8" or not occ.is_contiguous():
+            raise ValueError("occ must be a contiguous 3-d torch.uint8 tensor [M, size_y, size_x]")
+        M, sy, sx = (int(v) for v in occ.shape)
+        if pos_xy is not None and (tuple(pos_xy.shape) != (M, 2) or str(pos_xy.dtype) != "torch.float64" or not pos_xy.is_contiguous()):
+            raise ValueError("pos_xy must be a contiguous torch.float64 tensor [M, 2]")
+        oc = PoOccupancy(C.c_void_p(occ.data_ptr()), sx, sy, float(resolution), float(pos_x), float(pos_y))
+        _check(lib().po_set_map_stack_occupancy_device(self._h, M, C.byref(oc), None if pos_xy is None else C.c_void_p(pos_xy.data_ptr())))
+
+    def set_map_assignment(self, layer_of):
+        """layer_of[b] = the layer instance b of every map-reading batch call reads (validated: outside [0, M) raises and the previous table stays); None or
+        empty clears the table — every instance reads layer 0."""
+        a = None if layer_of is None else np.ascontiguousarray(layer_of, dtype=np.int32).reshape(-1)
+        _check(lib().po_set_map_assignment(self._h, 0 if a is None else len(a), _np(a)))
+
+    def set_map_assignment_device(self, layer_of):
+        """Device-pointer entry: contiguous torch int32 tensor [n], copied on the handle's stream (not validated: the kernels clamp each index into [0, M - 1])."""
+        if layer_of is None:
+            _check(lib().po_set_map_assignment_device(self._h, 0, None))
+            return
+        if layer_of.dim() != 1 or str(layer_of.dtype) != "torch.int32" or not layer_of.is_contiguous():
+            raise ValueError("layer_of must be a contiguous 1-d torch.int32 tensor")
+        _check(lib().po_set_map_assignment_device(self._h, int(layer_of.shape[0]), C.c_void_p(layer_of.data_ptr())))
+
+    def get_map_layer(self, k: int):
+        """Layer k of the handle's stack, like get_map: (dist [size_x, size_y] float32, resolution, pos_x, pos_y)."""
+        from .abi import PoMap
+
+        m = PoMap()
+        _check(lib().po_get_map_layer(self._h, int(k), C.byref(m), None))
+        d = np.empty((m.size_x, m.size_y), dtype=np.float32, order="F")
+        _check(lib().po_get_map_layer(self._h, int(k), C.byref(m), d.ctypes.data_as(C.c_void_p)))
+        return d, m.resolution, m.pos_x, m.pos_y
+
+    def map_sample_layer(self, k: int, xy):
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        d = np.zeros(len(xy)); ins = np.zeros(len(xy), dtype=np.int32)
+        _check(lib().po_map_sample_layer(self._h, int(k), len(xy), _np(xy), _np(d), _np(ins)))
+        return d, ins
 
     def postcheck_batch(self, states, info, n_points=None):
         """Host-pointer entry: states [B,N,5], info structured array -> n_valid [B], ok [B]."""

@@ -195,7 +195,11 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
     const std::string k(key);
     std::lock_guard<std::mutex> g(h->mu);
     if (k == "map_ptr") {  // where the handle's map layer lives (0: none); no device call
-        *value = (long long)reinterpret_cast<uintptr_t>(h->map.d);
+        *value = (long long)reinterpret_cast<uintptr_t>(h->maps.d);
+        return PO_OK;
+    }
+    if (k == "map_layers") {  // how many layers the handle's map stack holds (0: no map); no device call
+        *value = h->maps.d ? h->maps.M : 0;
         return PO_OK;
     }
     if (k == "fallback_paths") {  // split scheduling of refine = 2: how many paths the last solve's Newton launch handed to the fallback launch
@@ -665,15 +669,83 @@ static po::DevCar make_car(const po_params &p) {
     return c;
 }
 
+// ---- the map stack.  Every install goes through publish_stack; the single-map entries are the stack entries with M = 1. ----
+// The view the kernels get, after the layers are in place (h->mu held).  An install that changes M drops the assignment, one with the same M keeps it.
+static void publish_stack(po_handle h, int M, int sx, int sy, double res, double px, double py, bool layer_pos) {
+    const bool keep = h->maps.M == M && h->maps.layer_of;
+    po::DevMaps s{};
+    s.d = static_cast<const float *>(h->map_buf.p); s.sx = sx; s.sy = sy; s.res = res; s.px = px; s.py = py;
+    s.M = M; s.stride = (size_t)sx * (size_t)sy;
+    s.pos = layer_pos ? static_cast<const double *>(h->map_pos_buf.p) : nullptr;
+    s.layer_of = keep ? static_cast<const int *>(h->map_assign_buf.p) : nullptr;
+    s.n_assign = keep ? h->maps.n_assign : 0;
+    h->maps = s;
+}
+// M float layers from host memory (h->mu held): upload, synchronise, publish
+static int install_layers(po_handle h, int M, const po_map *map, const double *pos_xy) {
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t bytes = sizeof(float) * (size_t)M * (size_t)map->size_x * (size_t)map->size_y;
+    if (bytes > h->map_buf.cap) h->maps.d = nullptr;  // the old layers are about to be released: no map until the new ones are in place
+    if (int rc = grow_after_sync(h, h->map_buf, bytes)) return rc;
+    if (pos_xy) {
+        if (int rc = grow_after_sync(h, h->map_pos_buf, sizeof(double) * 2 * (size_t)M)) return rc;
+        HIP_TRY(hipMemcpyAsync(h->map_pos_buf.p, pos_xy, sizeof(double) * 2 * (size_t)M, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(h->map_buf.p, map->distance, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    publish_stack(h, M, map->size_x, map->size_y, map->resolution, map->pos_x, map->pos_y, pos_xy != nullptr);
+    return PO_OK;
+}
+
 int po_set_map(po_handle h, const po_map *map) {
     if (!h || !map || !map->distance || map->size_x < 1 || map->size_y < 1 || !(map->resolution > 0)) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
+    return install_layers(h, 1, map, nullptr);
+}
+
+int po_set_map_stack(po_handle h, int M, const po_map *layers, const double *pos_xy) {
+    if (!h || M < 1 || !layers || !layers->distance || layers->size_x < 1 || layers->size_y < 1 || !(layers->resolution > 0)) return PO_ERR_INVALID;
+    if (layers->size_x > po_edt_max_side() || layers->size_y > po_edt_max_side() || M > po_edt_max_images()) return PO_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> call(h->call_mu);
+    std::lock_guard<std::mutex> g(h->mu);
+    return install_layers(h, M, layers, pos_xy);
+}
+
+int po_set_map_assignment_device(po_handle h, int n, const int *layer_of) {
+    if (!h || n < 0) return PO_ERR_INVALID;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (n == 0 || !layer_of) {  // clear: every instance reads layer 0 again (launches already enqueued got the table by value of its address: the block stays)
+        h->maps.layer_of = nullptr; h->maps.n_assign = 0;
+        return PO_OK;
+    }
+    if (!h->maps.d) return PO_ERR_INVALID;  // no stack to assign into
     HIP_TRY(hipSetDevice(h->device));
-    const size_t bytes = sizeof(float) * (size_t)map->size_x * map->size_y;
-    if (int rc = h->map_buf.ensure(bytes)) return rc;
-    HIP_TRY(hipMemcpyAsync(h->map_buf.p, map->distance, bytes, hipMemcpyHostToDevice, h->stream));
+    if (int rc = grow_after_sync(h, h->map_assign_buf, sizeof(int) * (size_t)n)) return rc;
+    HIP_TRY(hipMemcpyAsync(h->map_assign_buf.p, layer_of, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+    h->maps.layer_of = static_cast<const int *>(h->map_assign_buf.p); h->maps.n_assign = n;
+    return PO_OK;
+}
+
+int po_set_map_assignment(po_handle h, int n, const int *layer_of) {
+    if (!h || n < 0) return PO_ERR_INVALID;
+    std::lock_guard<std::mutex> call(h->call_mu);
+    std::lock_guard<std::mutex> g(h->mu);
+    if (n == 0 || !layer_of) {
+        h->maps.layer_of = nullptr; h->maps.n_assign = 0;
+        return PO_OK;
+    }
+    if (!h->maps.d) return PO_ERR_INVALID;
+    for (int b = 0; b < n; ++b)
+        if (layer_of[b] < 0 || layer_of[b] >= h->maps.M) return PO_ERR_INVALID;  // (nothing has been touched: the previous table stays in force)
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = grow_after_sync(h, h->map_assign_buf, sizeof(int) * (size_t)n)) {
+        h->maps.layer_of = nullptr; h->maps.n_assign = 0;  // (the old block is gone)
+        return rc;
+    }
+    // the table replaces one that enqueued launches may still read: the copy is ordered behind them on the stream, and the caller's array is free when we return
+    HIP_TRY(hipMemcpyAsync(h->map_assign_buf.p, layer_of, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->map = po::DevMap{static_cast<const float *>(h->map_buf.p), map->size_x, map->size_y, map->resolution, map->pos_x, map->pos_y};
+    h->maps.layer_of = static_cast<const int *>(h->map_assign_buf.p); h->maps.n_assign = n;
     return PO_OK;
 }
 
@@ -715,24 +787,31 @@ int po_distance_map_batch(po_handle h, int M, const po_occupancy *occ, float *di
     return S.copy_out(h);
 }
 
-int po_set_map_occupancy_device(po_handle h, const po_occupancy *occ) {
-    if (int rc = check_occupancy(h, 1, occ)) return rc;
+int po_set_map_stack_occupancy_device(po_handle h, int M, const po_occupancy *occ, const double *pos_xy) {
+    if (int rc = check_occupancy(h, M, occ)) return rc;
     std::lock_guard<std::mutex> g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
-    // same size as before: both blocks are large enough already — nothing is allocated, nothing waits; the transform overwrites the layer in stream order
-    const size_t layer_bytes = sizeof(float) * (size_t)occ->size_x * occ->size_y;
-    if (layer_bytes > h->map_buf.cap) h->map = po::DevMap{};  // the old layer is about to be released: no map until the new one is in place
-    if (int rc = grow_after_sync(h, h->map_buf, layer_bytes)) return rc;
-    if (int rc = grow_after_sync(h, h->edt_buf, po_edt_scratch_bytes(1, occ->size_x, occ->size_y))) return rc;
-    HIP_TRY(po_launch_edt(occ->cells, 1, occ->size_x, occ->size_y, (float)occ->resolution, h->edt_buf.p, static_cast<float *>(h->map_buf.p), h->stream));
-    h->map = po::DevMap{static_cast<const float *>(h->map_buf.p), occ->size_x, occ->size_y, occ->resolution, occ->pos_x, occ->pos_y};
+    // same M and size as before: every block is large enough already — nothing is allocated, nothing waits; the transform overwrites the layers in stream order
+    const size_t stack_bytes = sizeof(float) * (size_t)M * (size_t)occ->size_x * (size_t)occ->size_y;
+    if (stack_bytes > h->map_buf.cap) h->maps.d = nullptr;  // the old layers are about to be released: no map until the new ones are in place
+    if (int rc = grow_after_sync(h, h->map_buf, stack_bytes)) return rc;
+    if (int rc = grow_after_sync(h, h->edt_buf, po_edt_scratch_bytes(M, occ->size_x, occ->size_y))) return rc;
+    if (pos_xy) {
+        if (int rc = grow_after_sync(h, h->map_pos_buf, sizeof(double) * 2 * (size_t)M)) return rc;
+        HIP_TRY(hipMemcpyAsync(h->map_pos_buf.p, pos_xy, sizeof(double) * 2 * (size_t)M, hipMemcpyDeviceToDevice, h->stream));
+    }
+    HIP_TRY(po_launch_edt(occ->cells, M, occ->size_x, occ->size_y, (float)occ->resolution, h->edt_buf.p, static_cast<float *>(h->map_buf.p), h->stream));
+    publish_stack(h, M, occ->size_x, occ->size_y, occ->resolution, occ->pos_x, occ->pos_y, pos_xy != nullptr);
     return PO_OK;
 }
 
-int po_set_map_occupancy(po_handle h, const po_occupancy *occ) {
-    if (int rc = check_occupancy(h, 1, occ)) return rc;
+int po_set_map_occupancy_device(po_handle h, const po_occupancy *occ) { return po_set_map_stack_occupancy_device(h, 1, occ, nullptr); }
+
+int po_set_map_stack_occupancy(po_handle h, int M, const po_occupancy *occ, const double *pos_xy) {
+    if (int rc = check_occupancy(h, M, occ)) return rc;
     Stage S;
-    const Slot<unsigned char> d_cells = S.in(occ->cells, (size_t)occ->size_x * (size_t)occ->size_y);
+    const Slot<unsigned char> d_cells = S.in(occ->cells, (size_t)M * (size_t)occ->size_x * (size_t)occ->size_y);
+    const Slot<double> d_pos = S.in(pos_xy, 2 * (size_t)M);
     std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and the final synchronisation are one atomic unit (po_handle_s)
     {
         std::lock_guard<std::mutex> g(h->mu);
@@ -741,23 +820,34 @@ int po_set_map_occupancy(po_handle h, const po_occupancy *occ) {
     }
     po_occupancy dev = *occ;
     dev.cells = d_cells;
-    PO_TRY(po_set_map_occupancy_device(h, &dev));
+    PO_TRY(po_set_map_stack_occupancy_device(h, M, &dev, d_pos));
     std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);  // (no output: the synchronise alone) like po_set_map: the caller's image may be reused, the map is in place
+    return S.copy_out(h);  // (no output: the synchronise alone) like po_set_map: the caller's images may be reused, the stack is in place
 }
 
-int po_get_map(po_handle h, po_map *geometry_out, float *distance_or_null) {
+int po_set_map_occupancy(po_handle h, const po_occupancy *occ) { return po_set_map_stack_occupancy(h, 1, occ, nullptr); }
+
+int po_get_map_layer(po_handle h, int k, po_map *geometry_out, float *distance_or_null) {
     if (!h || !geometry_out) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> call(h->call_mu);
     std::lock_guard<std::mutex> g(h->mu);
-    if (!h->map.d) return PO_ERR_INVALID;
-    *geometry_out = po_map{nullptr, h->map.sx, h->map.sy, h->map.res, h->map.px, h->map.py};
+    const po::DevMaps &s = h->maps;
+    if (!s.d || k < 0 || k >= s.M) return PO_ERR_INVALID;
+    double pos[2] = {s.px, s.py};
+    if (s.pos) {  // per-layer centres live on the device (they may have arrived through a device pointer)
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipMemcpyAsync(pos, s.pos + 2 * (size_t)k, sizeof(pos), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    *geometry_out = po_map{nullptr, s.sx, s.sy, s.res, pos[0], pos[1]};
     if (!distance_or_null) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(distance_or_null, h->map.d, sizeof(float) * (size_t)h->map.sx * h->map.sy, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(distance_or_null, s.d + (size_t)k * s.stride, sizeof(float) * s.stride, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return PO_OK;
 }
+
+int po_get_map(po_handle h, po_map *geometry_out, float *distance_or_null) { return po_get_map_layer(h, 0, geometry_out, distance_or_null); }
 
 // One argument check per stage, shared by its device-pointer entry and its host-pointer twin
 static bool postcheck_args_ok(po_handle h, int B, int N, const double *states, const po_info *info, const int *n_valid, const int *ok) {
@@ -770,24 +860,26 @@ static bool densify_args_ok(po_handle h, int B, int N, const double *states, con
 int po_postcheck_batch_device(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid, int *ok) {
     if (!postcheck_args_ok(h, B, N, states, info, n_valid, ok)) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
-    if (!h->map.d && h->params.enable_collision_check) return PO_ERR_INVALID;  // no map set
+    if (!h->maps.d && h->params.enable_collision_check) return PO_ERR_INVALID;  // no map set
+    if (!assignment_covers(h, B)) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));
     const po::DevCar car = make_car(h->params);
-    HIP_TRY(po_launch_postcheck(&h->map, &car, B, N, n_points, states, info, n_valid, ok, h->stream));
+    HIP_TRY(po_launch_postcheck(&h->maps, &car, B, N, n_points, states, info, n_valid, ok, h->stream));
     return PO_OK;
 }
 
 int po_densify_batch_device(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int M, double *out_states, int *n_out, int *ok) {
     if (!densify_args_ok(h, B, N, states, info, M, out_states, n_out, ok)) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
-    if (!h->map.d && h->params.enable_collision_check) return PO_ERR_INVALID;  // no map set
+    if (!h->maps.d && h->params.enable_collision_check) return PO_ERR_INVALID;  // no map set
+    if (!assignment_covers(h, B)) return PO_ERR_INVALID;
     if (!(h->params.output_spacing > 0)) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
     if (sizeof(double) * 15 * (size_t)N > 160 * 1024) return PO_ERR_UNSUPPORTED;
     HIP_TRY(hipSetDevice(h->device));
     const po::DevCar car = make_car(h->params);
-    HIP_TRY(po_launch_densify(&h->map, &car, B, N, n_points, states, info, h->params.output_spacing, M, out_states, n_out, ok, h->stream));
+    HIP_TRY(po_launch_densify(&h->maps, &car, B, N, n_points, states, info, h->params.output_spacing, M, out_states, n_out, ok, h->stream));
     return PO_OK;
 }
 
@@ -836,7 +928,7 @@ static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bo
 int po_bounds_batch_device(po_handle h, const po_bounds_in *in, double *bounds, int *n_valid) {
     if (!bounds_args_ok(h, in, bounds, n_valid)) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
-    if (!h->map.d) return PO_ERR_INVALID;  // po_set_map first
+    if (!h->maps.d || !assignment_covers(h, in->B)) return PO_ERR_INVALID;  // po_set_map first; an assignment covers every instance
     if (in->B == 0) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = h->coef_buf.ensure(sizeof(double) * (size_t)in->B * 2 * 6 * in->K)) return rc;
@@ -848,7 +940,7 @@ int po_bounds_batch_device(po_handle h, const po_bounds_in *in, double *bounds, 
     for (int j = 0; j < 4; ++j) D.d[j] = p.d[j];
     D.radius = std::sqrt((p.car_length / 8) * (p.car_length / 8) + (p.car_width / 2) * (p.car_width / 2)) + p.safety_margin;  // planning_flags.cpp:9
     D.coef = static_cast<double *>(h->coef_buf.p);
-    HIP_TRY(po_launch_bounds(&h->map, &D, bounds, n_valid, h->stream));
+    HIP_TRY(po_launch_bounds(&h->maps, &D, bounds, n_valid, h->stream));
     return PO_OK;
 }
 
@@ -898,7 +990,7 @@ static int smooth_args_ok(const po_smooth_in *in, const po_smooth_out *out) {
 int po_smooth_batch_device(po_handle h, const po_smooth_in *in, const po_smooth_out *out) {
     if (!h || !smooth_args_ok(in, out)) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
-    if (in->kind == PO_SMOOTH_TENSION && !h->map.d) return PO_ERR_INVALID;  // po_set_map first (clearance of every point)
+    if (in->kind == PO_SMOOTH_TENSION && (!h->maps.d || !assignment_covers(h, in->B))) return PO_ERR_INVALID;  // po_set_map first (clearance of every point)
     if (in->B == 0) return PO_OK;
     if (po_smooth_lds_bytes(in->kind, in->P) > 160 * 1024) return PO_ERR_UNSUPPORTED;
     HIP_TRY(hipSetDevice(h->device));
@@ -918,7 +1010,7 @@ int po_smooth_batch_device(po_handle h, const po_smooth_in *in, const po_smooth_
     D.scratch_stride = po_smooth_scratch_doubles(in->kind, in->P);
     if (int rc = h->smooth_buf.ensure(sizeof(double) * D.scratch_stride * (size_t)in->B)) return rc;
     D.scratch = static_cast<double *>(h->smooth_buf.p);
-    D.map = h->map;
+    D.maps = h->maps;
     D.perm_bits = 0;
     D.seq_band = h->env_smooth_seq ? 1 : 0; D.waves = h->env_smooth_waves; D.nopad = h->env_smooth_nopad ? 1 : 0;  // developer A/B switches (read once at po_create)
     if (!h->env_identity && in->B > 8)
@@ -1013,13 +1105,13 @@ int po_dp_search_batch_device(po_handle h, const po_spline_in *in, const double 
     if (!(p.search_lat_spacing > 0) || !(p.search_long_spacing > 0) || !(p.search_lateral_range > 0) ||
         2 * p.search_lateral_range / p.search_lat_spacing + 1 > 64) return PO_ERR_UNSUPPORTED;  // one wave per path: <= 64 lateral samples
     std::lock_guard<std::mutex> g(h->mu);
-    if (!h->map.d) return PO_ERR_INVALID;  // po_set_map first
+    if (!h->maps.d || !assignment_covers(h, in->B)) return PO_ERR_INVALID;  // po_set_map first; an assignment covers every instance
     if (in->B == 0) return PO_OK;
     if (po_dp_lds_bytes(in->K, L) > 160 * 1024) return PO_ERR_UNSUPPORTED;
     HIP_TRY(hipSetDevice(h->device));
     const po::DevSpline D = make_dev_spline(in);
     po::DevSearch Q{p.search_lateral_range, p.search_long_spacing, p.search_lat_spacing, start, L, layer_s, lb, ub, l0, n_layers};
-    HIP_TRY(po_launch_dp_search(&h->map, &D, &Q, h->env_dp_one_wave ? 1 : 0, h->stream));
+    HIP_TRY(po_launch_dp_search(&h->maps, &D, &Q, h->env_dp_one_wave ? 1 : 0, h->stream));
     return PO_OK;
 }
 
@@ -1098,20 +1190,22 @@ int po_dp_search_batch(po_handle h, const po_spline_in *in, const double *start,
     return S.copy_out(h);
 }
 
-int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside) {
+int po_map_sample_layer(po_handle h, int k, int n, const double *xy, double *dist, int *inside) {
     if (!h || n < 0 || (n > 0 && (!xy || !dist || !inside))) return PO_ERR_INVALID;
     std::lock_guard<std::mutex> call(h->call_mu);  // (post_buf is the staging block of po_postcheck_batch / po_densify_batch too)
     std::lock_guard<std::mutex> g(h->mu);
-    if (!h->map.d) return PO_ERR_INVALID;
+    if (!h->maps.d || k < 0 || k >= h->maps.M) return PO_ERR_INVALID;
     if (n == 0) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));
     Stage S;
     const Slot<double> d_xy = S.in(xy, 2 * (size_t)n), d_dist = S.out(dist, n);
     const Slot<int> d_inside = S.out(inside, n);
     PO_TRY(S.upload(h, h->post_buf));
-    HIP_TRY(po_launch_map_sample(&h->map, n, d_xy, d_dist, d_inside, h->stream));
+    HIP_TRY(po_launch_map_sample(&h->maps, k, n, d_xy, d_dist, d_inside, h->stream));
     return S.copy_out(h);
 }
+
+int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside) { return po_map_sample_layer(h, 0, n, xy, dist, inside); }
 
 const char *po_strerror(int code) {
     switch (code) {

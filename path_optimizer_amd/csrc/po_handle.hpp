@@ -102,7 +102,10 @@ struct po_handle_s {
     int env_smooth_waves = 0;
     DevBuf in_buf, out_buf, asm_buf, scale_buf, dbg_buf, map_buf, post_buf, coef_buf, bnd_buf, smooth_buf, smooth_io, plan_io, plan_arena, plan_host;
     DevBuf edt_buf, edt_io;  // occupancy -> distance transform: the 16-bit intermediate (2 bytes per cell); staging of the host-pointer entries (image + layers)
-    po::DevMap map{};  // obstacle-distance layer (po_set_map); map.d == nullptr until set
+    // The map stack: M layers in map_buf, their centres in map_pos_buf when they differ, the instance -> layer table in map_assign_buf.
+    // maps is the view the kernels get; maps.d == nullptr until a map is set (maps.M survives a failed re-install: "same M keeps the assignment" is judged against it).
+    DevBuf map_pos_buf, map_assign_buf;
+    po::DevMaps maps{};
     // Two locks, always taken in the order call_mu -> mu:
     // mu       guards the handle's fields and grow-only blocks while a device-pointer entry reads them and enqueues its launches;
     // call_mu  is the CALL lock: every host-pointer entry (and po_plan_batch*, whose stages share the plan arena) holds it from before its first ensure() until its
@@ -117,6 +120,9 @@ inline int grow_after_sync(po_handle h, DevBuf &buf, size_t bytes) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     return buf.ensure(bytes);
 }
+
+// A batch of B instances on the handle's map stack: with an assignment installed, every instance needs an entry of the table.  (h->mu held.)
+inline bool assignment_covers(const po_handle_s *h, int B) { return !h->maps.layer_of || B <= h->maps.n_assign; }
 
 // ---- Stage: the format of one staging block of a host-pointer entry.  The entry DECLARES its arrays, in any order, and gets a slot for each; reserve() sizes the
 // block from those declarations and grows the DevBuf it lives in, copy_in() enqueues one H2D copy per declared input, copy_out() one D2H copy per wanted output and

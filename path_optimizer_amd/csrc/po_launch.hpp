@@ -9,7 +9,7 @@
 
 namespace po {
 struct DevBatch; struct DevParams;                                                   // po_device.hpp
-struct DevMap; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
+struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
 struct DevResample; struct PlanGate; struct PlanRows;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
@@ -56,15 +56,15 @@ int po_has_polish_kernel_k(int N, int C, int keep);
 #undef PO_DECL_SIZES
 
 // ---- po_post.hip: map stages, spline stages, the glue of po_plan ----
-hipError_t po_launch_postcheck(const po::DevMap *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid,
+hipError_t po_launch_postcheck(const po::DevMaps *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid,
                                int *ok, hipStream_t st);
-hipError_t po_launch_densify(const po::DevMap *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info, double spacing,
+hipError_t po_launch_densify(const po::DevMaps *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info, double spacing,
                              int M, double *out, int *n_out, int *ok, hipStream_t st);
-hipError_t po_launch_map_sample(const po::DevMap *m, int n, const double *xy, double *dist, int *inside, hipStream_t st);
-hipError_t po_launch_bounds(const po::DevMap *m, const po::DevBounds *in, double *bounds, int *n_valid, hipStream_t st);
+hipError_t po_launch_map_sample(const po::DevMaps *m, int layer, int n, const double *xy, double *dist, int *inside, hipStream_t st);
+hipError_t po_launch_bounds(const po::DevMaps *m, const po::DevBounds *in, double *bounds, int *n_valid, hipStream_t st);
 hipError_t po_launch_resample(const po::DevSpline *in, const po::DevResample *r, hipStream_t st);
 hipError_t po_launch_limits(int B, int N, const int *n_points, const double *v, const double *a, double *max_k, double *max_kp, double mu, double rate, hipStream_t st);
-hipError_t po_launch_dp_search(const po::DevMap *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st);
+hipError_t po_launch_dp_search(const po::DevMaps *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st);
 size_t po_dp_lds_bytes(int K, int L);
 size_t po_spline_lds_bytes(int K);
 hipError_t po_launch_bspline(int B, int W, const int *n_way, const double *wx, const double *wy, int M, double *x, double *y, double *s, int *n_samples, hipStream_t st);

@@ -20,6 +20,18 @@ struct DevMap {
     int sx, sy;
     double res, px, py;
 };
+// The handle's map STACK (po_set_map_stack*): M layers of one geometry, layer k at d + k * stride, and which layer instance b of a batch reads.
+// A view: nothing here is owned.  M = 1 with pos == layer_of == nullptr is the single map of po_set_map.
+struct DevMaps {
+    const float *d;       // layer 0 (nullptr: no map installed)
+    int sx, sy;
+    double res, px, py;   // px, py: centre of every layer when pos == nullptr
+    int M;
+    size_t stride;        // elements per layer (sx * sy)
+    const double *pos;    // device [M][2]: centre of each layer, or nullptr
+    const int *layer_of;  // device [n_assign]: layer of instance b, or nullptr = every instance reads layer 0
+    int n_assign;
+};
 struct DevCar {  // CollisionChecker's CarGeometry, built on the host exactly like car_geometry.cpp:38-56
     double bx, br;            // bounding circle (local x, radius); local y = 0
     double cx[6], cy[6], cr[6];
@@ -86,6 +98,19 @@ struct PlanRows {
 };
 
 #ifdef PO_MAP_DEVICE_CODE  // kernels and device functions: po_kernels.hip only (po_capi.cpp needs just the structs)
+// Layer k of the stack as a DevMap.  k is clamped into [0, M - 1] HERE, where it is read: a table that arrived through a device pointer was never validated, and a
+// bad entry must select a wrong layer, never an address outside the stack.
+__device__ __forceinline__ DevMap map_layer(const DevMaps &s, int k) {
+    k = k < 0 ? 0 : (k >= s.M ? s.M - 1 : k);
+    DevMap m{s.d + (size_t)k * s.stride, s.sx, s.sy, s.res, s.px, s.py};
+    if (s.pos) { m.px = s.pos[2 * (size_t)k]; m.py = s.pos[2 * (size_t)k + 1]; }
+    return m;
+}
+// The map instance b reads.  Every caller runs one workgroup (or wave) per instance and passes the block's instance: b is wave-uniform, so the table entry, the
+// positions and the layer base are scalar loads and the DevMap stays in scalar registers, as the by-value kernel argument did.
+__device__ __forceinline__ DevMap map_of(const DevMaps &s, int b) {
+    return map_layer(s, (s.layer_of && b >= 0 && b < s.n_assign) ? s.layer_of[b] : 0);
+}
 // checkIfPositionWithinMap (GridMapMath.cpp): t = -(p - mapPos - 0.5*len); 0 <= t < len on both axes
 __device__ __forceinline__ bool map_inside(const DevMap &m, double x, double y) {
     const double lx = m.sx * m.res, ly = m.sy * m.res;

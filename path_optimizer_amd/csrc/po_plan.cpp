@@ -66,8 +66,9 @@ static bool plan_args_ok(po_handle h, const po_plan_in *in, const po_plan_out *o
 static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_out *out) {
     if (!plan_args_ok(h, in, out)) return PO_ERR_INVALID;
     if (!(in->max_length > 0)) return PO_ERR_INVALID;  // the device entry cannot look at the waypoints
-    if (!h->map.d) return PO_ERR_INVALID;
+    if (!h->maps.d) return PO_ERR_INVALID;
     const int B = in->B;
+    if (!assignment_covers(h, B)) return PO_ERR_INVALID;  // every instance needs its entry of the map assignment: refused before any stage is enqueued
     if (B == 0) return PO_OK;
     const po_params *prm = &h->params;
     hipStream_t st = h->stream;

@@ -12,9 +12,10 @@
 namespace po {
 
 // One block per path: first colliding state, then optimizePath's return value (path_optimizer.cpp:183-200).
-__global__ __launch_bounds__(128) void postcheck_kernel(DevMap m, DevCar c, int B, int N, const int *n_points, const double *states,
+__global__ __launch_bounds__(128) void postcheck_kernel(DevMaps ms, DevCar c, int B, int N, const int *n_points, const double *states,
                                                         const po_info *info, int *n_valid, int *ok) {
     const int b = blockIdx.x;
+    const DevMap m = map_of(ms, b);
     __shared__ int first;
     int n = n_points ? n_points[b] : N;
     n = n < 0 ? 0 : (n > N ? N : n);
@@ -34,9 +35,10 @@ __global__ __launch_bounds__(128) void postcheck_kernel(DevMap m, DevCar c, int 
     }
 }
 
-__global__ void map_sample_kernel(DevMap m, int n, const double *xy, double *dist, int *inside) {
+__global__ void map_sample_kernel(DevMaps ms, int layer, int n, const double *xy, double *dist, int *inside) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const DevMap m = map_layer(ms, layer);
     dist[i] = map_distance(m, xy[2 * i], xy[2 * i + 1]);
     inside[i] = map_inside(m, xy[2 * i], xy[2 * i + 1]) ? 1 : 0;
 }
@@ -148,8 +150,9 @@ __device__ void clearance_strict(const DevMap &m, double radius, double sx, doub
     }
 }
 // One block per path, one thread per (state, circle): updateBoundsImproved (:142-201)
-__global__ __launch_bounds__(256) void bounds_kernel(DevMap m, DevBounds in, double *bounds, int *n_valid) {
+__global__ __launch_bounds__(256) void bounds_kernel(DevMaps ms, DevBounds in, double *bounds, int *n_valid) {
     const int b = blockIdx.x;
+    const DevMap m = map_of(ms, b);
     __shared__ int first;
     int n = in.n_points ? in.n_points[b] : in.N;
     n = n < 0 ? 0 : (n > in.N ? in.N : n);
@@ -330,9 +333,10 @@ constexpr int kDpMaxLayers = 512, kDpMaxLat = 64;
 // NW waves per instance: every wave carries all lateral samples (lane = node of the current layer) and evaluates the edges from every NW-th node of the
 // previous layer; the partial minima meet in LDS (cost first, then the smaller previous index: the reference's first-minimum order).  NW = 8 for small
 // batches (B <= 512): a single planning instance otherwise spends 47 layers x 34 x 34 edges, each with an atan2, on one wave — 2.35 ms against 0.92 ms.
-template <int NW> __global__ __launch_bounds__(64 * NW) void dp_search_kernel(DevMap m, DevSpline in, DevSearch q) {
+template <int NW> __global__ __launch_bounds__(64 * NW) void dp_search_kernel(DevMaps ms, DevSpline in, DevSearch q) {
     extern __shared__ double lds[];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const DevMap m = map_of(ms, b);
     const size_t o = (size_t)b * q.L;
     if (in.n_knots && (in.n_knots[b] < 3 || in.n_knots[b] > in.K)) {  // no spline (an earlier stage of a pipeline failed): nothing to search
         for (int i = threadIdx.x; i < q.L; i += 64 * NW) { q.layer_s[o + i] = 0; q.lb[o + i] = 0; q.ub[o + i] = 0; }
@@ -723,10 +727,11 @@ __global__ __launch_bounds__(64) void segment_init_kernel(DevSpline in, const do
 
 // optimizePath's densifying output branch (path_optimizer.cpp:201-226): splines x(s), y(s) through the solved states (fitted by two lanes
 // in LDS), samples every `spacing` on all lanes, first colliding sample by atomicMin.
-__global__ __launch_bounds__(128) void densify_kernel(DevMap m, DevCar c, int B, int N, const int *n_points, const double *states, const po_info *info, double spacing,
+__global__ __launch_bounds__(128) void densify_kernel(DevMaps ms, DevCar c, int B, int N, const int *n_points, const double *states, const po_info *info, double spacing,
                                                       int M, double *out, int *n_out, int *ok) {
     extern __shared__ double lds[];  // knots s, x, y [N] + 2 x (a, b, c, 3 scratch) [N]
     const int b = blockIdx.x, tid = threadIdx.x;
+    const DevMap m = map_of(ms, b);
     __shared__ int first;
     int n = n_points ? n_points[b] : N;
     n = n < 0 ? 0 : (n > N ? N : n);
@@ -864,17 +869,17 @@ __global__ void plan_clear_kernel(int B, int N, const int *stage, double *states
 
 }  // namespace po
 
-extern "C" hipError_t po_launch_postcheck(const po::DevMap *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states,
+extern "C" hipError_t po_launch_postcheck(const po::DevMaps *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states,
                                           const po_info *info, int *n_valid, int *ok, hipStream_t st) {
     hipLaunchKernelGGL(po::postcheck_kernel, dim3(B), dim3(128), 0, st, *m, *c, B, N, n_points, states, info, n_valid, ok);
     return hipGetLastError();
 }
-extern "C" hipError_t po_launch_map_sample(const po::DevMap *m, int n, const double *xy, double *dist, int *inside, hipStream_t st) {
-    hipLaunchKernelGGL(po::map_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *m, n, xy, dist, inside);
+extern "C" hipError_t po_launch_map_sample(const po::DevMaps *m, int layer, int n, const double *xy, double *dist, int *inside, hipStream_t st) {
+    hipLaunchKernelGGL(po::map_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *m, layer, n, xy, dist, inside);
     return hipGetLastError();
 }
 
-extern "C" hipError_t po_launch_bounds(const po::DevMap *m, const po::DevBounds *in, double *bounds, int *n_valid, hipStream_t st) {
+extern "C" hipError_t po_launch_bounds(const po::DevMaps *m, const po::DevBounds *in, double *bounds, int *n_valid, hipStream_t st) {
     hipLaunchKernelGGL(po::spline_fit_kernel, dim3(in->B), dim3(64), 0, st, *in);
     hipLaunchKernelGGL(po::bounds_kernel, dim3(in->B), dim3(256), 0, st, *m, *in, bounds, n_valid);
     return hipGetLastError();
@@ -897,7 +902,7 @@ extern "C" hipError_t po_launch_limits(int B, int N, const int *n_points, const 
     hipLaunchKernelGGL(po::limits_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, B, N, n_points, v, a, max_k, max_kp, mu, rate);
     return hipGetLastError();
 }
-extern "C" hipError_t po_launch_dp_search(const po::DevMap *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st) {
+extern "C" hipError_t po_launch_dp_search(const po::DevMaps *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st) {
     const size_t lds1 = po_dp_lds_bytes(in->K, q->L), lds4 = lds1 + kDpEightWaveScratch;
     // few instances (a planner's own call: B = 1): eight waves per instance share the edge evaluations of a layer; a full batch keeps one wave per instance
     // (one_wave: the caller's A/B switch, po_debug_set "dp_one_wave")
@@ -948,7 +953,7 @@ extern "C" hipError_t po_launch_plan_clear(int B, int N, const int *stage, doubl
     return hipGetLastError();
 }
 
-extern "C" hipError_t po_launch_densify(const po::DevMap *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info,
+extern "C" hipError_t po_launch_densify(const po::DevMaps *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info,
                                         double spacing, int M, double *out, int *n_out, int *ok, hipStream_t st) {
     const size_t lds = sizeof(double) * 15 * (size_t)N;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&po::densify_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -154,6 +154,7 @@ template <int KIND> __device__ void assemble(const DevSmooth &a, Prob<KIND> &pb,
         // tension_smoother.cpp:238-261 (Hessian: [1 -2 1] and [-1 3 -3 1] stencils on x and on y), :263-314 (constraints)
         const double wc = a.w[3], wcr = a.w[4], wdev = a.w[5];
         const double v3[3] = {1, -2, 1}, v4[4] = {-1, 3, -3, 1};
+        const DevMap mp = map_of(a.maps, b);  // (b is the block's instance: scalar)
         for (int i = lane; i < P; i += nts) {
             for (int e = 0; e <= 3; ++e) {  // H[i][i+e], accumulated block by block like the reference's loop
                 double acc = 0;
@@ -174,7 +175,7 @@ template <int KIND> __device__ void assemble(const DevSmooth &a, Prob<KIND> &pb,
             if (i == 0) { lo = 0; hi = 0; }
             else if (i == P - 1) { lo = -0.5; hi = 0.5; }
             else {
-                double c = map_distance(a.map, xi, yi);  // Map::getObstacleDistance, tension_smoother.cpp:303
+                double c = map_distance(mp, xi, yi);  // Map::getObstacleDistance, tension_smoother.cpp:303
                 c = c < 2.0 ? c : 2.0;
                 lo = -c; hi = c;
             }

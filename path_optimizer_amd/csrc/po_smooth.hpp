@@ -19,7 +19,7 @@ struct DevSmooth {
     int max_iter, check_every, adapt_every, scaling;
     double *scratch;        // [B][scratch_stride]: scaled P band, D, E
     size_t scratch_stride;  // doubles
-    DevMap map;             // TENSION only
+    DevMaps maps;           // TENSION only: the map stack; instance b reads map_of(maps, b)
     int perm_bits;          // block -> instance mixing (po_device.hpp perm_index), 0 = blockIdx order
     long long *dbg_cycles;  // optional [B][8] per-phase shader-clock totals (dev tool: PO_SMOOTH_DEBUG=1), or nullptr
     int seq_band;           // dev (po_debug_set "smooth_seq"): narrow-band substitutions on one lane (the round-1 path) instead of partitioned over the wave

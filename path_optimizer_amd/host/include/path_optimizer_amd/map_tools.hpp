@@ -5,6 +5,9 @@
 //     getObstacleDistance(pos) / isInside(pos)  (src/tools/Map.cpp)       same names (device sampling, po_map_sample)
 //   ReferencePath::updateBounds(const Map&)                             updateBounds(ReferencePath&, knots, map): po_bounds_batch
 //     (-> ReferencePathImpl::updateBoundsImproved)                        fills the bounds and truncates the states like the reference
+//   — new —                                                            MapStack: M layers of one geometry on the engine, each with its own centre,
+//                                                                        and the instance -> layer table of the batched calls (po_set_map_stack*,
+//                                                                        po_set_map_assignment)
 //   CollisionChecker::isSingleStateCollisionFreeImproved(State)         same name; checkPaths(): the batched tail of optimizePath
 //     (src/tools/collision_checker.cpp)                                   (po_postcheck_batch)
 //
@@ -47,6 +50,45 @@ class Map {
         if (po_map_sample(engine_->handle(), 1, xy, d, in) != PO_OK) throw std::runtime_error("po_map_sample failed");
     }
     PoEngine *engine_;
+};
+
+// M obstacle-distance layers of one size and resolution on one engine: one local grid per vehicle, per perception hypothesis, per scene.  Layer k is centred at
+// pos_xy[2k], pos_xy[2k + 1].  Which layer instance b of a batched call reads is the engine's assignment (setAssignment); without one every instance reads layer 0.
+// Installing a MapStack replaces the engine's Map and the other way round (an engine holds one stack; a Map is a stack of one).
+class MapStack {
+ public:
+    // layers: [M][size_y][size_x] floats, every layer column-major like Map's
+    MapStack(const float *layers, int M, int size_x, int size_y, double resolution, const std::vector<double> &pos_xy, PoEngine *engine = nullptr)
+        : engine_(engine ? engine : &PoEngine::instance()), M_(M) {
+        if (pos_xy.size() != 2 * (size_t)(M > 0 ? M : 0)) throw std::invalid_argument("MapStack: pos_xy must hold M (x, y) pairs");
+        po_map m{layers, size_x, size_y, resolution, 0.0, 0.0};
+        const int rc = po_set_map_stack(engine_->handle(), M, &m, pos_xy.data());
+        if (rc != PO_OK) throw std::runtime_error(std::string("po_set_map_stack: ") + po_strerror(rc));
+    }
+    // occupancy: [M][size_y][size_x] bytes, 0 = occupied; the distance transform of all M images runs on the device (po_set_map_stack_occupancy)
+    MapStack(const unsigned char *occupancy, int M, int size_x, int size_y, double resolution, const std::vector<double> &pos_xy, PoEngine *engine = nullptr)
+        : engine_(engine ? engine : &PoEngine::instance()), M_(M) {
+        if (pos_xy.size() != 2 * (size_t)(M > 0 ? M : 0)) throw std::invalid_argument("MapStack: pos_xy must hold M (x, y) pairs");
+        po_occupancy o{occupancy, size_x, size_y, resolution, 0.0, 0.0};
+        const int rc = po_set_map_stack_occupancy(engine_->handle(), M, &o, pos_xy.data());
+        if (rc != PO_OK) throw std::runtime_error(std::string("po_set_map_stack_occupancy: ") + po_strerror(rc));
+    }
+    // layer_of[b] = the layer instance b reads; an index outside [0, M) throws and leaves the previous table in force.  Empty: every instance reads layer 0.
+    void setAssignment(const std::vector<int> &layer_of) const {
+        const int rc = po_set_map_assignment(engine_->handle(), (int)layer_of.size(), layer_of.empty() ? nullptr : layer_of.data());
+        if (rc != PO_OK) throw std::invalid_argument(std::string("po_set_map_assignment: ") + po_strerror(rc));
+    }
+    double getObstacleDistance(int layer, double x, double y) const { double d; int in; sample(layer, x, y, &d, &in); return d; }
+    bool isInside(int layer, double x, double y) const { double d; int in; sample(layer, x, y, &d, &in); return in != 0; }
+    int layers() const { return M_; }
+    PoEngine *engine() const { return engine_; }
+ private:
+    void sample(int layer, double x, double y, double *d, int *in) const {
+        const double xy[2] = {x, y};
+        if (po_map_sample_layer(engine_->handle(), layer, 1, xy, d, in) != PO_OK) throw std::runtime_error("po_map_sample_layer failed");
+    }
+    PoEngine *engine_;
+    int M_;
 };
 
 // The knots x_s_ / y_s_ were set from (tk::spline::set_points; ReferencePath::setSpline in the reference).

@@ -7,7 +7,8 @@
 //              std::vector<State> *final_path)        (src/path_optimizer/path_optimizer.cpp:40-85)
 //   bool solveWithoutSmoothing(reference_points, final_path)  (:87-117)              same signature (+ the knots of the spline a previous solve() left
 //                                                                                      behind, which the reference reads through reference_path_)
-//   — new —                                                                          static solveBatch(): many planning instances in one call
+//   — new —                                                                          static solveBatch(): many planning instances in one call; with a
+//                                                                                      MapStack and one layer index per problem, each on its own map
 #pragma once
 #include <cmath>
 #include <stdexcept>
@@ -77,6 +78,20 @@ class PathOptimizer {
     // Many planning instances in one call (one PathOptimizer::solve each).  stage (optional): see po_plan_out in po_hip.h.
     static std::vector<bool> solveBatch(const PlanningProblem *problems, size_t B, const Map &map, std::vector<std::vector<State>> *final_paths,
                                         std::vector<int> *stage = nullptr, int max_states = 0) {
+        return planBatch(problems, B, map.engine(), final_paths, stage, max_states);
+    }
+    // ... each on its own map: problem b drives through layer layer_of[b] of `maps` (installed as the engine's assignment: it stays in force afterwards)
+    static std::vector<bool> solveBatch(const PlanningProblem *problems, size_t B, const MapStack &maps, const std::vector<int> &layer_of,
+                                        std::vector<std::vector<State>> *final_paths, std::vector<int> *stage = nullptr, int max_states = 0) {
+        if (layer_of.size() != B) throw std::invalid_argument("solveBatch: one layer index per problem");
+        maps.setAssignment(layer_of);
+        return planBatch(problems, B, maps.engine(), final_paths, stage, max_states);
+    }
+    int lastStage() const { return last_stage_; }
+
+ private:
+    static std::vector<bool> planBatch(const PlanningProblem *problems, size_t B, PoEngine *engine, std::vector<std::vector<State>> *final_paths,
+                                       std::vector<int> *stage, int max_states) {
         std::vector<bool> ok(B, false);
         final_paths->assign(B, {});
         if (B == 0) return ok;
@@ -102,7 +117,7 @@ class PathOptimizer {
         }
         po_plan_in in{(int)B, (int)W, nw.data(), wx.data(), wy.data(), st.data(), gl.data(), longest, N};
         po_plan_out out{states.data(), n.data(), okv.data(), stg.data(), nullptr};
-        const int rc = po_plan_batch(map.engine()->handle(), &in, &out);
+        const int rc = po_plan_batch(engine->handle(), &in, &out);
         if (rc != PO_OK) throw std::runtime_error(std::string("po_plan_batch: ") + po_strerror(rc) + " " + po_last_hip_error());
         for (size_t b = 0; b < B; ++b) {
             ok[b] = okv[b] != 0;
@@ -114,9 +129,6 @@ class PathOptimizer {
         if (stage) *stage = stg;
         return ok;
     }
-    int lastStage() const { return last_stage_; }
-
- private:
     State start_, end_;
     const Map &map_;
     int last_stage_ = 0;
