@@ -268,7 +268,8 @@ int po_device_count(void);
  * entry takes the handle's inner lock while it enqueues, owns no staging, and its scratch is ordered by the stream.  The library orders the calls; every call returns
  * what it would return in SOME serial order of the calls, i.e. what the same call returns on a handle nobody else uses (results do not depend on what a handle ran
  * before: tests/test_handle_contract.py).  Two calls on one handle never overlap on the device — use two handles for that.
- * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_set_map_occupancy* / po_set_map_stack* / po_set_map_assignment* / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
+ * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_set_map_occupancy* / po_set_map_stack* (po_set_map_stack_obstacles* included) /
+ * po_set_map_assignment* / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
  * start afterwards use the new stream / map / switch, and the caller orders what is already enqueued on the old stream.  po_last_kernel_ms / po_last_phase_ms
  * describe the handle's last solve, whichever thread made it.  po_destroy must not race with any call. */
 int po_create(int device, const po_params *params, po_handle *out);
@@ -355,6 +356,52 @@ int po_set_map_assignment(po_handle h, int n, const int *layer_of);          /* 
 int po_set_map_assignment_device(po_handle h, int n, const int *layer_of);   /* device pointer, copied on the stream */
 int po_get_map_layer(po_handle h, int k, po_map *geometry_out, float *distance_or_null);
 int po_map_sample_layer(po_handle h, int k, int n, const double *xy, double *dist, int *inside);
+/* ---- the stack from per-layer OBSTACLE LISTS, rasterised on the device (csrc/po_raster.hip) ----
+ * A planner does not hold M images: it holds one static grid and, per hypothesis or vehicle, a short list of detected objects.  The entries below turn M such
+ * lists into the M occupancy images po_distance_map_batch reads ([M][size_y][size_x], 0 = occupied, 255 = free) — and, for the stack entries, on into the M distance
+ * layers — without the images ever existing on the host: a layer costs 136 bytes per obstacle over PCIe instead of one byte per cell.
+ * Definition (the bar is BIT equality, as for the distance transform).  The centre of cell (i, j) of layer k is grid_map's getPositionFromIndex,
+ *     px = (pos_x[k] + (0.5 * (size_x * resolution) - 0.5 * resolution)) + resolution * (-i),    py likewise with size_y, pos_y[k] and j,
+ * evaluated in IEEE double, one rounding per operation, nothing contracted.  A cell is occupied when its base cell is 0 (if a base is given) or when its centre is
+ * covered by any obstacle of the layer:
+ *   DISC   dx = px - v[0], dy = py - v[1]:  dx * dx + dy * dy <= v[2] * v[2]   (the boundary is inclusive);
+ *   POLY   the centre lies in the closed bounding box of the vertices (exact min / max) AND the cross products (bx - ax) * (py - ay) - (by - ay) * (px - ax) of
+ *          all edges (a -> b, the last edge closing back to vertex 0) are all >= 0 or all <= 0.  Convex polygons of either orientation; the bounding-box clause
+ *          keeps a degenerate (collinear) polygon a segment.  A NON-convex polygon gets what this predicate says (its convex kernel, roughly): not supported.
+ * A comparison with a NaN is false; an obstacle with an unknown kind, a POLY with n_verts < 3, or a NaN among the values its kind reads (DISC: v[0 .. 2]; POLY:
+ * the first 2 n_verts) covers nothing.  A layer without any occupied cell then falls under the distance transform's no-obstacle rule, unchanged.
+ * Host entries validate everything before they touch the handle — PO_ERR_INVALID, handle unchanged, for: first[0] != 0, first[] not non-decreasing, first[M] > n_obs;
+ * an unknown kind; n_verts outside 3 .. PO_OBS_MAX_VERTS for a POLY; a negative or non-finite radius; a non-finite coordinate; base_count not in {0, 1, M};
+ * base == NULL with base_count != 0.  n_obs = 0 and empty layers are valid.  Device entries cannot look at the lists: they read n_verts clamped into [0, 8] and first[]
+ * clamped into [0, n_obs], so a bad list rasterises wrongly but never reads outside obs.  Limits: those of po_distance_map_batch, beyond: PO_ERR_UNSUPPORTED.
+ * pos_xy is [M][2] or NULL (every layer at lists->pos_x / pos_y), exactly as in po_set_map_stack_occupancy*.
+ * po_set_map_stack_obstacles* = the rasteriser into an image block the handle owns, then the very sequence of po_set_map_stack_occupancy_device.  The device entry keeps
+ * that entry's contract word for word: with the M and size the handle already holds it allocates nothing and does not synchronise, and "map_ptr" stays where it is;
+ * when a block has to grow it synchronises the stream first.  The assignment's lifetime rules apply unchanged.  The host entry uploads obs, first, pos_xy and the
+ * base only.  Every pointer given to a device entry (those inside the struct too) is a device pointer and must stay valid until the stream has passed the call. */
+#define PO_OBS_DISC 0
+#define PO_OBS_POLY 1
+#define PO_OBS_MAX_VERTS 8
+typedef struct po_obstacle {
+    int    kind;      /* PO_OBS_DISC / PO_OBS_POLY */
+    int    n_verts;   /* POLY: 3 .. PO_OBS_MAX_VERTS; DISC: ignored */
+    double v[16];     /* DISC: v[0], v[1] = centre (world frame), v[2] = radius >= 0.
+                         POLY: (x, y) of vertex 0 .. n_verts-1, world frame, convex, either orientation */
+} po_obstacle;        /* 136 bytes */
+typedef struct po_obstacle_lists {
+    const po_obstacle   *obs;     /* [n_obs] */
+    const int           *first;   /* [M + 1], first[0] = 0, non-decreasing, first[M] <= n_obs:
+                                     layer k owns obs[first[k] .. first[k+1]) */
+    int                  n_obs;
+    const unsigned char *base;    /* NULL = every cell free; else base_count images [size_y][size_x], 0 = occupied (po_occupancy's convention) */
+    int                  base_count;  /* 0, 1 (one image shared by every layer, cell (i,j) -> cell (i,j)) or M */
+    int    size_x, size_y;
+    double resolution, pos_x, pos_y;  /* as po_occupancy */
+} po_obstacle_lists;
+int po_rasterize_batch(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy, unsigned char *cells_out);         /* host pointers, synchronous */
+int po_rasterize_batch_device(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy, unsigned char *cells_out);  /* device pointers, on the stream */
+int po_set_map_stack_obstacles(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy);                           /* host pointers, synchronous */
+int po_set_map_stack_obstacles_device(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy);                    /* device pointers, on the stream */
 /* For every path: walk the optimised states in order and stop at the first state that fails
  * CollisionChecker::isSingleStateCollisionFreeImproved (src/tools/collision_checker.cpp:42-59: bounding circle, then the
  * six footprint circles of src/tools/car_geometry.cpp:38-72; outside the map = collision).
@@ -548,7 +595,8 @@ const char *po_last_hip_error(void);
  * 6: round 6, po_info.status_refine / status_polish may be PO_NOT_AVAILABLE; po_create refuses refine_rounds + refine_extra_rounds >= 32; 7: po_occupancy,
  * po_distance_map_batch*, po_set_map_occupancy*, po_get_map, po_debug_get "map_ptr").  The map-stack entries
  * (po_set_map_stack*, po_set_map_assignment*, po_get_map_layer, po_map_sample_layer, po_debug_get "map_layers") were ADDED under 7: no struct layout, no existing
- * entry and no field's meaning changed, so a binding written against 7 drives this library unchanged; one that needs the new entries looks the symbols up.  A binding should compare
+ * entry and no field's meaning changed, so a binding written against 7 drives this library unchanged; one that needs the new entries looks the symbols up.  The
+ * obstacle-list entries (po_obstacle, po_obstacle_lists, po_rasterize_batch*, po_set_map_stack_obstacles*) were added under 7 by the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7
 const char *po_version(void);

@@ -45,6 +45,18 @@ class PoOccupancy(C.Structure):
                 ("pos_x", C.c_double), ("pos_y", C.c_double)]
 
 
+PO_OBS_DISC, PO_OBS_POLY, PO_OBS_MAX_VERTS = 0, 1, 8
+
+
+class PoObstacle(C.Structure):  # 136 bytes; binding.OBSTACLE_DTYPE is the same layout as a numpy record
+    _fields_ = [("kind", C.c_int), ("n_verts", C.c_int), ("v", C.c_double * 16)]
+
+
+class PoObstacleLists(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("first", C.c_void_p), ("n_obs", C.c_int), ("base", C.c_void_p), ("base_count", C.c_int),
+                ("size_x", C.c_int), ("size_y", C.c_int), ("resolution", C.c_double), ("pos_x", C.c_double), ("pos_y", C.c_double)]
+
+
 class PoInfo(C.Structure):
     _fields_ = [("status", C.c_int), ("iters", C.c_int), ("n_refactor", C.c_int), ("status_polish", C.c_int),
                 ("r_prim", C.c_double), ("r_dual", C.c_double), ("rho", C.c_double), ("obj", C.c_double),

@@ -27,7 +27,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_segment_init_batch_device", "po_plan_batch", "po_plan_batch_device", "po_densify_batch", "po_densify_batch_device",
            "po_distance_map_batch", "po_distance_map_batch_device", "po_set_map_occupancy", "po_set_map_occupancy_device", "po_get_map",
            "po_set_map_stack", "po_set_map_stack_occupancy", "po_set_map_stack_occupancy_device", "po_set_map_assignment", "po_set_map_assignment_device",
-           "po_get_map_layer", "po_map_sample_layer"]
+           "po_get_map_layer", "po_map_sample_layer",
+           "po_rasterize_batch", "po_rasterize_batch_device", "po_set_map_stack_obstacles", "po_set_map_stack_obstacles_device"]
 
 
 class PoError(RuntimeError):
@@ -79,6 +80,10 @@ def lib():
         L.po_set_map_assignment_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.po_get_map_layer.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.po_map_sample_layer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_rasterize_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_rasterize_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_set_map_stack_obstacles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_set_map_stack_obstacles_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -120,6 +125,58 @@ def keep_control_steps(form: int, ref_s) -> int:
 
 def _np(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ---- obstacle lists (po_obstacle) ----
+OBSTACLE_DTYPE = np.dtype([("kind", np.int32), ("n_verts", np.int32), ("v", np.float64, (16,))])  # po_obstacle, 136 bytes
+
+
+def obstacle_disc(x, y, r):
+    """A disc of radius r >= 0 centred at (x, y), world frame: one record of OBSTACLE_DTYPE."""
+    from .abi import PO_OBS_DISC
+
+    o = np.zeros((), dtype=OBSTACLE_DTYPE)
+    o["kind"] = PO_OBS_DISC
+    o["v"][:3] = (x, y, r)
+    return o
+
+
+def obstacle_polygon(xy):
+    """A convex polygon with 3 .. 8 vertices xy [n, 2] (world frame, either orientation)."""
+    from .abi import PO_OBS_MAX_VERTS, PO_OBS_POLY
+
+    xy = np.asarray(xy, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2 or not 3 <= len(xy) <= PO_OBS_MAX_VERTS:
+        raise ValueError("a polygon has 3 .. 8 vertices (x, y)")
+    o = np.zeros((), dtype=OBSTACLE_DTYPE)
+    o["kind"] = PO_OBS_POLY
+    o["n_verts"] = len(xy)
+    o["v"][:2 * len(xy)] = xy.reshape(-1)
+    return o
+
+
+def obstacle_box(cx, cy, half_length, half_width, yaw):
+    """An oriented box as a 4-vertex polygon.  The corners are computed HERE, on the host: the device sees polygons only, so no trigonometry enters the
+    bit-exact path (two hosts whose cos / sin differ in the last bit hand over different polygons, each rasterised exactly)."""
+    c, s = np.cos(yaw), np.sin(yaw)
+    corners = [(cx + sl * half_length * c - sw * half_width * s, cy + sl * half_length * s + sw * half_width * c) for sl, sw in ((1, 1), (-1, 1), (-1, -1), (1, -1))]
+    return obstacle_polygon(corners)
+
+
+def pack_obstacles(layers):
+    """M lists of obstacle records -> (obs [n_obs] of OBSTACLE_DTYPE, first [M + 1] int32): layer k owns obs[first[k]:first[k + 1]].  A tuple (obs, first) that is
+    packed already passes through (converted, not checked: the library checks)."""
+    if isinstance(layers, tuple) and len(layers) == 2:
+        return np.ascontiguousarray(layers[0], dtype=OBSTACLE_DTYPE).reshape(-1), np.ascontiguousarray(layers[1], dtype=np.int32).reshape(-1)
+    first = np.zeros(len(layers) + 1, dtype=np.int32)
+    first[1:] = np.cumsum([len(l) for l in layers])
+    obs = np.zeros(int(first[-1]), dtype=OBSTACLE_DTYPE)
+    n = 0
+    for l in layers:
+        for o in l:
+            obs[n] = o
+            n += 1
+    return obs, first
 
 
 def _i32(a):
@@ -331,6 +388,80 @@ class Engine:
             raise ValueError("pos_xy must be a contiguous torch.float64 tensor [M, 2]")
         oc = PoOccupancy(C.c_void_p(occ.data_ptr()), sx, sy, float(resolution), float(pos_x), float(pos_y))
         _check(lib().po_set_map_stack_occupancy_device(self._h, M, C.byref(oc), None if pos_xy is None else C.c_void_p(pos_xy.data_ptr())))
+
+    # ---- the stack from per-layer obstacle lists, rasterised on the device (po_raster.hip) ----
+    def _host_lists(self, layers, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base):
+        """(M, PoObstacleLists, pos array, the arrays the struct points into): host pointers."""
+        from .abi import PoObstacleLists
+
+        obs, first = pack_obstacles(layers)
+        M = len(first) - 1
+        b, nb = None, 0
+        if base is not None:
+            b = self._occ_u8(base)
+            if b.shape == (size_x, size_y):
+                b = b[None]
+            if b.ndim != 3 or b.shape[1:] != (size_x, size_y):
+                raise ValueError("base must be [size_x, size_y] or [M, size_x, size_y]")
+            nb = b.shape[0]
+            b = np.ascontiguousarray(b.transpose(0, 2, 1))  # [n][size_y][size_x], x contiguous
+        pos = self._pos_xy(pos_xy, M)
+        ls = PoObstacleLists(_np(obs) if len(obs) else None, _np(first), len(obs), _np(b), nb, int(size_x), int(size_y), float(resolution), float(pos_x), float(pos_y))
+        return M, ls, pos, (obs, first, b)
+
+    def rasterize_batch(self, layers, size_x, size_y, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0, base=None):
+        """M obstacle lists -> M occupancy images, uint8 [M, size_x, size_y] (0 = occupied, 255 = free), on the device; the handle's map is not touched.
+        layers: M lists of obstacle_disc / obstacle_box / obstacle_polygon records (or a packed (obs, first) tuple, see pack_obstacles); base: None, one image
+        [size_x, size_y] shared by every layer, or [M, size_x, size_y] (0 = occupied); pos_xy [M, 2]: the centre of each layer, None: every layer at (pos_x, pos_y)."""
+        M, ls, pos, keep = self._host_lists(layers, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base)
+        out = np.empty((M, size_y, size_x), dtype=np.uint8)
+        _check(lib().po_rasterize_batch(self._h, M, C.byref(ls), _np(pos), _np(out)))
+        return out.transpose(0, 2, 1)
+
+    def set_map_stack_obstacles(self, layers, size_x, size_y, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0, base=None):
+        """Build the stack from M obstacle lists: rasterised and transformed on the device; only the lists (136 bytes per obstacle), the centres and the base are
+        uploaded.  Layers bit-identical to set_map_stack_occupancy(rasterize_batch(...)).  Arguments as rasterize_batch."""
+        M, ls, pos, keep = self._host_lists(layers, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base)
+        _check(lib().po_set_map_stack_obstacles(self._h, M, C.byref(ls), _np(pos)))
+
+    @staticmethod
+    def _device_lists(obs, first, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base):
+        from .abi import PoObstacleLists
+
+        if str(obs.dtype) != "torch.uint8" or obs.dim() != 2 or obs.shape[1] != OBSTACLE_DTYPE.itemsize or not obs.is_contiguous():
+            raise ValueError("obs must be a contiguous torch.uint8 tensor [n_obs, 136]: the bytes of an OBSTACLE_DTYPE array")
+        if first.dim() != 1 or str(first.dtype) != "torch.int32" or not first.is_contiguous() or first.shape[0] < 2:
+            raise ValueError("first must be a contiguous torch.int32 tensor [M + 1]")
+        M = int(first.shape[0]) - 1
+        nb = 0
+        if base is not None:
+            if str(base.dtype) != "torch.uint8" or base.dim() != 3 or tuple(base.shape[1:]) != (size_y, size_x) or not base.is_contiguous():
+                raise ValueError("base must be a contiguous torch.uint8 tensor [1 or M, size_y, size_x]")
+            nb = int(base.shape[0])
+        if pos_xy is not None and (tuple(pos_xy.shape) != (M, 2) or str(pos_xy.dtype) != "torch.float64" or not pos_xy.is_contiguous()):
+            raise ValueError("pos_xy must be a contiguous torch.float64 tensor [M, 2]")
+        n_obs = int(obs.shape[0])
+        ls = PoObstacleLists(C.c_void_p(obs.data_ptr()) if n_obs else None, C.c_void_p(first.data_ptr()), n_obs, None if base is None else C.c_void_p(base.data_ptr()), nb,
+                             int(size_x), int(size_y), float(resolution), float(pos_x), float(pos_y))
+        return M, ls, None if pos_xy is None else C.c_void_p(pos_xy.data_ptr())
+
+    def rasterize_batch_device(self, obs, first, out, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0, base=None):
+        """Device-pointer entry, enqueued on the handle's stream.  obs: torch uint8 [n_obs, 136] (torch.from_numpy(obs_array.view(np.uint8).reshape(-1, 136)));
+        first: torch int32 [M + 1]; out: contiguous torch uint8 [M, size_y, size_x]; base: torch uint8 [1 or M, size_y, size_x] or None; pos_xy: torch float64
+        [M, 2] or None.  The lists are NOT validated (n_verts and first[] are read clamped).  Every tensor must stay alive until the stream has passed the call."""
+        if str(out.dtype) != "torch.uint8" or out.dim() != 3 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous torch.uint8 tensor [M, size_y, size_x]")
+        sy, sx = int(out.shape[1]), int(out.shape[2])
+        M, ls, pos = self._device_lists(obs, first, sx, sy, resolution, pos_xy, pos_x, pos_y, base)
+        if int(out.shape[0]) != M:
+            raise ValueError("out must hold M = len(first) - 1 images")
+        _check(lib().po_rasterize_batch_device(self._h, M, C.byref(ls), pos, C.c_void_p(out.data_ptr())))
+
+    def set_map_stack_obstacles_device(self, obs, first, size_x, size_y, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0, base=None):
+        """Device-pointer entry, enqueued on the handle's stream (no synchronisation and no allocation when M and the size are those the handle holds).
+        Tensors as rasterize_batch_device."""
+        M, ls, pos = self._device_lists(obs, first, int(size_x), int(size_y), resolution, pos_xy, pos_x, pos_y, base)
+        _check(lib().po_set_map_stack_obstacles_device(self._h, M, C.byref(ls), pos))
 
     def set_map_assignment(self, layer_of):
         """layer_of[b] = the layer instance b of every map-reading batch call reads (validated: outside [0, M) raises and the previous table stays); None or

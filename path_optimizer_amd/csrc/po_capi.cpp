@@ -787,22 +787,27 @@ int po_distance_map_batch(po_handle h, int M, const po_occupancy *occ, float *di
     return S.copy_out(h);
 }
 
-int po_set_map_stack_occupancy_device(po_handle h, int M, const po_occupancy *occ, const double *pos_xy) {
-    if (int rc = check_occupancy(h, M, occ)) return rc;
-    std::lock_guard<std::mutex> g(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
+// M images on the device -> the handle's stack (h->mu held, device set): grow what has to grow, transform, publish
+static int stack_from_images(po_handle h, int M, const unsigned char *cells, int sx, int sy, double res, double px, double py, const double *pos_xy) {
     // same M and size as before: every block is large enough already — nothing is allocated, nothing waits; the transform overwrites the layers in stream order
-    const size_t stack_bytes = sizeof(float) * (size_t)M * (size_t)occ->size_x * (size_t)occ->size_y;
+    const size_t stack_bytes = sizeof(float) * (size_t)M * (size_t)sx * (size_t)sy;
     if (stack_bytes > h->map_buf.cap) h->maps.d = nullptr;  // the old layers are about to be released: no map until the new ones are in place
     if (int rc = grow_after_sync(h, h->map_buf, stack_bytes)) return rc;
-    if (int rc = grow_after_sync(h, h->edt_buf, po_edt_scratch_bytes(M, occ->size_x, occ->size_y))) return rc;
+    if (int rc = grow_after_sync(h, h->edt_buf, po_edt_scratch_bytes(M, sx, sy))) return rc;
     if (pos_xy) {
         if (int rc = grow_after_sync(h, h->map_pos_buf, sizeof(double) * 2 * (size_t)M)) return rc;
         HIP_TRY(hipMemcpyAsync(h->map_pos_buf.p, pos_xy, sizeof(double) * 2 * (size_t)M, hipMemcpyDeviceToDevice, h->stream));
     }
-    HIP_TRY(po_launch_edt(occ->cells, M, occ->size_x, occ->size_y, (float)occ->resolution, h->edt_buf.p, static_cast<float *>(h->map_buf.p), h->stream));
-    publish_stack(h, M, occ->size_x, occ->size_y, occ->resolution, occ->pos_x, occ->pos_y, pos_xy != nullptr);
+    HIP_TRY(po_launch_edt(cells, M, sx, sy, (float)res, h->edt_buf.p, static_cast<float *>(h->map_buf.p), h->stream));
+    publish_stack(h, M, sx, sy, res, px, py, pos_xy != nullptr);
     return PO_OK;
+}
+
+int po_set_map_stack_occupancy_device(po_handle h, int M, const po_occupancy *occ, const double *pos_xy) {
+    if (int rc = check_occupancy(h, M, occ)) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    return stack_from_images(h, M, occ->cells, occ->size_x, occ->size_y, occ->resolution, occ->pos_x, occ->pos_y, pos_xy);
 }
 
 int po_set_map_occupancy_device(po_handle h, const po_occupancy *occ) { return po_set_map_stack_occupancy_device(h, 1, occ, nullptr); }
@@ -826,6 +831,114 @@ int po_set_map_stack_occupancy(po_handle h, int M, const po_occupancy *occ, cons
 }
 
 int po_set_map_occupancy(po_handle h, const po_occupancy *occ) { return po_set_map_stack_occupancy(h, 1, occ, nullptr); }
+
+// ---- obstacle lists -> occupancy images -> the stack (po_raster.hip) --------------------------------
+// What every entry can check without reading through a pointer of the struct (testable without a GPU)
+static int check_lists(po_handle h, int M, const po_obstacle_lists *L) {
+    if (!h || M < 1 || !L || !L->first || L->n_obs < 0 || (L->n_obs > 0 && !L->obs) || L->size_x < 1 || L->size_y < 1 || !(L->resolution > 0) ||
+        !std::isfinite(L->resolution))
+        return PO_ERR_INVALID;
+    if (L->base_count != 0 && L->base_count != 1 && L->base_count != M) return PO_ERR_INVALID;
+    if (L->base_count != 0 && !L->base) return PO_ERR_INVALID;
+    if (L->size_x > po_edt_max_side() || L->size_y > po_edt_max_side() || M > po_edt_max_images()) return PO_ERR_UNSUPPORTED;
+    return PO_OK;
+}
+// The host entries read the lists themselves: everything the device entries can only clamp is refused here, before the handle is touched
+static int check_list_contents(int M, const po_obstacle_lists *L) {
+    if (L->first[0] != 0) return PO_ERR_INVALID;
+    for (int k = 0; k < M; ++k)
+        if (L->first[k + 1] < L->first[k]) return PO_ERR_INVALID;
+    if (L->first[M] > L->n_obs) return PO_ERR_INVALID;
+    for (int i = 0; i < L->n_obs; ++i) {
+        const po_obstacle &o = L->obs[i];
+        if (o.kind == PO_OBS_DISC) {
+            if (!std::isfinite(o.v[0]) || !std::isfinite(o.v[1]) || !std::isfinite(o.v[2]) || o.v[2] < 0) return PO_ERR_INVALID;
+        } else if (o.kind == PO_OBS_POLY) {
+            if (o.n_verts < 3 || o.n_verts > PO_OBS_MAX_VERTS) return PO_ERR_INVALID;
+            for (int e = 0; e < 2 * o.n_verts; ++e)
+                if (!std::isfinite(o.v[e])) return PO_ERR_INVALID;
+        } else {
+            return PO_ERR_INVALID;
+        }
+    }
+    return PO_OK;
+}
+// The device copy of a host struct: the staged arrays in place of the caller's
+struct StagedLists {
+    Slot<po_obstacle> obs;
+    Slot<int> first;
+    Slot<unsigned char> base;
+    Slot<double> pos;
+    void declare(Stage &S, int M, const po_obstacle_lists *L, const double *pos_xy) {
+        obs = S.in(L->n_obs > 0 ? L->obs : nullptr, (size_t)L->n_obs);
+        first = S.in(L->first, (size_t)M + 1);
+        base = S.in(L->base_count > 0 ? L->base : nullptr, (size_t)L->base_count * (size_t)L->size_x * (size_t)L->size_y);
+        pos = S.in(pos_xy, 2 * (size_t)M);
+    }
+    po_obstacle_lists device(const po_obstacle_lists *L) const {
+        po_obstacle_lists d = *L;
+        d.obs = obs; d.first = first; d.base = base;
+        return d;
+    }
+};
+
+int po_rasterize_batch_device(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy, unsigned char *cells_out) {
+    if (int rc = check_lists(h, M, lists)) return rc;
+    if (!cells_out) return PO_ERR_INVALID;
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(po_launch_raster(lists, M, pos_xy, cells_out, h->stream));
+    return PO_OK;
+}
+
+int po_rasterize_batch(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy, unsigned char *cells_out) {
+    if (int rc = check_lists(h, M, lists)) return rc;
+    if (!cells_out) return PO_ERR_INVALID;
+    if (int rc = check_list_contents(M, lists)) return rc;
+    Stage S;
+    StagedLists d;
+    d.declare(S, M, lists, pos_xy);
+    const Slot<unsigned char> d_cells = S.out(cells_out, (size_t)M * (size_t)lists->size_x * (size_t)lists->size_y);
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        HIP_TRY(hipSetDevice(h->device));
+        PO_TRY(S.upload(h, h->edt_io, true));
+    }
+    const po_obstacle_lists dev = d.device(lists);
+    PO_TRY(po_rasterize_batch_device(h, M, &dev, d.pos, d_cells));
+    std::lock_guard<std::mutex> g(h->mu);
+    return S.copy_out(h);
+}
+
+int po_set_map_stack_obstacles_device(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy) {
+    if (int rc = check_lists(h, M, lists)) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    // the images live in a grow-only block of the handle: with the M and size it already holds nothing is allocated and nothing waits
+    if (int rc = grow_after_sync(h, h->raster_buf, (size_t)M * (size_t)lists->size_x * (size_t)lists->size_y)) return rc;
+    unsigned char *cells = static_cast<unsigned char *>(h->raster_buf.p);
+    HIP_TRY(po_launch_raster(lists, M, pos_xy, cells, h->stream));
+    return stack_from_images(h, M, cells, lists->size_x, lists->size_y, lists->resolution, lists->pos_x, lists->pos_y, pos_xy);
+}
+
+int po_set_map_stack_obstacles(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy) {
+    if (int rc = check_lists(h, M, lists)) return rc;
+    if (int rc = check_list_contents(M, lists)) return rc;
+    Stage S;  // obs, first, pos_xy and the base: the images never exist on the host
+    StagedLists d;
+    d.declare(S, M, lists, pos_xy);
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and the final synchronisation are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        HIP_TRY(hipSetDevice(h->device));
+        PO_TRY(S.upload(h, h->edt_io, true));
+    }
+    const po_obstacle_lists dev = d.device(lists);
+    PO_TRY(po_set_map_stack_obstacles_device(h, M, &dev, d.pos));
+    std::lock_guard<std::mutex> g(h->mu);
+    return S.copy_out(h);  // (no output: the synchronise alone) the caller's lists may be reused, the stack is in place
+}
 
 int po_get_map_layer(po_handle h, int k, po_map *geometry_out, float *distance_or_null) {
     if (!h || !geometry_out) return PO_ERR_INVALID;

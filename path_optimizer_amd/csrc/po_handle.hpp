@@ -102,6 +102,7 @@ struct po_handle_s {
     int env_smooth_waves = 0;
     DevBuf in_buf, out_buf, asm_buf, scale_buf, dbg_buf, map_buf, post_buf, coef_buf, bnd_buf, smooth_buf, smooth_io, plan_io, plan_arena, plan_host;
     DevBuf edt_buf, edt_io;  // occupancy -> distance transform: the 16-bit intermediate (2 bytes per cell); staging of the host-pointer entries (image + layers)
+    DevBuf raster_buf;  // obstacle lists -> map stack: the M occupancy images between the rasteriser and the transform (1 byte per cell)
     // The map stack: M layers in map_buf, their centres in map_pos_buf when they differ, the instance -> layer table in map_assign_buf.
     // maps is the view the kernels get; maps.d == nullptr until a map is set (maps.M survives a failed re-install: "same M keeps the assignment" is judged against it).
     DevBuf map_pos_buf, map_assign_buf;

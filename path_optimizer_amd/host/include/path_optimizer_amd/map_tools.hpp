@@ -8,6 +8,9 @@
 //   — new —                                                            MapStack: M layers of one geometry on the engine, each with its own centre,
 //                                                                        and the instance -> layer table of the batched calls (po_set_map_stack*,
 //                                                                        po_set_map_assignment)
+//   — new —                                                            Obstacle::disc / box / polygon and MapStack::fromObstacles: the stack from per-layer
+//                                                                        obstacle lists over an optional static grid, rasterised on the device
+//                                                                        (po_set_map_stack_obstacles)
 //   CollisionChecker::isSingleStateCollisionFreeImproved(State)         same name; checkPaths(): the batched tail of optimizePath
 //     (src/tools/collision_checker.cpp)                                   (po_postcheck_batch)
 //
@@ -15,8 +18,10 @@
 // (gm["distance"].data(), gm.getSize(), gm.getResolution(), gm.getPosition()) — or, second constructor, the OCCUPANCY buffer the reference's callers already
 // compute as `binary` (gm["obstacle"] cast to unsigned char, 0 = occupied): the distance transform then runs on the device — see INTEGRATION.md §C.
 #pragma once
+#include <cmath>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "po_hip.h"
@@ -52,6 +57,34 @@ class Map {
     PoEngine *engine_;
 };
 
+// One detected object of a layer's obstacle list (po_obstacle): a disc or a convex polygon with 3 .. 8 vertices, world frame.
+struct Obstacle {
+    po_obstacle o;
+    static Obstacle disc(double x, double y, double radius) {
+        Obstacle r{};
+        r.o.kind = PO_OBS_DISC;
+        r.o.v[0] = x; r.o.v[1] = y; r.o.v[2] = radius;
+        return r;
+    }
+    // vertices (x, y) in order, either orientation
+    static Obstacle polygon(const std::vector<std::pair<double, double>> &vertices) {
+        if (vertices.size() < 3 || vertices.size() > PO_OBS_MAX_VERTS) throw std::invalid_argument("Obstacle::polygon: 3 .. 8 vertices");
+        Obstacle r{};
+        r.o.kind = PO_OBS_POLY;
+        r.o.n_verts = (int)vertices.size();
+        for (size_t i = 0; i < vertices.size(); ++i) { r.o.v[2 * i] = vertices[i].first; r.o.v[2 * i + 1] = vertices[i].second; }
+        return r;
+    }
+    // An oriented box as a 4-vertex polygon: the corners are computed here, on the host — the device sees polygons only, no trigonometry enters the exact path.
+    static Obstacle box(double cx, double cy, double half_length, double half_width, double yaw) {
+        const double c = std::cos(yaw), s = std::sin(yaw);
+        const int sl[4] = {1, -1, -1, 1}, sw[4] = {1, 1, -1, -1};
+        std::vector<std::pair<double, double>> v;
+        for (int i = 0; i < 4; ++i) v.emplace_back(cx + sl[i] * half_length * c - sw[i] * half_width * s, cy + sl[i] * half_length * s + sw[i] * half_width * c);
+        return polygon(v);
+    }
+};
+
 // M obstacle-distance layers of one size and resolution on one engine: one local grid per vehicle, per perception hypothesis, per scene.  Layer k is centred at
 // pos_xy[2k], pos_xy[2k + 1].  Which layer instance b of a batched call reads is the engine's assignment (setAssignment); without one every instance reads layer 0.
 // Installing a MapStack replaces the engine's Map and the other way round (an engine holds one stack; a Map is a stack of one).
@@ -73,6 +106,24 @@ class MapStack {
         const int rc = po_set_map_stack_occupancy(engine_->handle(), M, &o, pos_xy.data());
         if (rc != PO_OK) throw std::runtime_error(std::string("po_set_map_stack_occupancy: ") + po_strerror(rc));
     }
+    // One list of obstacles per layer over an optional static grid (base: nullptr, or [size_y][size_x] bytes shared by every layer, 0 = occupied): rasterised and
+    // transformed on the device; only the lists and the base travel (po_set_map_stack_obstacles).
+    static MapStack fromObstacles(const std::vector<std::vector<Obstacle>> &layers, int size_x, int size_y, double resolution, const std::vector<double> &pos_xy,
+                                  const unsigned char *base = nullptr, PoEngine *engine = nullptr) {
+        const int M = (int)layers.size();
+        if (pos_xy.size() != 2 * (size_t)M) throw std::invalid_argument("MapStack: pos_xy must hold M (x, y) pairs");
+        std::vector<po_obstacle> obs;
+        std::vector<int> first(1, 0);
+        for (const auto &l : layers) {
+            for (const auto &ob : l) obs.push_back(ob.o);
+            first.push_back((int)obs.size());
+        }
+        po_obstacle_lists ls{obs.data(), first.data(), (int)obs.size(), base, base ? 1 : 0, size_x, size_y, resolution, 0.0, 0.0};
+        MapStack st(engine ? engine : &PoEngine::instance(), M);
+        const int rc = po_set_map_stack_obstacles(st.engine_->handle(), M, &ls, pos_xy.data());
+        if (rc != PO_OK) throw std::runtime_error(std::string("po_set_map_stack_obstacles: ") + po_strerror(rc));
+        return st;
+    }
     // layer_of[b] = the layer instance b reads; an index outside [0, M) throws and leaves the previous table in force.  Empty: every instance reads layer 0.
     void setAssignment(const std::vector<int> &layer_of) const {
         const int rc = po_set_map_assignment(engine_->handle(), (int)layer_of.size(), layer_of.empty() ? nullptr : layer_of.data());
@@ -83,6 +134,7 @@ class MapStack {
     int layers() const { return M_; }
     PoEngine *engine() const { return engine_; }
  private:
+    MapStack(PoEngine *engine, int M) : engine_(engine), M_(M) {}
     void sample(int layer, double x, double y, double *d, int *in) const {
         const double xy[2] = {x, y};
         if (po_map_sample_layer(engine_->handle(), layer, 1, xy, d, in) != PO_OK) throw std::runtime_error("po_map_sample_layer failed");

@@ -269,6 +269,17 @@ int main(int argc, char **argv) {
         std::printf("top-level %s\n", top_ok ? "ok" : "FAILED");
         if (!top_ok) return 6;
     }
+    // 6) the map stack from obstacle lists (MapStack::fromObstacles): a disc layer and a box layer (Obstacle::box) over no base, sampled through the stack
+    {
+        const std::vector<std::vector<Obstacle>> lists = {{Obstacle::disc(12.0, 2.5, 1.0)}, {Obstacle::box(-5.0, 4.0, 2.0, 1.0, 0.5), Obstacle::polygon({{0, 0}, {1, 0}, {0, 1}})}};
+        const MapStack stack = MapStack::fromObstacles(lists, 500, 500, 0.2, {0.0, 0.0, 0.0, 0.0});
+        const double in_disc = stack.getObstacleDistance(0, 12.0, 2.5), off_disc = stack.getObstacleDistance(0, 12.0, 6.5);
+        const double in_box = stack.getObstacleDistance(1, -5.0, 4.0), other_layer = stack.getObstacleDistance(1, 12.0, 2.5);
+        const bool stack_ok = stack.layers() == 2 && in_disc == 0.0 && std::fabs(off_disc - 3.0) < 0.3 && in_box == 0.0 && other_layer > 5.0 && stack.isInside(1, 49.0, 0.0) &&
+                              !stack.isInside(1, 51.0, 0.0);
+        std::printf("obstacle stack %s: disc %.3f / %.3f box %.3f other layer %.3f\n", stack_ok ? "ok" : "FAILED", in_disc, off_disc, in_box, other_layer);
+        if (!stack_ok) return 7;
+    }
     std::string bad = "KCP";
     std::printf("create(KCP)=%s\n", OsqpSolver::create(bad, refs[0], vs[0], N) ? "object" : "nullptr");
     return ok && dmax < 1e-12 ? 0 : 1;

@@ -276,7 +276,8 @@ def make_planning_scenes(seed: int, B: int, n_way: int = 24, way_ds: float = 3.0
     list of waypoints, a start and a goal state over an obstacle-distance map): a smooth curve inside the map, waypoints every `way_ds`
     metres jittered laterally by +-`noise` (what a coarse planner returns), start = first waypoint with the curve's heading, goal =
     last waypoint; obstacles (discs) kept >= 3 m away from the curve's first 6 m and otherwise scattered beside it.
-    Returns dict: way_x, way_y [B,n_way], start [B,4] (x, y, heading, k), goal [B,3], and the shared map tuple (dist, res, px, py)."""
+    Returns dict: way_x, way_y [B,n_way], start [B,4] (x, y, heading, k), goal [B,3], the shared map tuple (dist, res, px, py) and discs [n,3] (x, y, r),
+    the obstacle list the map was drawn from."""
     rng = np.random.default_rng(np.random.SeedSequence([SEED0, 81, seed]))
     kw = dict(size_x=700, size_y=700, resolution=0.2, pos=(0.0, 0.0))
     kw.update(map_kw or {})
@@ -327,4 +328,5 @@ def make_planning_scenes(seed: int, B: int, n_way: int = 24, way_ds: float = 3.0
     for ox, oy, r in discs:
         d = np.minimum(d, np.hypot(X - ox, Y - oy) - r)
     out["map"] = (np.maximum(d, 0.0).astype(np.float32), kw["resolution"], kw["pos"][0], kw["pos"][1])
+    out["discs"] = np.array(discs, dtype=np.float64).reshape(-1, 3)
     return out
