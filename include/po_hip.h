@@ -283,12 +283,15 @@ int po_set_stream(po_handle h, void *hip_stream);
  * and the second launch takes the parked paths in order of expected remaining work, longest first; 0: one launch; left alone the engine slices batches of
  * at least two rounds of the device's wave slots (2 x 4 x CUs = 2048 paths) on shapes that run one wave per path, a value set here applies to every batch.  Scheduling only: the same operations in the same
  * order — statuses and certificates do not depend on it, the solutions agree to round-off (the kernels of the two launches are compiled separately; identical bit for bit on the
- * BASELINE KP / K shapes, <= 1e-10 elsewhere); BASELINE config 3: 4.76 -> 4.06 ms).  Unknown key: PO_ERR_INVALID. */
+ * BASELINE KP / K shapes, <= 1e-10 elsewhere); BASELINE config 3: 4.76 -> 4.06 ms), "fixed_length" (default 1; 0: the generic kernels also for the path lengths the library was built with kernels
+ * of their own for — the Makefile's PO_FIXED_N, KP with keep 4, non-ragged batches of exactly such a length; same operations in the same order, separately compiled).
+ * Unknown key: PO_ERR_INVALID. */
 int po_debug_set(po_handle h, const char *key, int value);
 /* Developer read-back (synchronises the stream): "fallback_paths" = how many paths the Newton launch of the last solve with refine = 2 did not certify and handed to
  * the fallback launch; "newton_parked" = how many went on into the second of the sliced Newton launches (-1: the last solve was not sliced); "map_ptr" = the device
  * address of the handle's map layer — layer 0 of the stack (0: no map; does not synchronise — po_set_map_occupancy_device / po_set_map_stack_occupancy_device with
- * an unchanged size and layer count must leave it where it is); "map_layers" = M, the number of layers the handle holds (0: no map; does not synchronise). */
+ * an unchanged size and layer count must leave it where it is); "map_layers" = M, the number of layers the handle holds (0: no map; does not synchronise); "fixed_length_used" = 1 when the last solve ran the
+ * length-specialised kernels, 0 when it ran the generic ones (does not synchronise). */
 int po_debug_get(po_handle h, const char *key, long long *value);
 
 /* Host-pointer entry: H2D, solve, D2H, synchronous. */

@@ -36,7 +36,8 @@ class PoError(RuntimeError):
 
 
 _ENV_DEBUG = {"PO_IDENTITY_ORDER": "identity_order", "PO_DEBUG_CYCLES": "debug_cycles", "PO_SMOOTH_SEQ": "smooth_seq",
-              "PO_SMOOTH_WAVES": "smooth_waves", "PO_SMOOTH_NOPAD": "smooth_nopad", "PO_SMOOTH_DEBUG": "smooth_debug", "PO_DP_ONE_WAVE": "dp_one_wave", "PO_NEWTON_SLICE": "newton_slice"}
+              "PO_SMOOTH_WAVES": "smooth_waves", "PO_SMOOTH_NOPAD": "smooth_nopad", "PO_SMOOTH_DEBUG": "smooth_debug", "PO_DP_ONE_WAVE": "dp_one_wave", "PO_NEWTON_SLICE": "newton_slice",
+              "PO_FIXED_LENGTH": "fixed_length"}
 
 
 def lib():
@@ -209,7 +210,7 @@ class Engine:
             raise
 
     def debug_set(self, key: str, value: int):
-        """po_debug_set: developer A/B switches (identity_order, debug_cycles, host_threads, smooth_seq, smooth_waves, smooth_nopad, smooth_debug, dp_one_wave, newton_slice)."""
+        """po_debug_set: developer A/B switches (identity_order, debug_cycles, host_threads, smooth_seq, smooth_waves, smooth_nopad, smooth_debug, dp_one_wave, newton_slice, fixed_length)."""
         _check(lib().po_debug_set(self._h, key.encode(), int(value)))
 
     def debug_get(self, key: str) -> int:

@@ -181,6 +181,7 @@ int po_debug_set(po_handle h, const char *key, int value) {
     else if (k == "host_threads") h->host_threads = value < 0 ? 0 : value;
     else if (k == "debug_cycles") h->env_cycles = value != 0;
     else if (k == "newton_slice") { h->nw_slice = value > 0 ? (int)value : 0; h->nw_slice_forced = value > 0; }  // (set explicitly: also on batches the engine would not slice)
+    else if (k == "fixed_length") h->fixed_length = value != 0;  // (0: the generic kernels also for the lengths of PO_FIXED_N; an A/B switch, the results do not depend on it)
     else if (k == "smooth_seq") h->env_smooth_seq = value != 0;
     else if (k == "smooth_waves") h->env_smooth_waves = value;
     else if (k == "smooth_nopad") h->env_smooth_nopad = value != 0;
@@ -200,6 +201,10 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
     }
     if (k == "map_layers") {  // how many layers the handle's map stack holds (0: no map); no device call
         *value = h->maps.d ? h->maps.M : 0;
+        return PO_OK;
+    }
+    if (k == "fixed_length_used") {  // did the last solve run the length-specialised kernels (1) or the generic ones (0)?  no device call
+        *value = h->fixed_used;
         return PO_OK;
     }
     if (k == "fallback_paths") {  // split scheduling of refine = 2: how many paths the last solve's Newton launch handed to the fallback launch
@@ -320,6 +325,7 @@ static void fill_dev_batch(const po_handle_s *h, po::DevBatch *D, const po_batch
     D->fb_list = nullptr;
     D->nw_phase = 0; D->nw_state = nullptr; D->nw_stride = 0; D->nw_keys = nullptr; D->nw_list = nullptr;
     D->nw_follows = 0;
+    D->fixed_len = (h->fixed_length && !in->n_points && po_has_fixed_length(in->formulation, in->N, C, in->keep)) ? 1 : 0;
     D->n = n; D->m = m;
 }
 
@@ -344,6 +350,7 @@ int po_solve_batch_device(po_handle h, const po_batch_in *in, const po_batch_out
     }
     if ((rc = h->scale_buf.ensure(sizeof(double) * 64 * (size_t)in->B))) return rc;
     D.scale = static_cast<double *>(h->scale_buf.p);
+    h->fixed_used = D.fixed_len;
     bool polish = false;
     if (h->params.polish || h->params.refine) {  // OSQP's polish (opt-in) and the Newton refinement pick the ADMM state up from pol_buf, where the solve kernels leave it
         const int sd = po_polish_state_doubles(in->formulation, in->N, C, in->keep);

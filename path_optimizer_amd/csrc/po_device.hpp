@@ -70,6 +70,9 @@ struct DevBatch {
     // set by the engine on the warm-start launch of a split solve (po_params.refine = 2): newton_kernel follows on the same stream and writes the outputs of every path
     // the warm start reports SOLVED (from its own result, or — attempt not taken — from the state block), so the solve kernel skips its output pass for those
     int nw_follows;
+    // set by the engine: the length-specialised kernels (Fast's NFIX, po_fast.inc) may be taken for this batch — not ragged, its N, C, keep are those of an instantiation of
+    // the Makefile's PO_FIXED_N, and po_debug_set("fixed_length", 0) has not switched them off.  Read by the launchers only; no kernel looks at it.
+    int fixed_len;
 };
 
 template <int F> struct FormTraits;

@@ -221,7 +221,15 @@ struct ReclassFn {
 //         of the keep-4 kernel.  NT = 64: both roles share ONE wave (lanes 0..31 / 32..63, <= 32 chunks); NT = 128: one wave per role (<= 64 chunks).  What crosses the role
 //         boundary inside a sweep is a 3-vector (+ the running control accumulator) through an LDS slot.  See solve_split().
 // NWX (what the kernels are instantiated with): 1 = one lane per chunk, 2 = role-split, 3 = role-split of an odd keep.
-template <int F, int SPL, int NT, bool TWO, int NWX = 1> struct Fast {
+// NFIX: the path length at COMPILE time (0: at run time), for the LDS LAYOUT and the global offsets: LayoutF — TP, every table offset, the row counts of the scans — is then a
+// constant of the instantiation and the LDS addresses are immediates; the same LayoutF / state block / parking block as at run time, so a path may cross between a fixed and a
+// generic kernel (fall-back rounds, polish, a resumed path).  N and C THEMSELVES stay run-time values on purpose: with N a constant the compiler merges the per-stage
+// `stage(q) < N` regions and drops the copies of the final-stage rows that cannot occur, which changes where multiply-adds are contracted — 10 % fewer instructions still, but the
+// results then differ from the generic kernels' in the last bits and a path in 4 096 takes one Newton step more (DESIGN.md section 19).  Layout only: bit for bit the generic
+// kernels' results.  The launchers take such an instantiation only for a non-ragged batch of exactly that length.
+template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fast {
+    static_assert(NFIX == 0 || (F == F_KP && TWO && NWX == 1 && NFIX >= 2 && NFIX <= NT * SPL), "fixed length: KP, one lane per chunk, a length the shape covers");
+    static constexpr int kFixC = NFIX > 0 ? (NFIX + SPL - 2) / SPL : 0;  // controls of a path of NFIX points (keep == SPL on this shape: path_c())
     static constexpr int NW = (NWX == 2 || NWX == 3) ? 2 : 1, ODD = NWX == 3 ? 1 : 0;
     static_assert(NWX >= 1 && NWX <= 5, "NWX");
     static_assert(NW == 1 || (NW == 2 && TWO && (NT == 64 || NT == 128) && SPL >= 2 && FormTraits<F>::HAS_U), "role-split mapping: KP / KPC, two-level");
@@ -266,8 +274,8 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1> struct Fast {
     // (forced inline: outlined — which the inliner does once the kernel is large enough — `this` escapes, the object lives in scratch, and every LDS access
     // through S degrades to a flat load: 17.5 -> 41.7 ms per BASELINE batch)
     __device__ __forceinline__ Fast(const DevParams &P_, const DevBatch &in_, double *S_, int b_)
-        : P(P_), in(in_), L(path_n(in_, b_), path_c<F>(in_, b_), SPL, TWO, NT, NW, CH, NG), S(S_), N(path_n(in_, b_)), C(path_c<F>(in_, b_)), keep(in_.keep), tid(threadIdx.x), b(b_),
-          po((size_t)b_ * in_.N) {
+        : P(P_), in(in_), L(NFIX > 0 ? NFIX : path_n(in_, b_), NFIX > 0 ? kFixC : path_c<F>(in_, b_), SPL, TWO, NT, NW, CH, NG), S(S_), N(path_n(in_, b_)),
+          C(path_c<F>(in_, b_)), keep(in_.keep), tid(threadIdx.x), b(b_), po((size_t)b_ * (NFIX > 0 ? NFIX : in_.N)) {
         sc = in_.scale + (size_t)b_ * kScStride;
         elo = -kInf; ehi = kInf;
         if (P.end_heading) {  // solver_kp_as_input.cpp:193-202
@@ -4039,8 +4047,8 @@ constexpr int kStatusRestoreEntry = 3;  // admm_loop only: a round below eps ran
                                         // returns the point the round started from — it met eps in the round before — as PO_STATUS_SOLVED, not certified
 // RESUME (kernels with the refinement phase, po_params.refine_rounds > 1): continue from `prev` (iteration count, rho, refactorisation count) with the
 // termination thresholds scaled by eps_mul; the state is the one the refinement left, re-expressed for the type-based step vector.
-template <bool UNI, bool RESUME, int F, int SPL, int NT, bool TWO, int NWX>
-__device__ __forceinline__ LoopOut admm_loop(Fast<F, SPL, NT, TWO, NWX> &fx, typename Fast<F, SPL, NT, TWO, NWX>::LS &st, const DevBatch &in, const DevParams &P, long long tc[3], long long ph[8],
+template <bool UNI, bool RESUME, int F, int SPL, int NT, bool TWO, int NWX, int NFIX>
+__device__ __forceinline__ LoopOut admm_loop(Fast<F, SPL, NT, TWO, NWX, NFIX> &fx, typename Fast<F, SPL, NT, TWO, NWX, NFIX>::LS &st, const DevBatch &in, const DevParams &P, long long tc[3], long long ph[8],
                                              double eps_mul = 1.0, bool resume = false, int it0 = 0, int nref0 = 0, double rho_prev = 0.0) {
     // (rho is wave-uniform and alive for the whole solve: scalar registers — uni(), po_device.hpp)
     double rho = uni(fmin(fmax(P.rho0, kRhoMin), kRhoMax));
@@ -4077,7 +4085,7 @@ __device__ __forceinline__ LoopOut admm_loop(Fast<F, SPL, NT, TWO, NWX> &fx, typ
         PO_FRESH_LANE_ID(fx);
         long long t2 = prof ? __builtin_readcyclecounter() : 0;
         const bool can_check = P.check_every > 0 && (it % P.check_every == 0);
-        typename Fast<F, SPL, NT, TWO, NWX>::Cert cert = {0, 0, 0};
+        typename Fast<F, SPL, NT, TWO, NWX, NFIX>::Cert cert = {0, 0, 0};
         if constexpr (TWO) {
             if (can_check) cert = fx.template update_pass_two<true, false, UNI>(st, rho, first);
             else if (first) (void)fx.template update_pass_two<false, true, UNI>(st, rho, true);
@@ -4148,8 +4156,8 @@ constexpr int kNwStagnation = 8;
 // point, on return st.cls* hold the row classes of the bounds and v is expressed for the type-based step vector at rho_solve.
 // PH: 0 the whole phase; 1 first of the two sliced launches (parks); 2 second (resumes) — compile-time, each with its own register allocation (one body with both
 // at run time: 77 -> 207 spilled VGPRs, the launch 3.8 -> 4.9 ms)
-template <int F, int SPL, int NT, int NWX, int PH = 0>
-__device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, NWX> &fx, typename Fast<F, SPL, NT, true, NWX>::LS &st, const DevParams &P, double rho_solve, double rp0, double rd0,
+template <int F, int SPL, int NT, int NWX, int PH = 0, int NFIX = 0>
+__device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, NWX, NFIX> &fx, typename Fast<F, SPL, NT, true, NWX, NFIX>::LS &st, const DevParams &P, double rho_solve, double rp0, double rd0,
                                                          int slice = 0, double *park = nullptr, int *park_key = nullptr) {
     constexpr bool resume = PH == 2;
     if constexpr (PH != 1) slice = 0;
@@ -4371,9 +4379,10 @@ __device__ __forceinline__ void zero_outputs(const DevBatch &in, int b, int nt) 
 // REF = 2 (newton_fallback_kernel only, general variant): round `in.round` >= 1 of a path the Newton launch did not certify — the type-based iteration resumed from the
 // state block at a 10 x tighter eps, then the Newton refinement again (po_params.refine_rounds / refine_extra_rounds; round 5 removed the chained-rounds queue, the
 // speculative continuations, the probe launches and the refine = 1 phase that used to live here: the Newton split launches beat them on every shape, DESIGN.md §10).
-template <int F, int SPL, int NT, bool TWO, bool UNI, int NWX, int REF = 0> __device__ __forceinline__ void solve_body(const DevBatch &in, const DevParams &P, int b_given = -1) {
+template <int F, int SPL, int NT, bool TWO, bool UNI, int NWX, int REF = 0, int NFIX = 0> __device__ __forceinline__ void solve_body(const DevBatch &in, const DevParams &P, int b_given = -1) {
     static_assert(TWO || !UNI, "the single-level mapping has no uniform variant");
     static_assert(REF == 0 || (REF == 2 && TWO && !UNI), "the later rounds run on the general variant of the two-level mapping");
+    static_assert(NFIX == 0 || (REF == 0 && UNI), "fixed length: the uniform warm start only");
     extern __shared__ double smem[];
     // workgroup i lands on XCD i mod 8 (a static partition of the launch): a bit-mixing bijection on [0, B) (xorshift / odd multiply on
     // perm_bits bits, cycle-walking back into range) keeps any regular pattern in the caller's path order — periodic or clustered — from
@@ -4387,8 +4396,8 @@ template <int F, int SPL, int NT, bool TWO, bool UNI, int NWX, int REF = 0> __de
     if constexpr (TWO && !UNI) {
         if (in.only_deferred && round == 0 && in.out_info[b].status != kStatusDeferred) return;  // solved by the UNI = true launch that went before
     }
-    Fast<F, SPL, NT, TWO, NWX> fx(P, in, smem, b);
-    typename Fast<F, SPL, NT, TWO, NWX>::LS st;
+    Fast<F, SPL, NT, TWO, NWX, NFIX> fx(P, in, smem, b);
+    typename Fast<F, SPL, NT, TWO, NWX, NFIX>::LS st;
     fx.load(st);
     if (fx.inputs_have_nan()) {  // block-uniform; never "solved", nothing computed: the path's outputs are zeroed (a defined value, not the buffer's previous content)
         zero_outputs(in, b, NT);
@@ -4441,10 +4450,10 @@ template <int F, int SPL, int NT, bool TWO, bool UNI, int NWX, int REF = 0> __de
         if (P.refine && lo.status == PO_STATUS_SOLVED) {
             const bool last = round + 1 >= rounds_total;
             __syncthreads();
-            typename Fast<F, SPL, NT, TWO, NWX>::LS st2;
+            typename Fast<F, SPL, NT, TWO, NWX, NFIX>::LS st2;
             fx.load(st2);
             fx.template state_io<false>(st2, state);
-            const RefineOut ro = refine_phase_newton<F, SPL, NT, NWX>(fx, st2, P, lo.rho, lo.R.rp, lo.R.rd);
+            const RefineOut ro = refine_phase_newton<F, SPL, NT, NWX, 0, NFIX>(fx, st2, P, lo.rho, lo.R.rp, lo.R.rd);
             __syncthreads();
             // (an early return here costs the whole kernel its register allocation: a failed attempt leaves through the hand-back exit below instead)
             if (ro.take) fx.template state_io<true>(st2, state);  // else: out of iterations and not better — the solved point stays
@@ -4479,8 +4488,8 @@ template <int F, int SPL, int NT, bool TWO, bool UNI, int NWX, int REF = 0> __de
         if (in.dbg_cycles != nullptr) { long long *d = in.dbg_cycles + (size_t)b * 16; d[0] = tc[0]; d[1] = tc[1]; d[2] = tc[2]; d[3] = lo.it; for (int i = 0; i < 8; ++i) d[4 + i] = ph[i]; d[12] = UNI ? 1 : 0; }
     }
 }
-template <int F, int SPL, int NT, bool TWO, bool UNI, int NWX = 1> __global__ PO_KERNEL_ATTR __launch_bounds__(NT) void solve_kernel_fast(DevBatch in, DevParams P) {
-    solve_body<F, SPL, NT, TWO, UNI, NWX, 0>(in, P);
+template <int F, int SPL, int NT, bool TWO, bool UNI, int NWX = 1, int NFIX = 0> __global__ PO_KERNEL_ATTR __launch_bounds__(NT) void solve_kernel_fast(DevBatch in, DevParams P) {
+    solve_body<F, SPL, NT, TWO, UNI, NWX, 0, NFIX>(in, P);
 }
 
 // OSQP's polish on the paths the solve kernels reported solved (po_params.polish; launched after both loop variants, same shape and LDS layout).
@@ -4570,8 +4579,8 @@ template <int F, int SPL, int NT, int NWX = 1> __global__ PO_KERNEL_ATTR __launc
     }
 }
 
-template <int F, int SPL, int NT, int NWX = 1, int PH = 1> __global__ PO_KERNEL_ATTR __launch_bounds__(NT) void newton_kernel(DevBatch in, DevParams P) {
-    using FX = Fast<F, SPL, NT, true, NWX>;
+template <int F, int SPL, int NT, int NWX = 1, int PH = 1, int NFIX = 0> __global__ PO_KERNEL_ATTR __launch_bounds__(NT) void newton_kernel(DevBatch in, DevParams P) {
+    using FX = Fast<F, SPL, NT, true, NWX, NFIX>;
     extern __shared__ double smem[];
     // SLICED LAUNCHES (in.nw_phase; the engine's default on one-wave shapes, DESIGN.md section 11): phase 1 runs every path for at most P.ref_nw_slice Newton steps — every path takes
     // that many, so the launch has no tail — and parks what is not finished (state block of its own, a priority key); nw_sort_kernel orders the parked paths by expected
@@ -4608,7 +4617,7 @@ template <int F, int SPL, int NT, int NWX = 1, int PH = 1> __global__ PO_KERNEL_
 #ifdef PO_NW_TRACE
     const long long tk1_ = __builtin_readcyclecounter();
 #endif
-    const RefineOut ro = refine_phase_newton<F, SPL, NT, NWX, PH>(fx, st, P, lo_rho, rp0, rd0, slicing ? P.ref_nw_slice : 1 << 30, pscal, slicing ? in.nw_keys + b : nullptr);
+    const RefineOut ro = refine_phase_newton<F, SPL, NT, NWX, PH, NFIX>(fx, st, P, lo_rho, rp0, rd0, slicing ? P.ref_nw_slice : 1 << 30, pscal, slicing ? in.nw_keys + b : nullptr);
     __syncthreads();
 #ifdef PO_NW_TRACE
     const long long tk2_ = __builtin_readcyclecounter();

@@ -81,7 +81,9 @@ extern "C" hipError_t po_launch_solve(int form, const po::DevBatch *in, const po
     using namespace po;
     hipError_t e;
     if (form == F_KP) {
-        e = po_launch_solve_kp_uni(in, P, st, lds_out);
+        // a listed length (DevBatch::fixed_len): the uniform warm start compiled for that length; the general variant behind it picks up what it deferred, as always
+        e = in->fixed_len ? po_launch_solve_kp_fix_uni(in, P, st, lds_out) : kNotMyShape;
+        if (e == kNotMyShape) e = po_launch_solve_kp_uni(in, P, st, lds_out);
         if (e == kNotMyShape) {  // not a shape of keep 1 .. 8: the wide objects
             e = po_launch_solve_kp_w_uni(in, P, st, lds_out);
             return e != hipSuccess ? e : po_launch_solve_kp_w(in, P, st, lds_out);
@@ -102,7 +104,8 @@ extern "C" hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_
 extern "C" hipError_t po_launch_newton(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
     using namespace po;
     if (form == F_KP) {  // (an object answers kNotMyShape for a shape it does not hold; any other code is that launch's own failure and is returned as it is)
-        hipError_t e = po_launch_newton_kp(in, P, st);
+        hipError_t e = !in->fixed_len ? kNotMyShape : (in->nw_phase == 2 ? po_launch_newton_kp_fix2(in, P, st) : po_launch_newton_kp_fix1(in, P, st));
+        if (e == kNotMyShape) e = po_launch_newton_kp(in, P, st);
         if (e == kNotMyShape) e = po_launch_newton_kp_b(in, P, st);
         if (e == kNotMyShape) e = po_launch_newton_kp_c(in, P, st);
         if (e == kNotMyShape) e = po_launch_newton_kp_w1(in, P, st);
@@ -204,6 +207,8 @@ extern "C" hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipSt
     hipLaunchKernelGGL(po::nw_sort_kernel, dim3(1), dim3(po::kNwSortThreads), 0, st, keys, B, list);
     return hipGetLastError();
 }
+// is there a length-specialised instantiation for a (non-ragged) batch of this shape?  (KP only)
+extern "C" int po_has_fixed_length(int form, int N, int C, int keep) { return form == po::F_KP ? po_has_fixed_length_kp(N, C, keep) : 0; }
 extern "C" int po_polish_state_doubles(int form, int N, int C, int keep) {
     using namespace po;
     if (form == F_KP) { const int d = po_polish_state_doubles_kp(N, C, keep); return d ? d : po_polish_state_doubles_kp_w(N, C, keep); }

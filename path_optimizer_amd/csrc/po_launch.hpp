@@ -30,6 +30,7 @@ int po_shape_threads(int form, int N, int C, int keep);
 int po_polish_state_doubles(int form, int N, int C, int keep);
 int po_newton_park_doubles(int form, int N, int C, int keep);
 int po_has_polish_kernel(int form, int N, int C, int keep);
+int po_has_fixed_length(int form, int N, int C, int keep);
 
 // ---- po_solve_form.hip: one object per formulation, loop variant and shape group; the names are pasted together there (PO_G / PO_CAT) ----
 #define PO_DECL_SOLVE(name) hipError_t name(const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out)
@@ -44,6 +45,9 @@ PO_DECL_NEWTON(po_launch_newton_kp); PO_DECL_NEWTON(po_launch_newton_kpc); PO_DE
 PO_DECL_NEWTON(po_launch_newton_kp_b);  // KP's role-split shapes (second Newton object)
 PO_DECL_NEWTON(po_launch_newton_kp_c);  // KP's multi-group shapes (third)
 PO_DECL_NEWTON(po_launch_newton_kp_w1); PO_DECL_NEWTON(po_launch_newton_kp_w2); PO_DECL_NEWTON(po_launch_newton_kp_w3);  // keep 9 .. 16
+// the length-specialised kernels of KP's headline shape (Makefile: PO_FIXED_N), objects of their own: the uniform warm start; the first / second Newton launch
+PO_DECL_SOLVE(po_launch_solve_kp_fix_uni); PO_DECL_LAUNCH(po_launch_newton_kp_fix1); PO_DECL_LAUNCH(po_launch_newton_kp_fix2);
+int po_has_fixed_length_kp(int N, int C, int keep);
 PO_DECL_LAUNCH(po_launch_polish_kp); PO_DECL_LAUNCH(po_launch_polish_kpc); PO_DECL_LAUNCH(po_launch_polish_k);
 PO_DECL_SIZES(po_polish_state_doubles_kp); PO_DECL_SIZES(po_polish_state_doubles_kp_w);
 PO_DECL_SIZES(po_polish_state_doubles_kpc); PO_DECL_SIZES(po_polish_state_doubles_k);

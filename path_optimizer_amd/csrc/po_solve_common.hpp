@@ -292,6 +292,52 @@ template <int F, bool FB, int G = PO_SHAPE_GROUP> hipError_t launch_newton(const
 #undef PO_X
     return kNotMyShape;
 }
+// ---- the length-specialised kernels (Fast's NFIX): KP, the shape (SPL 4, NT 64, one lane per chunk), the lengths of the Makefile's PO_FIXED_N.  Objects of their own
+// (-DPO_FIX=1 the uniform warm start, 2 / 3 the first / second Newton launch), which get the list as -D'PO_FIXED_LIST(X)=X(200) ...'.  Everything else — the general
+// warm-start variant, newton_fallback_kernel, the polish, every other shape, ragged batches, unlisted lengths — runs the generic kernels; the layouts are the same.
+#ifdef PO_FIX
+#ifndef PO_FIXED_LIST
+#define PO_FIXED_LIST(X)
+#endif
+constexpr int kFixSpl = 4, kFixNt = 64;
+// the batch is one the fixed instantiations are built for: KP's keep 4 on one lane per chunk, C what path_c() gives a path of N points; returns its LDS bytes (0: not that shape)
+static inline size_t fixed_shape_lds(int N, int C, int keep) {
+    Shape s;
+    if (keep != kFixSpl || C != (N + keep - 2) / keep || !resolve_shape(F_KP, N, C, keep, &s)) return 0;
+    if (!s.two || s.nt != kFixNt || s.spl != kFixSpl || s.nwx != 1) return 0;
+    const size_t lds = lds_of(F_KP, N, C, s);
+    return lds <= 160 * 1024 ? lds : 0;
+}
+#if PO_FIX == 1
+static inline bool has_fixed_length(int N, int C, int keep) {
+    if (!fixed_shape_lds(N, C, keep)) return false;
+#define PO_X(N_) if (N == N_) return true;
+    PO_FIXED_LIST(PO_X)
+#undef PO_X
+    return false;
+}
+static inline hipError_t launch_form_fixed(const DevBatch *in_, const DevParams *P, hipStream_t st, size_t *lds_out) {
+    const size_t lds = (in_->fixed_len && in_->n_points == nullptr) ? fixed_shape_lds(in_->N, in_->C, in_->keep) : 0;
+    if (!lds) return kNotMyShape;
+    DevBatch copy = *in_;
+    copy.only_deferred = 0;
+    const DevBatch *in = &copy;
+#define PO_X(N_) if (in->N == N_) { if (lds_out) *lds_out = lds; return launch1(&solve_kernel_fast<F_KP, kFixSpl, kFixNt, true, true, 1, N_>, in, P, kFixNt, lds, st); }
+    PO_FIXED_LIST(PO_X)
+#undef PO_X
+    return kNotMyShape;
+}
+#else
+template <int PH> static inline hipError_t launch_newton_fixed(const DevBatch *in, const DevParams *P, hipStream_t st) {
+    const size_t lds = (in->fixed_len && in->n_points == nullptr) ? fixed_shape_lds(in->N, in->C, in->keep) : 0;
+    if (!lds || (in->nw_phase == 2) != (PH == 2)) return kNotMyShape;
+#define PO_X(N_) if (in->N == N_) return launch1(&newton_kernel<F_KP, kFixSpl, kFixNt, 1, PH, N_>, in, P, kFixNt, lds, st);
+    PO_FIXED_LIST(PO_X)
+#undef PO_X
+    return kNotMyShape;
+}
+#endif
+#endif
 // OSQP's polish: one-lane-per-chunk shapes (the role-split shapes of keep 6 .. 8 have no polish kernel: status_polish stays 0 = not attempted, like the single-level mapping)
 template <int F> inline bool has_polish_kernel(int N, int C, int keep) {
     Shape s;
