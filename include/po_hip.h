@@ -291,7 +291,9 @@ int po_debug_set(po_handle h, const char *key, int value);
  * the fallback launch; "newton_parked" = how many went on into the second of the sliced Newton launches (-1: the last solve was not sliced); "map_ptr" = the device
  * address of the handle's map layer — layer 0 of the stack (0: no map; does not synchronise — po_set_map_occupancy_device / po_set_map_stack_occupancy_device with
  * an unchanged size and layer count must leave it where it is); "map_layers" = M, the number of layers the handle holds (0: no map; does not synchronise); "fixed_length_used" = 1 when the last solve ran the
- * length-specialised kernels, 0 when it ran the generic ones (does not synchronise). */
+ * length-specialised kernels, 0 when it ran the generic ones (does not synchronise); "dp_waves_used" = 8 or 1, the waves per instance of the handle's last DP lattice
+ * search — po_dp_search_batch* or the search inside po_plan_batch* (0: none yet; does not synchronise): one wave above 512 instances, under "dp_one_wave", and when
+ * the eight-wave reduction scratch does not fit in LDS beside the spline. */
 int po_debug_get(po_handle h, const char *key, long long *value);
 
 /* Host-pointer entry: H2D, solve, D2H, synchronous. */

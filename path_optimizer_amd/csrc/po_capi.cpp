@@ -207,6 +207,10 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
         *value = h->fixed_used;
         return PO_OK;
     }
+    if (k == "dp_waves_used") {  // which variant the launcher picked for the handle's last DP lattice search: 8 or 1 waves per instance (0: no search yet); no device call
+        *value = h->dp_waves_used;
+        return PO_OK;
+    }
     if (k == "fallback_paths") {  // split scheduling of refine = 2: how many paths the last solve's Newton launch handed to the fallback launch
         *value = 0;
         if (!h->fb_buf.p) return PO_OK;
@@ -1231,7 +1235,7 @@ int po_dp_search_batch_device(po_handle h, const po_spline_in *in, const double 
     HIP_TRY(hipSetDevice(h->device));
     const po::DevSpline D = make_dev_spline(in);
     po::DevSearch Q{p.search_lateral_range, p.search_long_spacing, p.search_lat_spacing, start, L, layer_s, lb, ub, l0, n_layers};
-    HIP_TRY(po_launch_dp_search(&h->maps, &D, &Q, h->env_dp_one_wave ? 1 : 0, h->stream));
+    HIP_TRY(po_launch_dp_search(&h->maps, &D, &Q, h->env_dp_one_wave ? 1 : 0, &h->dp_waves_used, h->stream));
     return PO_OK;
 }
 

@@ -96,6 +96,7 @@ struct po_handle_s {
     int wave_slots = 1024;  // paths the device runs at a time (one wave per SIMD: 4 per CU); batches below two rounds of that are not sliced (no queueing tail to remove)
     bool fixed_length = true;  // take the length-specialised kernels where the batch has one (po_debug_set "fixed_length"; 0: always the generic kernels).  Same results.
     int fixed_used = 0;        // ... and whether the last solve ran them (po_debug_get "fixed_length_used")
+    int dp_waves_used = 0;     // waves per instance of the last DP lattice search: 8 or 1 (0: none yet; po_debug_get "dp_waves_used")
     int nw_slice = 8;  // steps of the first of the two Newton launches (po_debug_set "newton_slice"; 0: one launch).  Scheduling only.
     HostBuf fb_host; // ... and the pinned word its count is read back into (refine_chain = 2)
     // developer switches (po_debug_set; the library reads no environment variable): identity_order (block i solves path i), debug_cycles (per-phase shader

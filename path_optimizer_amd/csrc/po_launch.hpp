@@ -68,7 +68,7 @@ hipError_t po_launch_map_sample(const po::DevMaps *m, int layer, int n, const do
 hipError_t po_launch_bounds(const po::DevMaps *m, const po::DevBounds *in, double *bounds, int *n_valid, hipStream_t st);
 hipError_t po_launch_resample(const po::DevSpline *in, const po::DevResample *r, hipStream_t st);
 hipError_t po_launch_limits(int B, int N, const int *n_points, const double *v, const double *a, double *max_k, double *max_kp, double mu, double rate, hipStream_t st);
-hipError_t po_launch_dp_search(const po::DevMaps *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st);
+hipError_t po_launch_dp_search(const po::DevMaps *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, int *waves_used, hipStream_t st);  // *waves_used: 8 or 1
 size_t po_dp_lds_bytes(int K, int L);
 size_t po_spline_lds_bytes(int K);
 hipError_t po_launch_bspline(int B, int W, const int *n_way, const double *wx, const double *wy, int M, double *x, double *y, double *s, int *n_samples, hipStream_t st);

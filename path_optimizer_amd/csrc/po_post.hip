@@ -765,6 +765,12 @@ __global__ __launch_bounds__(128) void densify_kernel(DevMaps ms, DevCar c, int 
         }
         for (int j = 0; j < 5; ++j) o[5 * i + j] = v[j];
     }
+    // More samples than room: the reference's walk tests a sample for collision BEFORE it stores it, so M samples kept and sample M colliding is a complete answer
+    // (n_out = M), not a capacity problem.  One lane looks at that one sample.
+    if (total > M && tid == 0 && c.enable) {
+        const SplAt pa = S.at((double)M * spacing);
+        if (!collision_free(m, c, S.x(pa), S.y(pa), S.heading(pa))) atomicMin(&first, M);
+    }
     __syncthreads();
     const int f = first;
     if (f < total || total > M) {  // truncated by a collision (or by the capacity)
@@ -774,7 +780,7 @@ __global__ __launch_bounds__(128) void densify_kernel(DevMaps ms, DevCar c, int 
     }
     if (tid == 0) {
         if (f >= total && total <= M) { n_out[b] = total; ok[b] = 1; }
-        else if (f >= lim && total > M) { n_out[b] = -2; ok[b] = 0; }  // M too small before any collision
+        else if (f > M && total > M) { n_out[b] = -2; ok[b] = 0; }  // M too small: no collision among samples 0 .. M
         else { n_out[b] = f; ok[b] = (f > 0 && (double)(f - 1) * spacing >= 20.0) ? 1 : 0; }
     }
 }
@@ -902,16 +908,18 @@ extern "C" hipError_t po_launch_limits(int B, int N, const int *n_points, const 
     hipLaunchKernelGGL(po::limits_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, B, N, n_points, v, a, max_k, max_kp, mu, rate);
     return hipGetLastError();
 }
-extern "C" hipError_t po_launch_dp_search(const po::DevMaps *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, hipStream_t st) {
+extern "C" hipError_t po_launch_dp_search(const po::DevMaps *m, const po::DevSpline *in, const po::DevSearch *q, int one_wave, int *waves_used, hipStream_t st) {
     const size_t lds1 = po_dp_lds_bytes(in->K, q->L), lds4 = lds1 + kDpEightWaveScratch;
     // few instances (a planner's own call: B = 1): eight waves per instance share the edge evaluations of a layer; a full batch keeps one wave per instance
     // (one_wave: the caller's A/B switch, po_debug_set "dp_one_wave")
     if (in->B <= 512 && !one_wave && lds4 <= 160 * 1024) {
+        if (waves_used) *waves_used = 8;
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&po::dp_search_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(po::dp_search_kernel<8>, dim3(in->B), dim3(512), lds4, st, *m, *in, *q);
         return hipGetLastError();
     }
+    if (waves_used) *waves_used = 1;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&po::dp_search_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(po::dp_search_kernel<1>, dim3(in->B), dim3(64), lds1, st, *m, *in, *q);
