@@ -268,7 +268,7 @@ int po_device_count(void);
  * entry takes the handle's inner lock while it enqueues, owns no staging, and its scratch is ordered by the stream.  The library orders the calls; every call returns
  * what it would return in SOME serial order of the calls, i.e. what the same call returns on a handle nobody else uses (results do not depend on what a handle ran
  * before: tests/test_handle_contract.py).  Two calls on one handle never overlap on the device — use two handles for that.
- * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_set_map_occupancy* / po_set_map_stack* (po_set_map_stack_obstacles* included) /
+ * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_set_map_occupancy* / po_set_map_stack* (po_set_map_stack_obstacles* and po_set_map_stack_scene* included) / po_set_world_occupancy* /
  * po_set_map_assignment* / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
  * start afterwards use the new stream / map / switch, and the caller orders what is already enqueued on the old stream.  po_last_kernel_ms / po_last_phase_ms
  * describe the handle's last solve, whichever thread made it.  po_destroy must not race with any call. */
@@ -293,7 +293,8 @@ int po_debug_set(po_handle h, const char *key, int value);
  * an unchanged size and layer count must leave it where it is); "map_layers" = M, the number of layers the handle holds (0: no map; does not synchronise); "fixed_length_used" = 1 when the last solve ran the
  * length-specialised kernels, 0 when it ran the generic ones (does not synchronise); "dp_waves_used" = 8 or 1, the waves per instance of the handle's last DP lattice
  * search — po_dp_search_batch* or the search inside po_plan_batch* (0: none yet; does not synchronise): one wave above 512 instances, under "dp_one_wave", and when
- * the eight-wave reduction scratch does not fit in LDS beside the spline. */
+ * the eight-wave reduction scratch does not fit in LDS beside the spline; "world_cells" = size_x * size_y of the handle's world grid (po_set_world_occupancy*; 0: none;
+ * does not synchronise). */
 int po_debug_get(po_handle h, const char *key, long long *value);
 
 /* Host-pointer entry: H2D, solve, D2H, synchronous. */
@@ -399,7 +400,9 @@ typedef struct po_obstacle_lists {
                                      layer k owns obs[first[k] .. first[k+1]) */
     int                  n_obs;
     const unsigned char *base;    /* NULL = every cell free; else base_count images [size_y][size_x], 0 = occupied (po_occupancy's convention) */
-    int                  base_count;  /* 0, 1 (one image shared by every layer, cell (i,j) -> cell (i,j)) or M */
+    int                  base_count;  /* 0, 1 (one image shared by every layer, cell (i,j) -> cell (i,j)) or M.  A shared base IGNORES pos_xy: it means the
+                                         same thing in every layer only when all layers have one centre.  The position-aware form of a static grid is the
+                                         world grid (po_set_world_occupancy, po_scene.use_world). */
     int    size_x, size_y;
     double resolution, pos_x, pos_y;  /* as po_occupancy */
 } po_obstacle_lists;
@@ -407,6 +410,68 @@ int po_rasterize_batch(po_handle h, int M, const po_obstacle_lists *lists, const
 int po_rasterize_batch_device(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy, unsigned char *cells_out);  /* device pointers, on the stream */
 int po_set_map_stack_obstacles(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy);                           /* host pointers, synchronous */
 int po_set_map_stack_obstacles_device(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy);                    /* device pointers, on the stream */
+/* ---- the STATIC WORLD of the stack: a world grid on the handle and polygon rings (csrc/po_scene.hip) ----
+ * Two more sources of occupied cells in front of the distance transform.  (1) What a planner holds of its site is ONE large static occupancy grid; each layer of
+ * the stack is a window into it at pos_xy[k].  (2) The other half of what perception and HD maps deliver is a boundary: a free-space or drivable-area ring of tens to
+ * hundreds of vertices, non-convex, with everything outside it not drivable — and non-convex blobs such as building footprints.
+ *
+ * The world grid.  One static occupancy image of the whole site, kept on the handle's device until replaced.  Layout and convention of po_occupancy (0 = occupied,
+ * [size_y][size_x], x contiguous, centre pos_x / pos_y, its OWN resolution, which need not be the layers').  outside_occupied: what a layer cell whose centre falls
+ * outside the world is (0 = free, 1 = occupied).  world == NULL clears it.  The handle owns its copy (a grow-only block; when it has to grow, the stream is
+ * synchronised first): the caller's image may be reused as soon as the stream has passed the call (host entry: on return).  PO_ERR_INVALID: a NULL image, a size
+ * below 1, a resolution that is not positive and finite, a non-finite centre, outside_occupied not in {0, 1}.  Limits: 1 .. 16384 cells per side; beyond:
+ * PO_ERR_UNSUPPORTED.  po_debug_get "world_cells" returns size_x * size_y, or 0 when there is none.
+ *
+ * Definition (the bar is BIT equality, as for po_rasterize_batch).  The cell centre (px, py) of cell (i, j) of layer k is the one of po_rasterize_batch, unchanged.
+ * A cell is occupied when any of the following five clauses holds.  Every operation is one rounded IEEE double operation, nothing is contracted, and a comparison
+ * with a NaN is false.
+ *   base, obstacles   as po_rasterize_batch (DISC, POLY), on scene->lists.
+ *   world (only with use_world).  The world has wsx, wsy, wres, wpx, wpy;  lx = (double)wsx * wres, ly likewise.  This is grid_map's isInside and
+ *          getIndexFromPosition:  tx = -((px - wpx) - 0.5 * lx), ty likewise; the centre is inside <=> tx >= 0 && ty >= 0 && tx < lx && ty < ly;
+ *          ix = (int)(-(((px - 0.5 * lx) - wpx) / wres)), iy likewise (the conversion truncates).  Inside and 0 <= ix < wsx && 0 <= iy < wsy:
+ *          occupied <=> world[iy][ix] == 0.  Otherwise: occupied <=> outside_occupied.
+ *   SOLID rings       some SOLID ring the layer owns (shared or its own) CONTAINS the centre.
+ *   FREE rings        the layer owns at least one FREE ring and none of them CONTAINS the centre.
+ * CONTAINS is the even-odd rule with the cross product POLY uses, for a ring with n >= 3 vertices.  For every edge a -> b (the last one closing back to vertex 0):
+ *          straddles = (ay > py) != (by > py);   t = (bx - ax) * (py - ay) - (by - ay) * (px - ax);   right = (by > ay) ? (t > 0) : (t < 0).
+ * The ring contains the centre when the number of edges with straddles && right is odd.  Consequences: orientation does not matter; of an axis-aligned box the low
+ * edges belong to it and the high edges do not; a self-intersecting ring gets even-odd filling; a horizontal edge never counts.  Holes are not a ring attribute: use
+ * a FREE outer ring plus SOLID islands.
+ * Device entries cannot look at the arrays, so they read them clamped: start[] into [0, n_verts]; n_shared and first[] into [0, n_rings]; a ring with fewer than 3
+ * vertices is ignored and does not count as a FREE ring of the layer; a ring with more than PO_RING_MAX_VERTS is read as its first PO_RING_MAX_VERTS vertices, with
+ * the closing edge from the last of them to vertex 0; a ring whose flag is neither 0 nor 1 is ignored; first == NULL means no layer owns rings of its own.  A bad
+ * table rasterises wrongly.  It never reads outside verts, start, flags or the world block.
+ * Host entries refuse with PO_ERR_INVALID, before they touch the handle: a table that breaks an inequality stated at po_rings; a ring with fewer than 3 or more than
+ * PO_RING_MAX_VERTS vertices; a non-finite vertex; an unknown flag; first == NULL with n_shared != n_rings; anything po_rasterize_batch refuses.  Every entry refuses
+ * negative counts, a NULL array with a positive count, use_world not in {0, 1}, and use_world without a world on the handle.
+ * A scene with n_rings == 0 and use_world == 0 gives the bytes of po_rasterize_batch on scene->lists.
+ * po_set_map_stack_scene* = the scene rasteriser into the image block the handle owns, then the very sequence of po_set_map_stack_occupancy_device; the device entry
+ * keeps that entry's contract word for word (with the M and size the handle already holds it allocates nothing and does not synchronise, and "map_ptr" stays where it
+ * is; the same M keeps the assignment; a block that has to grow does so behind a synchronisation of the stream). */
+int po_set_world_occupancy(po_handle h, const po_occupancy *world, int outside_occupied);         /* host pointer, synchronous */
+int po_set_world_occupancy_device(po_handle h, const po_occupancy *world, int outside_occupied);  /* device pointer; copied into the handle's block on the stream */
+#define PO_WORLD_MAX_SIDE 16384
+#define PO_RING_SOLID 0      /* the ring's interior is occupied */
+#define PO_RING_FREE  1      /* free space: a layer that owns FREE rings is occupied wherever none of them contains the cell */
+#define PO_RING_MAX_VERTS 4096
+typedef struct po_rings {
+    const double *verts;   /* [n_verts][2]: x, y, world frame */
+    const int    *start;   /* [n_rings + 1], start[0] = 0, non-decreasing, start[n_rings] <= n_verts: ring r owns verts[start[r] .. start[r+1]) */
+    const int    *flags;   /* [n_rings]: PO_RING_SOLID / PO_RING_FREE */
+    int n_rings, n_verts;
+    int n_shared;          /* rings [0, n_shared) belong to EVERY layer (the static world: drivable area, buildings) */
+    const int    *first;   /* NULL (then n_shared == n_rings) or [M + 1], first[0] == n_shared, non-decreasing, first[M] <= n_rings:
+                              layer k also owns rings [first[k], first[k+1]) */
+} po_rings;
+typedef struct po_scene {
+    po_obstacle_lists lists;   /* exactly as today: layer geometry, discs / convex polygons, base */
+    po_rings          rings;   /* n_rings == 0: none (the other fields are not looked at) */
+    int               use_world;  /* 1: the handle's world grid contributes; PO_ERR_INVALID when none is installed */
+} po_scene;
+int po_rasterize_scene_batch(po_handle h, int M, const po_scene *scene, const double *pos_xy, unsigned char *cells_out);         /* host pointers, synchronous */
+int po_rasterize_scene_batch_device(po_handle h, int M, const po_scene *scene, const double *pos_xy, unsigned char *cells_out);  /* device pointers, on the stream */
+int po_set_map_stack_scene(po_handle h, int M, const po_scene *scene, const double *pos_xy);                                     /* host pointers, synchronous */
+int po_set_map_stack_scene_device(po_handle h, int M, const po_scene *scene, const double *pos_xy);                              /* device pointers, on the stream */
 /* For every path: walk the optimised states in order and stop at the first state that fails
  * CollisionChecker::isSingleStateCollisionFreeImproved (src/tools/collision_checker.cpp:42-59: bounding circle, then the
  * six footprint circles of src/tools/car_geometry.cpp:38-72; outside the map = collision).
@@ -601,7 +666,8 @@ const char *po_last_hip_error(void);
  * po_distance_map_batch*, po_set_map_occupancy*, po_get_map, po_debug_get "map_ptr").  The map-stack entries
  * (po_set_map_stack*, po_set_map_assignment*, po_get_map_layer, po_map_sample_layer, po_debug_get "map_layers") were ADDED under 7: no struct layout, no existing
  * entry and no field's meaning changed, so a binding written against 7 drives this library unchanged; one that needs the new entries looks the symbols up.  The
- * obstacle-list entries (po_obstacle, po_obstacle_lists, po_rasterize_batch*, po_set_map_stack_obstacles*) were added under 7 by the same rule.  A binding should compare
+ * obstacle-list entries (po_obstacle, po_obstacle_lists, po_rasterize_batch*, po_set_map_stack_obstacles*) and the static-world entries (po_rings, po_scene, po_set_world_occupancy*, po_rasterize_scene_batch*, po_set_map_stack_scene*,
+ * po_debug_get "world_cells") were added under 7 by the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7
 const char *po_version(void);

@@ -57,6 +57,18 @@ class PoObstacleLists(C.Structure):
                 ("size_x", C.c_int), ("size_y", C.c_int), ("resolution", C.c_double), ("pos_x", C.c_double), ("pos_y", C.c_double)]
 
 
+PO_RING_SOLID, PO_RING_FREE, PO_RING_MAX_VERTS, PO_WORLD_MAX_SIDE = 0, 1, 4096, 16384
+
+
+class PoRings(C.Structure):
+    _fields_ = [("verts", C.c_void_p), ("start", C.c_void_p), ("flags", C.c_void_p), ("n_rings", C.c_int), ("n_verts", C.c_int), ("n_shared", C.c_int),
+                ("first", C.c_void_p)]
+
+
+class PoScene(C.Structure):
+    _fields_ = [("lists", PoObstacleLists), ("rings", PoRings), ("use_world", C.c_int)]
+
+
 class PoInfo(C.Structure):
     _fields_ = [("status", C.c_int), ("iters", C.c_int), ("n_refactor", C.c_int), ("status_polish", C.c_int),
                 ("r_prim", C.c_double), ("r_dual", C.c_double), ("rho", C.c_double), ("obj", C.c_double),

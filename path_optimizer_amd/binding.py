@@ -28,7 +28,9 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_distance_map_batch", "po_distance_map_batch_device", "po_set_map_occupancy", "po_set_map_occupancy_device", "po_get_map",
            "po_set_map_stack", "po_set_map_stack_occupancy", "po_set_map_stack_occupancy_device", "po_set_map_assignment", "po_set_map_assignment_device",
            "po_get_map_layer", "po_map_sample_layer",
-           "po_rasterize_batch", "po_rasterize_batch_device", "po_set_map_stack_obstacles", "po_set_map_stack_obstacles_device"]
+           "po_rasterize_batch", "po_rasterize_batch_device", "po_set_map_stack_obstacles", "po_set_map_stack_obstacles_device",
+           "po_set_world_occupancy", "po_set_world_occupancy_device", "po_rasterize_scene_batch", "po_rasterize_scene_batch_device",
+           "po_set_map_stack_scene", "po_set_map_stack_scene_device"]
 
 
 class PoError(RuntimeError):
@@ -85,6 +87,12 @@ def lib():
         L.po_rasterize_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_set_map_stack_obstacles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.po_set_map_stack_obstacles_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_set_world_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.po_set_world_occupancy_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.po_rasterize_scene_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_rasterize_scene_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_set_map_stack_scene.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_set_map_stack_scene_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -178,6 +186,23 @@ def pack_obstacles(layers):
             obs[n] = o
             n += 1
     return obs, first
+
+
+def pack_rings(shared, layers=None):
+    """Rings -> the arrays of po_rings: (verts [n_verts, 2] float64, start [n_rings + 1] int32, flags [n_rings] int32, n_shared, first [M + 1] int32 or None).
+    shared: a list of (xy array [n, 2], flag) every layer owns; layers: None, or M lists of (xy, flag), the rings of each layer alone.  flag is abi.PO_RING_SOLID or
+    abi.PO_RING_FREE.  Converted, not checked: the library checks."""
+    rings = list(shared) + ([] if layers is None else [r for l in layers for r in l])
+    xy = [np.asarray(r[0], dtype=np.float64).reshape(-1, 2) for r in rings]
+    start = np.zeros(len(rings) + 1, dtype=np.int32)
+    start[1:] = np.cumsum([len(v) for v in xy])
+    verts = np.concatenate(xy) if xy else np.zeros((0, 2))
+    flags = np.array([int(r[1]) for r in rings], dtype=np.int32)
+    first = None
+    if layers is not None:
+        first = np.full(len(layers) + 1, len(shared), dtype=np.int32)
+        first[1:] += np.cumsum([len(l) for l in layers]).astype(np.int32)
+    return np.ascontiguousarray(verts, dtype=np.float64), start, flags, len(shared), first
 
 
 def _i32(a):
@@ -465,6 +490,97 @@ class Engine:
         Tensors as rasterize_batch_device."""
         M, ls, pos = self._device_lists(obs, first, int(size_x), int(size_y), resolution, pos_xy, pos_x, pos_y, base)
         _check(lib().po_set_map_stack_obstacles_device(self._h, M, C.byref(ls), pos))
+
+    # ---- the static world: a world grid on the handle and polygon rings (po_scene.hip; DESIGN.md section 21) ----
+    def set_world_occupancy(self, world, resolution, pos_x=0.0, pos_y=0.0, outside_occupied=False):
+        """Install the site's static occupancy grid world[size_x, size_y] (0 = occupied; its own resolution and centre) on the handle; None clears it.  Scene
+        calls with use_world=True read it: a layer cell is occupied when the world cell under its centre is, or, outside the world, when outside_occupied."""
+        from .abi import PoOccupancy
+
+        if world is None:
+            _check(lib().po_set_world_occupancy(self._h, None, 0))
+            return
+        w = np.asfortranarray(self._occ_u8(world))
+        if w.ndim != 2:
+            raise ValueError("world must be [size_x, size_y]")
+        oc = PoOccupancy(w.ctypes.data_as(C.c_void_p), w.shape[0], w.shape[1], float(resolution), float(pos_x), float(pos_y))
+        _check(lib().po_set_world_occupancy(self._h, C.byref(oc), int(bool(outside_occupied))))
+
+    def set_world_occupancy_device(self, world, resolution, pos_x=0.0, pos_y=0.0, outside_occupied=False):
+        """Device-pointer entry: world is a CONTIGUOUS torch uint8 tensor [size_y, size_x] on the handle's device (x contiguous), copied into the handle's block
+        on the stream; it must stay alive until the stream has passed the call."""
+        from .abi import PoOccupancy
+
+        if world.dim() != 2 or str(world.dtype) != "torch.uint8" or not world.is_contiguous():
+            raise ValueError("world must be a contiguous 2-d torch.uint8 tensor [size_y, size_x]")
+        oc = PoOccupancy(C.c_void_p(world.data_ptr()), int(world.shape[1]), int(world.shape[0]), float(resolution), float(pos_x), float(pos_y))
+        _check(lib().po_set_world_occupancy_device(self._h, C.byref(oc), int(bool(outside_occupied))))
+
+    def _host_scene(self, layers, rings, use_world, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base):
+        """(M, PoScene, pos array, the arrays the struct points into): host pointers.  rings: None, or what pack_rings returns."""
+        from .abi import PoRings, PoScene
+
+        M, ls, pos, keep = self._host_lists(layers, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base)
+        rg = PoRings()
+        if rings is not None:
+            verts = np.ascontiguousarray(rings[0], dtype=np.float64).reshape(-1, 2)
+            start, flags = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in rings[1:3])
+            first = _i32(rings[4])
+            if len(start) != len(flags) + 1 or (first is not None and first.shape != (M + 1,)):
+                raise ValueError("rings: start must be [n_rings + 1], flags [n_rings] and first None or [M + 1]")
+            rg = PoRings(_np(verts), _np(start), _np(flags), len(flags), len(verts), int(rings[3]), _np(first))
+            keep = keep + (verts, start, flags, first)
+        return M, PoScene(ls, rg, int(bool(use_world))), pos, keep
+
+    def rasterize_scene_batch(self, layers, rings, size_x, size_y, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0, base=None, use_world=False):
+        """rasterize_batch plus the static world: rings (pack_rings(shared, per_layer) or None) and, with use_world, the handle's world grid.  uint8
+        [M, size_x, size_y], 0 = occupied, 255 = free; the handle's map is not touched."""
+        M, sc, pos, keep = self._host_scene(layers, rings, use_world, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base)
+        out = np.empty((M, size_y, size_x), dtype=np.uint8)
+        _check(lib().po_rasterize_scene_batch(self._h, M, C.byref(sc), _np(pos), _np(out)))
+        return out.transpose(0, 2, 1)
+
+    def set_map_stack_scene(self, layers, rings, size_x, size_y, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0, base=None, use_world=False):
+        """Build the stack from M scenes: rasterised and transformed on the device.  Layers bit-identical to set_map_stack_occupancy(rasterize_scene_batch(...))."""
+        M, sc, pos, keep = self._host_scene(layers, rings, use_world, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base)
+        _check(lib().po_set_map_stack_scene(self._h, M, C.byref(sc), _np(pos)))
+
+    def _device_scene(self, obs, first, rings, use_world, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base):
+        """rings: None or (verts float64 [n_verts, 2], start int32 [n_rings + 1], flags int32 [n_rings], n_shared, first int32 [M + 1] or None), contiguous torch
+        tensors on the handle's device.  The tables are NOT validated (the kernel reads them clamped)."""
+        from .abi import PoRings, PoScene
+
+        M, ls, pos = self._device_lists(obs, first, size_x, size_y, resolution, pos_xy, pos_x, pos_y, base)
+        rg = PoRings()
+        if rings is not None:
+            verts, start, flags, n_shared, rfirst = rings
+            if not hasattr(verts, "data_ptr") or str(verts.dtype) != "torch.float64" or verts.dim() != 2 or verts.shape[1] != 2 or not verts.is_contiguous():
+                raise ValueError("rings: verts must be a contiguous torch.float64 tensor [n_verts, 2]")
+            def i32_ok(a, n=None):
+                return hasattr(a, "data_ptr") and a.dim() == 1 and str(a.dtype) == "torch.int32" and a.is_contiguous() and (n is None or int(a.shape[0]) == n)
+
+            if not i32_ok(start) or int(start.shape[0]) < 1:
+                raise ValueError("rings: start must be a contiguous torch.int32 tensor [n_rings + 1]")
+            if not i32_ok(flags, int(start.shape[0]) - 1) or (rfirst is not None and not i32_ok(rfirst, M + 1)):
+                raise ValueError("rings: flags must be a contiguous torch.int32 tensor [n_rings] and first None or one of [M + 1]")
+            rg = PoRings(C.c_void_p(verts.data_ptr()) if verts.shape[0] else None, C.c_void_p(start.data_ptr()), C.c_void_p(flags.data_ptr()) if flags.shape[0] else None,
+                         int(flags.shape[0]), int(verts.shape[0]), int(n_shared), None if rfirst is None else C.c_void_p(rfirst.data_ptr()))
+        return M, PoScene(ls, rg, int(bool(use_world))), pos
+
+    def rasterize_scene_batch_device(self, obs, first, rings, out, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0, base=None, use_world=False):
+        """Device-pointer entry, enqueued on the handle's stream: rasterize_batch_device plus rings (see _device_scene) and the handle's world grid."""
+        if str(out.dtype) != "torch.uint8" or out.dim() != 3 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous torch.uint8 tensor [M, size_y, size_x]")
+        sy, sx = int(out.shape[1]), int(out.shape[2])
+        M, sc, pos = self._device_scene(obs, first, rings, use_world, sx, sy, resolution, pos_xy, pos_x, pos_y, base)
+        if int(out.shape[0]) != M:
+            raise ValueError("out must hold M = len(first) - 1 images")
+        _check(lib().po_rasterize_scene_batch_device(self._h, M, C.byref(sc), pos, C.c_void_p(out.data_ptr())))
+
+    def set_map_stack_scene_device(self, obs, first, rings, size_x, size_y, resolution, pos_xy=None, pos_x=0.0, pos_y=0.0, base=None, use_world=False):
+        """Device-pointer entry, enqueued on the handle's stream (no synchronisation and no allocation when M and the size are those the handle holds)."""
+        M, sc, pos = self._device_scene(obs, first, rings, use_world, int(size_x), int(size_y), resolution, pos_xy, pos_x, pos_y, base)
+        _check(lib().po_set_map_stack_scene_device(self._h, M, C.byref(sc), pos))
 
     def set_map_assignment(self, layer_of):
         """layer_of[b] = the layer instance b of every map-reading batch call reads (validated: outside [0, M) raises and the previous table stays); None or

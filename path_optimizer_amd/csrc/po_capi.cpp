@@ -203,6 +203,10 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
         *value = h->maps.d ? h->maps.M : 0;
         return PO_OK;
     }
+    if (k == "world_cells") {  // the size of the handle's world grid (0: none); no device call
+        *value = h->world.cells ? (long long)h->world.size_x * (long long)h->world.size_y : 0;
+        return PO_OK;
+    }
     if (k == "fixed_length_used") {  // did the last solve run the length-specialised kernels (1) or the generic ones (0)?  no device call
         *value = h->fixed_used;
         return PO_OK;
@@ -949,6 +953,172 @@ int po_set_map_stack_obstacles(po_handle h, int M, const po_obstacle_lists *list
     PO_TRY(po_set_map_stack_obstacles_device(h, M, &dev, d.pos));
     std::lock_guard<std::mutex> g(h->mu);
     return S.copy_out(h);  // (no output: the synchronise alone) the caller's lists may be reused, the stack is in place
+}
+
+// ---- the static world: a world grid on the handle, polygon rings (po_scene.hip) --------------------------------
+static int check_world(po_handle h, const po_occupancy *w, int outside_occupied) {
+    if (!h || (outside_occupied != 0 && outside_occupied != 1)) return PO_ERR_INVALID;
+    if (!w) return PO_OK;  // clears
+    if (!w->cells || w->size_x < 1 || w->size_y < 1 || !(w->resolution > 0) || !std::isfinite(w->resolution) || !std::isfinite(w->pos_x) || !std::isfinite(w->pos_y))
+        return PO_ERR_INVALID;
+    if (w->size_x > PO_WORLD_MAX_SIDE || w->size_y > PO_WORLD_MAX_SIDE) return PO_ERR_UNSUPPORTED;
+    return PO_OK;
+}
+// The image into the handle's block, on the stream (h->mu held): launches already enqueued that read the old world run before the copy
+static int install_world(po_handle h, const po_occupancy *w, int outside_occupied, hipMemcpyKind kind) {
+    if (!w) {  // (the block stays: launches already enqueued got its address by value)
+        h->world = po_occupancy{};
+        return PO_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t bytes = (size_t)w->size_x * (size_t)w->size_y;
+    if (bytes > h->world_buf.cap) h->world.cells = nullptr;  // the old image is about to be released: no world until the new one is in place
+    if (int rc = grow_after_sync(h, h->world_buf, bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(h->world_buf.p, w->cells, bytes, kind, h->stream));
+    h->world = *w;
+    h->world.cells = static_cast<const unsigned char *>(h->world_buf.p);
+    h->world_outside = outside_occupied;
+    return PO_OK;
+}
+
+int po_set_world_occupancy_device(po_handle h, const po_occupancy *world, int outside_occupied) {
+    if (int rc = check_world(h, world, outside_occupied)) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    return install_world(h, world, outside_occupied, hipMemcpyDeviceToDevice);
+}
+
+int po_set_world_occupancy(po_handle h, const po_occupancy *world, int outside_occupied) {
+    if (int rc = check_world(h, world, outside_occupied)) return rc;
+    std::lock_guard<std::mutex> call(h->call_mu);
+    std::lock_guard<std::mutex> g(h->mu);
+    PO_TRY(install_world(h, world, outside_occupied, hipMemcpyHostToDevice));
+    if (world) HIP_TRY(hipStreamSynchronize(h->stream));  // the caller's image may be reused
+    return PO_OK;
+}
+
+// What every scene entry can check without reading through a pointer of the struct (testable without a GPU); the handle is not looked at before the struct
+static int check_scene(po_handle h, int M, const po_scene *S) {
+    if (!h || !S) return PO_ERR_INVALID;
+    if (int rc = check_lists(h, M, &S->lists)) return rc;
+    const po_rings &R = S->rings;
+    if (R.n_rings < 0 || (R.n_rings > 0 && (R.n_verts < 0 || !R.start || !R.flags || (R.n_verts > 0 && !R.verts)))) return PO_ERR_INVALID;
+    if (S->use_world != 0 && S->use_world != 1) return PO_ERR_INVALID;
+    return PO_OK;
+}
+// The host entries read the tables themselves: everything the device entries can only clamp is refused here, before the handle is touched
+static int check_scene_contents(int M, const po_scene *S) {
+    if (int rc = check_list_contents(M, &S->lists)) return rc;
+    const po_rings &R = S->rings;
+    if (R.n_rings == 0) return PO_OK;
+    if (R.start[0] != 0) return PO_ERR_INVALID;
+    for (int r = 0; r < R.n_rings; ++r) {
+        const long long n = (long long)R.start[r + 1] - (long long)R.start[r];
+        if (n < 3 || n > PO_RING_MAX_VERTS) return PO_ERR_INVALID;  // (also: start[] non-decreasing)
+        if (R.flags[r] != PO_RING_SOLID && R.flags[r] != PO_RING_FREE) return PO_ERR_INVALID;
+    }
+    if (R.start[R.n_rings] > R.n_verts) return PO_ERR_INVALID;
+    for (size_t i = 0; i < 2 * (size_t)R.n_verts; ++i)
+        if (!std::isfinite(R.verts[i])) return PO_ERR_INVALID;
+    if (R.n_shared < 0 || R.n_shared > R.n_rings) return PO_ERR_INVALID;
+    if (!R.first) return R.n_shared == R.n_rings ? PO_OK : PO_ERR_INVALID;
+    if (R.first[0] != R.n_shared) return PO_ERR_INVALID;
+    for (int k = 0; k < M; ++k)
+        if (R.first[k + 1] < R.first[k]) return PO_ERR_INVALID;
+    if (R.first[M] > R.n_rings) return PO_ERR_INVALID;
+    return PO_OK;
+}
+// The device copy of a host scene: the staged arrays in place of the caller's
+struct StagedScene {
+    StagedLists lists;
+    Slot<double> verts;
+    Slot<int> start, flags, first;
+    void declare(Stage &S, int M, const po_scene *sc, const double *pos_xy) {
+        lists.declare(S, M, &sc->lists, pos_xy);
+        const po_rings &R = sc->rings;
+        if (R.n_rings == 0) return;
+        verts = S.in(R.n_verts > 0 ? R.verts : nullptr, 2 * (size_t)R.n_verts);
+        start = S.in(R.start, (size_t)R.n_rings + 1);
+        flags = S.in(R.flags, (size_t)R.n_rings);
+        first = S.in(R.first, (size_t)M + 1);
+    }
+    po_scene device(const po_scene *sc) const {
+        po_scene d = *sc;
+        d.lists = lists.device(&sc->lists);
+        d.rings.verts = verts; d.rings.start = start; d.rings.flags = flags; d.rings.first = first;
+        return d;
+    }
+};
+// scene -> M images at `cells` on the device (h->mu held, device set): po_raster.hip's image of the lists, then the world and the rings ORed into it
+static int scene_images(po_handle h, int M, const po_scene *S, const double *pos_xy, unsigned char *cells) {
+    HIP_TRY(po_launch_raster(&S->lists, M, pos_xy, cells, h->stream));
+    if (S->rings.n_rings == 0 && !S->use_world) return PO_OK;  // nothing to add: the bytes of po_rasterize_batch
+    po_scene sc = *S;
+    if (sc.rings.n_rings == 0) sc.rings = po_rings{};
+    HIP_TRY(po_launch_scene(&sc, M, pos_xy, S->use_world ? &h->world : nullptr, h->world_outside, cells, h->stream));
+    return PO_OK;
+}
+static bool world_missing(po_handle h, const po_scene *S) { return S->use_world && !h->world.cells; }  // (h->mu held)
+
+int po_rasterize_scene_batch_device(po_handle h, int M, const po_scene *scene, const double *pos_xy, unsigned char *cells_out) {
+    if (int rc = check_scene(h, M, scene)) return rc;
+    if (!cells_out) return PO_ERR_INVALID;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (world_missing(h, scene)) return PO_ERR_INVALID;
+    HIP_TRY(hipSetDevice(h->device));
+    return scene_images(h, M, scene, pos_xy, cells_out);
+}
+
+int po_rasterize_scene_batch(po_handle h, int M, const po_scene *scene, const double *pos_xy, unsigned char *cells_out) {
+    if (int rc = check_scene(h, M, scene)) return rc;
+    if (!cells_out) return PO_ERR_INVALID;
+    if (int rc = check_scene_contents(M, scene)) return rc;
+    Stage S;
+    StagedScene d;
+    d.declare(S, M, scene, pos_xy);
+    const Slot<unsigned char> d_cells = S.out(cells_out, (size_t)M * (size_t)scene->lists.size_x * (size_t)scene->lists.size_y);
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        if (world_missing(h, scene)) return PO_ERR_INVALID;  // (nothing has been touched)
+        HIP_TRY(hipSetDevice(h->device));
+        PO_TRY(S.upload(h, h->edt_io, true));
+    }
+    const po_scene dev = d.device(scene);
+    PO_TRY(po_rasterize_scene_batch_device(h, M, &dev, d.lists.pos, d_cells));
+    std::lock_guard<std::mutex> g(h->mu);
+    return S.copy_out(h);
+}
+
+int po_set_map_stack_scene_device(po_handle h, int M, const po_scene *scene, const double *pos_xy) {
+    if (int rc = check_scene(h, M, scene)) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (world_missing(h, scene)) return PO_ERR_INVALID;
+    HIP_TRY(hipSetDevice(h->device));
+    const po_obstacle_lists &L = scene->lists;
+    // the images live in a grow-only block of the handle: with the M and size it already holds nothing is allocated and nothing waits
+    if (int rc = grow_after_sync(h, h->raster_buf, (size_t)M * (size_t)L.size_x * (size_t)L.size_y)) return rc;
+    unsigned char *cells = static_cast<unsigned char *>(h->raster_buf.p);
+    PO_TRY(scene_images(h, M, scene, pos_xy, cells));
+    return stack_from_images(h, M, cells, L.size_x, L.size_y, L.resolution, L.pos_x, L.pos_y, pos_xy);
+}
+
+int po_set_map_stack_scene(po_handle h, int M, const po_scene *scene, const double *pos_xy) {
+    if (int rc = check_scene(h, M, scene)) return rc;
+    if (int rc = check_scene_contents(M, scene)) return rc;
+    Stage S;  // the lists, the ring tables, pos_xy and the base: the images never exist on the host
+    StagedScene d;
+    d.declare(S, M, scene, pos_xy);
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and the final synchronisation are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        if (world_missing(h, scene)) return PO_ERR_INVALID;  // (nothing has been touched)
+        HIP_TRY(hipSetDevice(h->device));
+        PO_TRY(S.upload(h, h->edt_io, true));
+    }
+    const po_scene dev = d.device(scene);
+    PO_TRY(po_set_map_stack_scene_device(h, M, &dev, d.lists.pos));
+    std::lock_guard<std::mutex> g(h->mu);
+    return S.copy_out(h);  // (no output: the synchronise alone) the caller's tables may be reused, the stack is in place
 }
 
 int po_get_map_layer(po_handle h, int k, po_map *geometry_out, float *distance_or_null) {

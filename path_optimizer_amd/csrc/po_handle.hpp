@@ -116,6 +116,11 @@ struct po_handle_s {
     //          last read-back has been synchronised, so staging, launch and read-back of one call are atomic with respect to every other call on the handle.
     std::mutex mu;
     std::mutex call_mu;
+    // The world grid: one static occupancy image of the site in world_buf; world.cells == nullptr until one is set.  The scene entries read it.
+    // (Declared last: no member the solve or the map stages read has moved.)
+    DevBuf world_buf;
+    po_occupancy world{};
+    int world_outside = 0;
 };
 
 // A grow-only block that launches already enqueued on the handle's stream may still read: they are finished before the old block is released.  (h->mu held.)

@@ -1,7 +1,7 @@
 // po_launch.hpp — every internal entry of libpo_hip.so that one translation unit defines and another calls, declared ONCE.  These functions have C linkage: no
 // name mangling, so a prototype that drifts from its definition would link and pass garbage.  Both sides include this header — the file that defines an entry and
 // every file that calls it — which turns such a drift into a compile error (conflicting declaration).  A new entry gets its prototype here and nowhere else.
-// Declarations only (forward-declared structs): po_edt.hip and po_raster.hip, which share no header with the solve kernels, include it too.
+// Declarations only (forward-declared structs): po_edt.hip, po_raster.hip and po_scene.hip, which share no header with the solve kernels, include it too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -96,4 +96,7 @@ int po_edt_max_images(void);
 
 // ---- po_raster.hip: per-layer obstacle lists -> occupancy images (every pointer, those inside *lists too, is a device pointer) ----
 hipError_t po_launch_raster(const po_obstacle_lists *lists, int M, const double *pos_xy, unsigned char *out, hipStream_t st);
+
+// ---- po_scene.hip: the world grid and the rings of *scene ORed into po_launch_raster's image of scene->lists (device pointers; world == nullptr: no world clause) ----
+hipError_t po_launch_scene(const po_scene *scene, int M, const double *pos_xy, const po_occupancy *world, int outside_occupied, unsigned char *img, hipStream_t st);
 }  // extern "C"

@@ -11,6 +11,10 @@
 //   — new —                                                            Obstacle::disc / box / polygon and MapStack::fromObstacles: the stack from per-layer
 //                                                                        obstacle lists over an optional static grid, rasterised on the device
 //                                                                        (po_set_map_stack_obstacles)
+//   — new —                                                            Ring::solid / free, World and MapStack::fromScene: the static world — polygon rings of
+//                                                                        any shape (drivable area, footprints) and the site's static grid, which each
+//                                                                        layer windows at its own centre (po_set_world_occupancy, po_set_map_stack_scene;
+//                                                                        DESIGN.md section 21)
 //   CollisionChecker::isSingleStateCollisionFreeImproved(State)         same name; checkPaths(): the batched tail of optimizePath
 //     (src/tools/collision_checker.cpp)                                   (po_postcheck_batch)
 //
@@ -85,6 +89,38 @@ struct Obstacle {
     }
 };
 
+// A polygon ring of any shape with 3 .. PO_RING_MAX_VERTS vertices (x, y), world frame, either orientation, filled by the even-odd rule.  solid: its interior is
+// occupied (a building footprint, a clustered obstacle).  free: free space (a drivable-area boundary) — a layer that owns free rings is occupied wherever none of
+// them contains the cell.
+struct Ring {
+    std::vector<std::pair<double, double>> vertices;
+    int flag;
+    static Ring solid(std::vector<std::pair<double, double>> v) { return make(std::move(v), PO_RING_SOLID); }
+    static Ring free(std::vector<std::pair<double, double>> v) { return make(std::move(v), PO_RING_FREE); }
+ private:
+    static Ring make(std::vector<std::pair<double, double>> v, int flag) {
+        if (v.size() < 3 || v.size() > PO_RING_MAX_VERTS) throw std::invalid_argument("Ring: 3 .. 4096 vertices");
+        return Ring{std::move(v), flag};
+    }
+};
+
+// The site's static occupancy grid on the engine ([size_y][size_x] bytes, x contiguous, 0 = occupied; its own resolution and centre), kept until replaced or
+// cleared.  Every MapStack::fromScene(..., use_world = true) on that engine reads it: each layer is a window into it at the layer's own centre.
+class World {
+ public:
+    World(const unsigned char *occupancy, int size_x, int size_y, double resolution, double pos_x, double pos_y, bool outside_occupied, PoEngine *engine = nullptr)
+        : engine_(engine ? engine : &PoEngine::instance()) {
+        po_occupancy o{occupancy, size_x, size_y, resolution, pos_x, pos_y};
+        const int rc = po_set_world_occupancy(engine_->handle(), &o, outside_occupied ? 1 : 0);
+        if (rc != PO_OK) throw std::runtime_error(std::string("po_set_world_occupancy: ") + po_strerror(rc));
+    }
+    void clear() const { (void)po_set_world_occupancy(engine_->handle(), nullptr, 0); }
+    long long cells() const { long long n = 0; (void)po_debug_get(engine_->handle(), "world_cells", &n); return n; }
+    PoEngine *engine() const { return engine_; }
+ private:
+    PoEngine *engine_;
+};
+
 // M obstacle-distance layers of one size and resolution on one engine: one local grid per vehicle, per perception hypothesis, per scene.  Layer k is centred at
 // pos_xy[2k], pos_xy[2k + 1].  Which layer instance b of a batched call reads is the engine's assignment (setAssignment); without one every instance reads layer 0.
 // Installing a MapStack replaces the engine's Map and the other way round (an engine holds one stack; a Map is a stack of one).
@@ -122,6 +158,44 @@ class MapStack {
         MapStack st(engine ? engine : &PoEngine::instance(), M);
         const int rc = po_set_map_stack_obstacles(st.engine_->handle(), M, &ls, pos_xy.data());
         if (rc != PO_OK) throw std::runtime_error(std::string("po_set_map_stack_obstacles: ") + po_strerror(rc));
+        return st;
+    }
+    // fromObstacles plus the static world: `shared` rings belong to every layer, rings[k] to layer k alone (empty vector: no layer has rings of its own); with
+    // use_world the engine's World contributes (po_set_map_stack_scene).
+    static MapStack fromScene(const std::vector<std::vector<Obstacle>> &layers, const std::vector<Ring> &shared, const std::vector<std::vector<Ring>> &rings,
+                              bool use_world, int size_x, int size_y, double resolution, const std::vector<double> &pos_xy, const unsigned char *base = nullptr,
+                              PoEngine *engine = nullptr) {
+        const int M = (int)layers.size();
+        if (pos_xy.size() != 2 * (size_t)M) throw std::invalid_argument("MapStack: pos_xy must hold M (x, y) pairs");
+        if (!rings.empty() && rings.size() != (size_t)M) throw std::invalid_argument("MapStack: rings must be empty or hold one list per layer");
+        std::vector<po_obstacle> obs;
+        std::vector<int> first(1, 0);
+        for (const auto &l : layers) {
+            for (const auto &ob : l) obs.push_back(ob.o);
+            first.push_back((int)obs.size());
+        }
+        std::vector<double> verts;
+        std::vector<int> start(1, 0), flags, rfirst;
+        const auto add = [&](const Ring &r) {
+            for (const auto &v : r.vertices) { verts.push_back(v.first); verts.push_back(v.second); }
+            start.push_back((int)(verts.size() / 2));
+            flags.push_back(r.flag);
+        };
+        for (const Ring &r : shared) add(r);
+        if (!rings.empty()) {
+            rfirst.push_back((int)flags.size());
+            for (const auto &l : rings) {
+                for (const Ring &r : l) add(r);
+                rfirst.push_back((int)flags.size());
+            }
+        }
+        po_scene sc{};
+        sc.lists = po_obstacle_lists{obs.data(), first.data(), (int)obs.size(), base, base ? 1 : 0, size_x, size_y, resolution, 0.0, 0.0};
+        sc.rings = po_rings{verts.data(), start.data(), flags.data(), (int)flags.size(), (int)(verts.size() / 2), (int)shared.size(), rfirst.empty() ? nullptr : rfirst.data()};
+        sc.use_world = use_world ? 1 : 0;
+        MapStack st(engine ? engine : &PoEngine::instance(), M);
+        const int rc = po_set_map_stack_scene(st.engine_->handle(), M, &sc, pos_xy.data());
+        if (rc != PO_OK) throw std::runtime_error(std::string("po_set_map_stack_scene: ") + po_strerror(rc));
         return st;
     }
     // layer_of[b] = the layer instance b reads; an index outside [0, M) throws and leaves the previous table in force.  Empty: every instance reads layer 0.
