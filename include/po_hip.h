@@ -637,6 +637,85 @@ typedef struct po_plan_out {
 int po_plan_batch(po_handle h, const po_plan_in *in, const po_plan_out *out);         /* host pointers, synchronous */
 int po_plan_batch_device(po_handle h, const po_plan_in *in, const po_plan_out *out);  /* device pointers; synchronises the stream once mid-way */
 
+/* ---- score and select: B candidate paths -> eight features and a cost each, one winner per group, the winners gathered (csrc/po_select.hip) ----
+ * The output side of "many hypotheses per call": po_plan_batch* leaves B paths in HBM; the caller wants one decision per vehicle.  A group is a contiguous range
+ * of candidates (the variants of one vehicle); the call scores every candidate against the map layer it was planned on, picks the cheapest feasible one of each
+ * group and copies the winners' rows out, so that G paths cross PCIe instead of B.  sel_states / sel_n have the layout of prev_states / prev_n: fed back unchanged
+ * in the next cycle they give the hysteresis feature (distance to last cycle's choice) without leaving the device.  The reference has no such stage.
+ *
+ * Map access.  Candidate b reads the layer every map stage reads for instance b (the assignment of po_set_map_assignment*, else layer 0).  The call needs a map and
+ * an assignment that covers B: PO_ERR_INVALID otherwise, as po_bounds_batch*.  The footprint is the six circles (cx_q, cy_q, cr_q) of the post-solve collision check
+ * (CarGeometry from po_params: rr, rl, fr, fl, fm, rm); its bounding circle is not used.
+ *
+ * Definition (the bar is BIT equality).  Every operation is one rounded IEEE double operation in the order written, nothing contracted; a comparison with a NaN is
+ * false; min(a, b) = b < a ? b : a; max(a, b) = b > a ? b : a.  n = n_states[b] clamped into [0, N] (N when NULL); row i = (x_i, y_i, z_i, k_i, s_i).
+ *   Per state i < n:   cz = pcos(z_i), sz = psin(z_i) (include/po_pmath.h);  for q = 0 .. 5:  gx = (cx_q * cz - cy_q * sz) + x_i,  gy = (cx_q * sz + cy_q * cz) + y_i,
+ *       c_iq = D(gx, gy) - cr_q with D = Map::getObstacleDistance on the candidate's layer (0 outside the map, so the clearance there is -cr_q);
+ *       c_i = c_i0, then c_i = min(c_i, c_iq) for q = 1 .. 5;   t = d_safe - c_i, t = t > 0 ? t : 0, p_i = t * t;   e_i: below.
+ *   Per interval i < n - 1, ds_i = s_{i+1} - s_i:
+ *       T1_i = (0.5 * (k_i * k_i + k_{i+1} * k_{i+1})) * ds_i          T2_i = ds_i > 0 ? ((k_{i+1} - k_i) * (k_{i+1} - k_i)) / ds_i : 0
+ *       T5_i = (0.5 * (p_i + p_{i+1})) * ds_i                          T7_i = (0.5 * (e_i + e_{i+1})) * ds_i
+ *   The fold F(op, init, v):  64 partials P_t = init;  for i ascending P_{i mod 64} = op(P_{i mod 64}, v_i);  then for h = 32, 16, 8, 4, 2, 1: P_t = op(P_t, P_{t+h})
+ *       for t < h;  the result is P_0.  It is fixed so that a path's features depend neither on the batch size nor on the path's position in the batch.
+ *   Features:  0 LENGTH = s_{n-1}    1 CURV = F(+, +0.0, T1)    2 CURV_RATE = F(+, +0.0, T2)    3 KMAX = F(max, +0.0, |k_i|)    4 CLR_MIN = F(min, DBL_MAX, c_i)
+ *       5 PROX = F(+, +0.0, T5)    6 GOAL = sqrt((x_{n-1} - gx) * (x_{n-1} - gx) + (y_{n-1} - gy) * (y_{n-1} - gy)) with (gx, gy) = goal[b][0 .. 1], 0 when goal is NULL
+ *       7 DEV_PREV = F(+, +0.0, T7).   n = 0: LENGTH = GOAL = 0 (the folds give 0, 0, 0, DBL_MAX, 0, 0).
+ *   e_i, the squared distance of state i to the previous path of the candidate's group g: np = prev_n[g] clamped into [0, Np] (Np when NULL), points (u_j, v_j) =
+ *       columns 0 and 1 of rows j < np of prev_states[g].  e_i = 0 for every i when prev_states is NULL, Np = 0, np < 2 or the candidate is in no group.  Otherwise,
+ *       for segment j = 0 .. np - 2:  dx = u_{j+1} - u_j, dy = v_{j+1} - v_j, px = x_i - u_j, py = y_i - v_j;  L2 = dx * dx + dy * dy, dot = px * dx + py * dy;
+ *       t = L2 > 0 ? dot / L2 : 0, then t = t < 0 ? 0 : t, then t = t > 1 ? 1 : t;  qx = px - t * dx, qy = py - t * dy, D_j = qx * qx + qy * qy;
+ *       e_i = D_0, then e_i = min(e_i, D_j) for j = 1 .. np - 2.  Np is not limited.
+ *   Feasible <=> ok[b] != 0 (NULL: 1), n >= 2, every value of rows < n is finite, all eight features are finite, CLR_MIN >= min_clearance, KMAX <= max_kmax,
+ *       GOAL <= max_goal_dist, and the cost below is finite.
+ *   cost = (((((((w0 * f0 + w1 * f1) + w2 * f2) + w3 * f3) + w4 * f4) + w5 * f5) + w6 * f6) + w7 * f7) of a feasible candidate, +infinity otherwise.
+ *   Selection: best[g] = the feasible candidate of group g with the smallest cost, the smallest index among equal costs; best_cost[g] its cost; n_feasible[g] how
+ *       many are feasible; sel_n[g] = its n, rows < n of sel_states[g] are bitwise its rows and the rest are zero.  No feasible candidate (or an empty group):
+ *       best = -1, best_cost = +infinity, n_feasible = 0, sel_n = 0, all rows zero.
+ * Groups.  group_start[G + 1]: group g = candidates [group_start[g], group_start[g+1]).  The host entry validates the table — non-decreasing, group_start[0] >= 0,
+ *   group_start[G] <= B, else PO_ERR_INVALID.  The device entry cannot: its kernels read gs'[0] = clamp(gs[0], 0, B), gs'[g+1] = clamp(max(gs[g+1], gs'[g]), 0, B)
+ *   (a small launch ahead of the two kernels writes gs' into the handle's scratch), and n_states / prev_n clamped where they are read: a bad table selects wrong
+ *   rows, never an address outside the buffers.  A candidate outside every group is scored and never selected; its e_i are 0.
+ * Return codes.  PO_ERR_INVALID: a NULL handle, struct or required pointer (B > 0 and G > 0: states, group_start, best; sel_n when sel_states is given; goal needs
+ *   goal_stride >= 2); a negative B, N, G; prev_states given with Np < 0; a non-finite weight; a NaN among d_safe, min_clearance, max_kmax, max_goal_dist; no map; an
+ *   assignment shorter than B.  B = 0 or G = 0: PO_OK, nothing is launched and nothing is written — this is decided after the argument checks above and BEFORE
+ *   the map and assignment rule, so an empty call is PO_OK on a handle without a map too.
+ * `p` is a host pointer in both entries.  cost goes to a block the handle owns when out->cost is NULL (the selection reads it).  Deterministic: no atomics.
+ * po_default_select_params: w = {1, 10, 10, 0, 0, 10, 5, 1}, d_safe = 0.5, min_clearance = 0, max_kmax = max_goal_dist = DBL_MAX — a starting point nobody has tuned. */
+enum { PO_FEAT_LENGTH = 0, PO_FEAT_CURV = 1, PO_FEAT_CURV_RATE = 2, PO_FEAT_KMAX = 3,
+       PO_FEAT_CLR_MIN = 4, PO_FEAT_PROX = 5, PO_FEAT_GOAL = 6, PO_FEAT_DEV_PREV = 7, PO_N_FEAT = 8 };
+typedef struct po_select_params {
+    double w[PO_N_FEAT];      /* cost weights, finite */
+    double d_safe;            /* proximity penalty starts below this clearance */
+    double min_clearance;     /* feasible iff CLR_MIN >= min_clearance */
+    double max_kmax;          /* feasible iff KMAX <= max_kmax */
+    double max_goal_dist;     /* feasible iff GOAL <= max_goal_dist */
+} po_select_params;
+void po_default_select_params(po_select_params *p);
+typedef struct po_select_in {
+    int B, N;                     /* candidates, rows per candidate (stride) */
+    const double *states;         /* [B][N][5] x, y, heading, k, s : po_plan_out.states / po_batch_out states */
+    const int    *n_states;       /* optional [B] (NULL: N) */
+    const int    *ok;             /* optional [B] (NULL: all 1) : po_plan_out.ok / po_postcheck ok */
+    const double *goal;           /* optional [B][goal_stride], x, y first : po_plan_in.goal */
+    int goal_stride;
+    int G;                        /* groups */
+    const int    *group_start;    /* [G+1]: group g = candidates [group_start[g], group_start[g+1]) */
+    int Np;                       /* rows per previous path (stride); 0: none */
+    const double *prev_states;    /* optional [G][Np][5]: last cycle's sel_states */
+    const int    *prev_n;         /* optional [G] (NULL: Np) : last cycle's sel_n */
+} po_select_in;
+typedef struct po_select_out {
+    double *feat;        /* optional [B][PO_N_FEAT] */
+    double *cost;        /* optional [B]; +inf = infeasible */
+    int    *best;        /* [G]: candidate index, -1 = no feasible candidate */
+    double *best_cost;   /* optional [G] */
+    int    *n_feasible;  /* optional [G] */
+    double *sel_states;  /* optional [G][N][5]: the winners' rows, zero beyond sel_n */
+    int    *sel_n;       /* [G] when sel_states is given */
+} po_select_out;
+int po_select_batch(po_handle h, const po_select_params *p, const po_select_in *in, const po_select_out *out);         /* host pointers, synchronous */
+int po_select_batch_device(po_handle h, const po_select_params *p, const po_select_in *in, const po_select_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -667,7 +746,8 @@ const char *po_last_hip_error(void);
  * (po_set_map_stack*, po_set_map_assignment*, po_get_map_layer, po_map_sample_layer, po_debug_get "map_layers") were ADDED under 7: no struct layout, no existing
  * entry and no field's meaning changed, so a binding written against 7 drives this library unchanged; one that needs the new entries looks the symbols up.  The
  * obstacle-list entries (po_obstacle, po_obstacle_lists, po_rasterize_batch*, po_set_map_stack_obstacles*) and the static-world entries (po_rings, po_scene, po_set_world_occupancy*, po_rasterize_scene_batch*, po_set_map_stack_scene*,
- * po_debug_get "world_cells") were added under 7 by the same rule.  A binding should compare
+ * po_debug_get "world_cells") and the score-and-select entries (po_select_params, po_select_in, po_select_out, po_default_select_params, po_select_batch*) were
+ * added under 7 by the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7
 const char *po_version(void);

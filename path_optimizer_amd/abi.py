@@ -122,3 +122,21 @@ class PoPlanIn(C.Structure):
 
 class PoPlanOut(C.Structure):
     _fields_ = [("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("stage", C.c_void_p), ("info", C.c_void_p)]
+
+
+# ---- score and select (po_select_batch*) ----
+PO_FEAT_LENGTH, PO_FEAT_CURV, PO_FEAT_CURV_RATE, PO_FEAT_KMAX, PO_FEAT_CLR_MIN, PO_FEAT_PROX, PO_FEAT_GOAL, PO_FEAT_DEV_PREV, PO_N_FEAT = 0, 1, 2, 3, 4, 5, 6, 7, 8
+
+
+class PoSelectParams(C.Structure):
+    _fields_ = [("w", C.c_double * PO_N_FEAT), ("d_safe", C.c_double), ("min_clearance", C.c_double), ("max_kmax", C.c_double), ("max_goal_dist", C.c_double)]
+
+
+class PoSelectIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("goal", C.c_void_p),
+                ("goal_stride", C.c_int), ("G", C.c_int), ("group_start", C.c_void_p), ("Np", C.c_int), ("prev_states", C.c_void_p), ("prev_n", C.c_void_p)]
+
+
+class PoSelectOut(C.Structure):
+    _fields_ = [("feat", C.c_void_p), ("cost", C.c_void_p), ("best", C.c_void_p), ("best_cost", C.c_void_p), ("n_feasible", C.c_void_p),
+                ("sel_states", C.c_void_p), ("sel_n", C.c_void_p)]

@@ -30,7 +30,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_get_map_layer", "po_map_sample_layer",
            "po_rasterize_batch", "po_rasterize_batch_device", "po_set_map_stack_obstacles", "po_set_map_stack_obstacles_device",
            "po_set_world_occupancy", "po_set_world_occupancy_device", "po_rasterize_scene_batch", "po_rasterize_scene_batch_device",
-           "po_set_map_stack_scene", "po_set_map_stack_scene_device"]
+           "po_set_map_stack_scene", "po_set_map_stack_scene_device",
+           "po_default_select_params", "po_select_batch", "po_select_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -93,6 +94,10 @@ def lib():
         L.po_rasterize_scene_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_set_map_stack_scene.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.po_set_map_stack_scene_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.po_default_select_params.argtypes = [C.c_void_p]
+        L.po_default_select_params.restype = None
+        L.po_select_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -109,6 +114,15 @@ def _check(rc: int):
 def default_params() -> PoParams:
     p = PoParams()
     lib().po_default_params(C.byref(p))
+    return p
+
+
+def default_select_params():
+    """po_default_select_params: the cost weights and thresholds of po_select_batch* (a starting point nobody has tuned)."""
+    from .abi import PoSelectParams
+
+    p = PoSelectParams()
+    lib().po_default_select_params(C.byref(p))
     return p
 
 
@@ -777,6 +791,43 @@ class Engine:
         pi = PoPlanIn(B, W, p(t, "n_way"), p(t, "way_x"), p(t, "way_y"), p(t, "start"), p(t, "goal"), float(max_length), N)
         po = PoPlanOut(p(out, "states"), p(out, "n_states"), p(out, "ok"), p(out, "stage"), p(out, "info"))
         _check(lib().po_plan_batch_device(self._h, C.byref(pi), C.byref(po)))
+
+    # ---- score and select: one winner per group of candidates ----
+    def select_batch(self, states, group_start, n_states=None, ok=None, goal=None, prev_states=None, prev_n=None, params=None, want_states=True):
+        """Host-pointer entry of po_select_batch.  states [B,N,5], group_start [G+1]; optional n_states [B], ok [B], goal [B,>=2], prev_states [G,Np,5], prev_n [G].
+        Returns a dict: feat [B,8], cost [B], best [G], best_cost [G], n_feasible [G], sel_states [G,N,5] and sel_n [G] (None without want_states)."""
+        from .abi import PO_N_FEAT, PoSelectIn, PoSelectOut
+
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        B, N = states.shape[0], states.shape[1]
+        gs = _i32(group_start).reshape(-1)
+        G = len(gs) - 1
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        gl, pv = f(goal), f(prev_states)
+        ns, okk, pn = _i32(n_states), _i32(ok), _i32(prev_n)
+        si = PoSelectIn(B, N, _np(states), _np(ns), _np(okk), _np(gl), 0 if gl is None else gl.shape[1], G, _np(gs), 0 if pv is None else pv.shape[1], _np(pv), _np(pn))
+        r = {"feat": np.zeros((B, PO_N_FEAT)), "cost": np.zeros(B), "best": np.zeros(G, dtype=np.int32), "best_cost": np.zeros(G),
+             "n_feasible": np.zeros(G, dtype=np.int32), "sel_states": np.zeros((G, N, 5)) if want_states else None,
+             "sel_n": np.zeros(G, dtype=np.int32) if want_states else None}
+        so = PoSelectOut(*[_np(r[k]) for k in ("feat", "cost", "best", "best_cost", "n_feasible", "sel_states", "sel_n")])
+        sp = params if params is not None else default_select_params()
+        _check(lib().po_select_batch(self._h, C.byref(sp), C.byref(si), C.byref(so)))
+        return r
+
+    def select_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: states [B,N,5] f64, group_start [G+1] i32 (+ n_states, ok, goal [B,stride], prev_states [G,Np,5], prev_n); out: best [G] i32
+        (+ feat [B,8], cost [B], best_cost [G], n_feasible [G], sel_states [G,N,5] with sel_n [G]).  Enqueued on the handle's stream, no synchronisation."""
+        from .abi import PoSelectIn, PoSelectOut
+
+        B, N = t["states"].shape[0], t["states"].shape[1]
+        G = t["group_start"].shape[0] - 1
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        gl, pv = t.get("goal"), t.get("prev_states")
+        si = PoSelectIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "goal"), 0 if gl is None else int(gl.stride(0)), G, p(t, "group_start"),
+                        0 if pv is None else int(pv.shape[1]), p(t, "prev_states"), p(t, "prev_n"))
+        so = PoSelectOut(*[p(out, k) for k in ("feat", "cost", "best", "best_cost", "n_feasible", "sel_states", "sel_n")])
+        sp = params if params is not None else default_select_params()
+        _check(lib().po_select_batch_device(self._h, C.byref(sp), C.byref(si), C.byref(so)))
 
     def map_sample(self, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)

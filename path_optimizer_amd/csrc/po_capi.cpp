@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <new>
 #include <string>
@@ -1211,6 +1212,90 @@ int po_postcheck_batch(po_handle h, int B, int N, const int *n_points, const dou
     PO_TRY(po_postcheck_batch_device(h, B, N, d_np, d_states, d_info, d_nvalid, d_ok));
     std::lock_guard<std::mutex> g(h->mu);
     return S.copy_out(h);
+}
+
+// ---- score and select --------------------------------------------------------------------------
+void po_default_select_params(po_select_params *p) {
+    if (!p) return;
+    const double w[PO_N_FEAT] = {1, 10, 10, 0, 0, 10, 5, 1};  // a starting point nobody has tuned
+    for (int j = 0; j < PO_N_FEAT; ++j) p->w[j] = w[j];
+    p->d_safe = 0.5;
+    p->min_clearance = 0.0;
+    p->max_kmax = std::numeric_limits<double>::max();
+    p->max_goal_dist = std::numeric_limits<double>::max();
+}
+
+static bool select_args_ok(po_handle h, const po_select_params *p, const po_select_in *in, const po_select_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0 || in->G < 0) return false;
+    for (int j = 0; j < PO_N_FEAT; ++j)
+        if (!std::isfinite(p->w[j])) return false;
+    if (std::isnan(p->d_safe) || std::isnan(p->min_clearance) || std::isnan(p->max_kmax) || std::isnan(p->max_goal_dist)) return false;
+    if (in->prev_states && in->Np < 0) return false;
+    if (in->B == 0 || in->G == 0) return true;
+    if (!in->states || !in->group_start || !out->best) return false;
+    if (in->goal && in->goal_stride < 2) return false;
+    return !out->sel_states || out->sel_n;
+}
+
+int po_select_batch_device(po_handle h, const po_select_params *p, const po_select_in *in, const po_select_out *out) {
+    if (!select_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0 || in->G == 0) return PO_OK;  // nothing to score or nothing to select: no launch, whatever the handle holds
+    std::lock_guard<std::mutex> g(h->mu);
+    if (!h->maps.d || !assignment_covers(h, in->B)) return PO_ERR_INVALID;  // po_set_map first; an assignment covers every candidate
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t gs_bytes = (sizeof(int) * ((size_t)in->G + 1) + 15) & ~(size_t)15;
+    PO_TRY(grow_after_sync(h, h->select_buf, gs_bytes + (out->cost ? 0 : sizeof(double) * (size_t)in->B)));
+    po::DevSelect D{};
+    D.B = in->B; D.N = in->N; D.G = in->G; D.goal_stride = in->goal_stride;
+    D.Np = in->prev_states && in->Np > 0 ? in->Np : 0;
+    D.states = in->states; D.n_states = in->n_states; D.ok = in->ok; D.goal = in->goal;
+    D.group_start = in->group_start;
+    D.prev_states = D.Np ? in->prev_states : nullptr; D.prev_n = in->prev_n;
+    for (int j = 0; j < PO_N_FEAT; ++j) D.w[j] = p->w[j];
+    D.d_safe = p->d_safe; D.min_clearance = p->min_clearance; D.max_kmax = p->max_kmax; D.max_goal_dist = p->max_goal_dist;
+    D.gs = static_cast<int *>(h->select_buf.p);
+    D.feat = out->feat;
+    D.cost = out->cost ? out->cost : reinterpret_cast<double *>(static_cast<char *>(h->select_buf.p) + gs_bytes);
+    D.best = out->best; D.best_cost = out->best_cost; D.n_feasible = out->n_feasible; D.sel_states = out->sel_states; D.sel_n = out->sel_n;
+    const po::DevCar car = make_car(h->params);
+    HIP_TRY(po_launch_select(&h->maps, &car, &D, h->stream));
+    return PO_OK;
+}
+
+int po_select_batch(po_handle h, const po_select_params *p, const po_select_in *in, const po_select_out *out) {
+    if (!select_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    const bool empty = in->B == 0 || in->G == 0;
+    if (!empty) {  // the table is in host memory here: validated (the device entry reads it clamped instead)
+        const int *gs = in->group_start;
+        if (gs[0] < 0 || gs[in->G] > in->B) return PO_ERR_INVALID;
+        for (int g = 0; g < in->G; ++g)
+            if (gs[g + 1] < gs[g]) return PO_ERR_INVALID;
+    }
+    const size_t B = in->B, G = in->G, N = in->N, Np = in->prev_states && in->Np > 0 ? in->Np : 0;
+    Stage S;
+    po_select_in d = *in;
+    po_select_out o{};
+    if (!empty) {
+        const Slot<double> states = S.in(in->states, 5 * B * N), goal = S.in(in->goal, B * (size_t)in->goal_stride), prev = S.in(Np ? in->prev_states : nullptr, 5 * G * Np);
+        const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), gs = S.in(in->group_start, G + 1), pn = S.in(Np ? in->prev_n : nullptr, G);
+        // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernels skip it
+        const Slot<double> feat = out->feat ? S.out(out->feat, PO_N_FEAT * B) : Slot<double>{}, cost = out->cost ? S.out(out->cost, B) : Slot<double>{};
+        const Slot<double> bc = out->best_cost ? S.out(out->best_cost, G) : Slot<double>{}, ss = out->sel_states ? S.out(out->sel_states, 5 * G * N) : Slot<double>{};
+        const Slot<int> best = S.out(out->best, G), nf = out->n_feasible ? S.out(out->n_feasible, G) : Slot<int>{}, sn = out->sel_n ? S.out(out->sel_n, G) : Slot<int>{};
+        std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
+        {
+            std::lock_guard<std::mutex> g(h->mu);
+            HIP_TRY(hipSetDevice(h->device));
+            PO_TRY(S.upload(h, h->post_buf));
+        }
+        d.states = states; d.goal = goal; d.prev_states = prev; d.n_states = ns; d.ok = ok; d.group_start = gs; d.prev_n = pn;
+        d.Np = (int)Np;
+        o = po_select_out{feat, cost, best, bc, nf, ss, sn};
+        PO_TRY(po_select_batch_device(h, p, &d, &o));
+        std::lock_guard<std::mutex> g(h->mu);
+        return S.copy_out(h);
+    }
+    return PO_OK;  // B = 0 or G = 0: nothing is staged, launched or written
 }
 
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------

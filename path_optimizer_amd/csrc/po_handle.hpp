@@ -121,6 +121,7 @@ struct po_handle_s {
     DevBuf world_buf;
     po_occupancy world{};
     int world_outside = 0;
+    DevBuf select_buf;  // score and select: the clamped group table [G + 1] and, when the caller wants no cost array, cost [B]
 };
 
 // A grow-only block that launches already enqueued on the handle's stream may still read: they are finished before the old block is released.  (h->mu held.)

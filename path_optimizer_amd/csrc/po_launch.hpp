@@ -10,7 +10,7 @@
 namespace po {
 struct DevBatch; struct DevParams;                                                   // po_device.hpp
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
-struct DevResample; struct PlanGate; struct PlanRows;
+struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
 
@@ -99,4 +99,7 @@ hipError_t po_launch_raster(const po_obstacle_lists *lists, int M, const double 
 
 // ---- po_scene.hip: the world grid and the rings of *scene ORed into po_launch_raster's image of scene->lists (device pointers; world == nullptr: no world clause) ----
 hipError_t po_launch_scene(const po_scene *scene, int M, const double *pos_xy, const po_occupancy *world, int outside_occupied, unsigned char *img, hipStream_t st);
+
+// ---- po_select.hip: score and select (the clamped group table into a->gs, then one wave per candidate, then one wave per group; device pointers) ----
+hipError_t po_launch_select(const po::DevMaps *m, const po::DevCar *c, const po::DevSelect *a, hipStream_t st);
 }  // extern "C"

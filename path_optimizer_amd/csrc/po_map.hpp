@@ -97,6 +97,18 @@ struct PlanRows {
     double *states; po_info *info;      // [B][N][5], [B]
 };
 
+// score-and-select launch arguments (po_select.hip): po_select_in / po_select_out, the knobs of po_select_params, and the handle's scratch
+struct DevSelect {
+    int B, N, G, Np, goal_stride;
+    const double *states; const int *n_states, *ok; const double *goal;
+    const int *group_start;  // the caller's table [G + 1], unvalidated
+    const double *prev_states; const int *prev_n;
+    double w[PO_N_FEAT], d_safe, min_clearance, max_kmax, max_goal_dist;
+    int *gs;                 // scratch [G + 1]: the table as the kernels read it (clamped, non-decreasing)
+    double *feat, *cost;     // cost is never null here (the handle's scratch when the caller gave none)
+    int *best; double *best_cost; int *n_feasible; double *sel_states; int *sel_n;
+};
+
 #ifdef PO_MAP_DEVICE_CODE  // kernels and device functions: po_kernels.hip only (po_capi.cpp needs just the structs)
 // Layer k of the stack as a DevMap.  k is clamped into [0, M - 1] HERE, where it is read: a table that arrived through a device pointer was never validated, and a
 // bad entry must select a wrong layer, never an address outside the stack.
