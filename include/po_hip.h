@@ -716,6 +716,71 @@ typedef struct po_select_out {
 int po_select_batch(po_handle h, const po_select_params *p, const po_select_in *in, const po_select_out *out);         /* host pointers, synchronous */
 int po_select_batch_device(po_handle h, const po_select_params *p, const po_select_in *in, const po_select_out *out);  /* device pointers, on the stream, no synchronisation */
 
+/* ---- speed profile: v, a and t for every state of B planned paths (csrc/po_speed.hip) ----
+ * Every path the chain returns has State.v = State.a = 0, as in the reference.  This stage gives a path its time parameterisation on the device — the classic
+ * forward / backward pass over squared speed — and with it the two arrays po_limits_batch* (updateLimits) consumes: out->v and out->a have its [B][N] layout, so
+ * select -> speed -> limits -> a KPC solve needs no host round trip.  `states` is the [B][N][5] layout of po_plan_out.states, po_batch_out states and
+ * po_select_out.sel_states.  The reference has no such stage.
+ *
+ * Definition (the bar is BIT equality).  Every operation is one rounded IEEE double operation in the order written, nothing contracted; sqrt and / are the
+ * correctly rounded ones; a comparison with a NaN is false; min(a, b) = b < a ? b : a; max(a, b) = b > a ? b : a.  g = 9.8; A = mu * g (mu of the handle's
+ * po_params; one multiply, as updateLimits forms it); R = po_params.max_curvature_rate.  n = n_states[b] clamped into [0, N] (N when NULL); row i = (x_i, y_i, z_i, k_i, s_i).
+ *   Not profiled: status = 0 and the v, a, t rows and total_time are all zero when ok[b] == 0, or n < 2, or v0[b] is not a finite value >= 0, or any k or s of
+ *       rows < n is non-finite, or (use_map) any x, y or heading of rows < n is non-finite.
+ *   Otherwise, with ds_i = s_{i+1} - s_i and d_i = ds_i > 0 ? ds_i : 0:
+ *   1. Caps, per state i < n, in squared speed.  W_i = v_max * v_max, then in this order:
+ *       lateral:    ak = |k_i|;  if ak > 0: W_i = min(W_i, a_lat_max / ak).
+ *       rate:       r_j = ds_j > 0 ? |k_{j+1} - k_j| / ds_j : 0 for interval j;  rr = 0;  if i > 0: rr = max(rr, r_{i-1});  if i < n - 1: rr = max(rr, r_i);
+ *                   if rr > 0: q = R / rr, W_i = min(W_i, q * q).
+ *       per state:  if v_limit is given and l = v_limit[b][i] >= 0 (a negative or NaN entry is no limit): W_i = min(W_i, l * l).
+ *       clearance:  if use_map: c_i = the per-state clearance of po_select_batch's definition (six circles, the layer of instance b);  cc = c_i > 0 ? c_i : 0,
+ *                   vc = clear_v0 + clear_gain * cc, W_i = min(W_i, vc * vc).
+ *   2. Forward pass.  w_0 = min(W_0, v0 * v0).  For i = 0 .. n - 2:  lat = w_i * |k_i|;  rem = A * A - lat * lat;  rem = rem > 0 ? rem : 0;
+ *       ax = min(sqrt(rem), a_max);  w_{i+1} = min(W_{i+1}, w_i + (2 * ax) * d_i).
+ *   3. Backward pass.  If v_end is given and e = v_end[b] is a finite value >= 0: w_{n-1} = min(w_{n-1}, e * e).  For i = n - 2 .. 0:
+ *       lat = w_{i+1} * |k_{i+1}|;  rem as above;  bx = min(sqrt(rem), b_max);  w_i = min(w_i, w_{i+1} + (2 * bx) * d_i).
+ *   4. Outputs.  v_i = sqrt(w_i).  For i < n - 1: a_i = ds_i > 0 ? (w_{i+1} - w_i) / (2 * ds_i) : 0, then a_i = max(-A, min(a_i, A));  a_{n-1} = 0.
+ *       t_0 = 0;  vs = v_i + v_{i+1};  t_{i+1} = t_i + (vs > 0 ? (2 * d_i) / vs : 0).  total_time = t_{n-1}.  Rows >= n are zero.
+ *       status = 2 when the final w_0 < v0 * v0 (the vehicle enters faster than the caps and the braking limits allow), else 1.
+ *   The clamp on a: rounding otherwise leaves |a| an ulp above A on friction-limited intervals, and updateLimits' sqrt(A^2 - a^2) would be NaN; with the clamp
+ *       a * a <= A * A holds in rounded arithmetic.
+ *   Known property, stated and not fixed: an interval's friction bound is evaluated at the state the pass comes from, so a_i^2 + (w_i k_i)^2 can exceed A^2 on
+ *       braking intervals.  No claim is made about it.
+ * Return codes.  PO_ERR_INVALID: a NULL handle, struct or required pointer (B > 0: states, v0, v, a, status); a negative B or N; a parameter outside the ranges
+ *   given at po_speed_params (all seven are checked whatever use_map says), or NaN; use_map with no map or with an assignment shorter than B (the rule of
+ *   po_bounds_batch*).  B = 0: PO_OK, nothing is launched and nothing is written — decided after the argument and parameter checks and BEFORE the map rule.
+ *   use_map = 0 reads no map and works on a handle without one.
+ * `p` is a host pointer in both entries.  out->v doubles as the buffer between the two kernels (W, then w, then v): no scratch is allocated.  Deterministic: no
+ * atomics, and a path's results depend neither on the batch size nor on its position in the batch.
+ * po_default_speed_params: {15, 3, 2, 3, 1, 2, 0} — a starting point nobody has tuned. */
+typedef struct po_speed_params {
+    double v_max;       /* > 0, finite */
+    double a_lat_max;   /* 0 < a_lat_max <= mu * 9.8 */
+    double a_max;       /* > 0: forward acceleration cap */
+    double b_max;       /* > 0: braking cap */
+    double clear_v0;    /* >= 0: speed allowed at clearance <= 0 (use_map only) */
+    double clear_gain;  /* >= 0: speed per metre of clearance, 1/s (use_map only) */
+    int    use_map;     /* 0: no map is read and none is needed */
+} po_speed_params;
+void po_default_speed_params(po_speed_params *p);
+typedef struct po_speed_in {
+    int B, N;                /* paths, rows per path (stride) */
+    const double *states;    /* [B][N][5] x, y, heading, k, s */
+    const int    *n_states;  /* optional [B] (NULL: N) */
+    const int    *ok;        /* optional [B] (NULL: all 1) */
+    const double *v0;        /* [B] start speed */
+    const double *v_end;     /* optional [B] end speed (NULL: free) */
+    const double *v_limit;   /* optional [B][N]: per-state speed limit, a negative or NaN entry = none */
+} po_speed_in;
+typedef struct po_speed_out {
+    double *v, *a;           /* [B][N] — the layout po_limits_batch* reads */
+    double *t;               /* optional [B][N] */
+    double *total_time;      /* optional [B] */
+    int    *status;          /* [B]: 0 not profiled, 1 profiled, 2 profiled and entering too fast */
+} po_speed_out;
+int po_speed_batch(po_handle h, const po_speed_params *p, const po_speed_in *in, const po_speed_out *out);         /* host pointers, synchronous */
+int po_speed_batch_device(po_handle h, const po_speed_params *p, const po_speed_in *in, const po_speed_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -746,8 +811,8 @@ const char *po_last_hip_error(void);
  * (po_set_map_stack*, po_set_map_assignment*, po_get_map_layer, po_map_sample_layer, po_debug_get "map_layers") were ADDED under 7: no struct layout, no existing
  * entry and no field's meaning changed, so a binding written against 7 drives this library unchanged; one that needs the new entries looks the symbols up.  The
  * obstacle-list entries (po_obstacle, po_obstacle_lists, po_rasterize_batch*, po_set_map_stack_obstacles*) and the static-world entries (po_rings, po_scene, po_set_world_occupancy*, po_rasterize_scene_batch*, po_set_map_stack_scene*,
- * po_debug_get "world_cells") and the score-and-select entries (po_select_params, po_select_in, po_select_out, po_default_select_params, po_select_batch*) were
- * added under 7 by the same rule.  A binding should compare
+ * po_debug_get "world_cells") and the score-and-select entries (po_select_params, po_select_in, po_select_out, po_default_select_params, po_select_batch*) and
+ * the speed-profile entries (po_speed_params, po_speed_in, po_speed_out, po_default_speed_params, po_speed_batch*) were added under 7 by the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7
 const char *po_version(void);

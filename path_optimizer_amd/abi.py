@@ -140,3 +140,18 @@ class PoSelectIn(C.Structure):
 class PoSelectOut(C.Structure):
     _fields_ = [("feat", C.c_void_p), ("cost", C.c_void_p), ("best", C.c_void_p), ("best_cost", C.c_void_p), ("n_feasible", C.c_void_p),
                 ("sel_states", C.c_void_p), ("sel_n", C.c_void_p)]
+
+
+# ---- speed profile (po_speed_batch*) ----
+class PoSpeedParams(C.Structure):
+    _fields_ = [("v_max", C.c_double), ("a_lat_max", C.c_double), ("a_max", C.c_double), ("b_max", C.c_double), ("clear_v0", C.c_double),
+                ("clear_gain", C.c_double), ("use_map", C.c_int)]
+
+
+class PoSpeedIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("v0", C.c_void_p),
+                ("v_end", C.c_void_p), ("v_limit", C.c_void_p)]
+
+
+class PoSpeedOut(C.Structure):
+    _fields_ = [("v", C.c_void_p), ("a", C.c_void_p), ("t", C.c_void_p), ("total_time", C.c_void_p), ("status", C.c_void_p)]

@@ -31,7 +31,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_rasterize_batch", "po_rasterize_batch_device", "po_set_map_stack_obstacles", "po_set_map_stack_obstacles_device",
            "po_set_world_occupancy", "po_set_world_occupancy_device", "po_rasterize_scene_batch", "po_rasterize_scene_batch_device",
            "po_set_map_stack_scene", "po_set_map_stack_scene_device",
-           "po_default_select_params", "po_select_batch", "po_select_batch_device"]
+           "po_default_select_params", "po_select_batch", "po_select_batch_device",
+           "po_default_speed_params", "po_speed_batch", "po_speed_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -98,6 +99,10 @@ def lib():
         L.po_default_select_params.restype = None
         L.po_select_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_default_speed_params.argtypes = [C.c_void_p]
+        L.po_default_speed_params.restype = None
+        L.po_speed_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_speed_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -123,6 +128,15 @@ def default_select_params():
 
     p = PoSelectParams()
     lib().po_default_select_params(C.byref(p))
+    return p
+
+
+def default_speed_params():
+    """po_default_speed_params: the caps of po_speed_batch* (a starting point nobody has tuned)."""
+    from .abi import PoSpeedParams
+
+    p = PoSpeedParams()
+    lib().po_default_speed_params(C.byref(p))
     return p
 
 
@@ -828,6 +842,37 @@ class Engine:
         so = PoSelectOut(*[p(out, k) for k in ("feat", "cost", "best", "best_cost", "n_feasible", "sel_states", "sel_n")])
         sp = params if params is not None else default_select_params()
         _check(lib().po_select_batch_device(self._h, C.byref(sp), C.byref(si), C.byref(so)))
+
+    # ---- speed profile: v, a, t for every state of every path ----
+    def speed_batch(self, states, v0, n_states=None, ok=None, v_end=None, v_limit=None, params=None, want_t=True):
+        """Host-pointer entry of po_speed_batch.  states [B,N,5], v0 [B]; optional n_states [B], ok [B], v_end [B], v_limit [B,N] (negative or NaN: no limit).
+        Returns a dict: v, a [B,N] (what limits_batch reads), t [B,N] and total_time [B] (None without want_t), status [B]."""
+        from .abi import PoSpeedIn, PoSpeedOut
+
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        B, N = states.shape[0], states.shape[1]
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        v0, ve, vl = f(v0), f(v_end), f(v_limit)
+        ns, okk = _i32(n_states), _i32(ok)
+        si = PoSpeedIn(B, N, _np(states), _np(ns), _np(okk), _np(v0), _np(ve), _np(vl))
+        r = {"v": np.zeros((B, N)), "a": np.zeros((B, N)), "t": np.zeros((B, N)) if want_t else None, "total_time": np.zeros(B) if want_t else None,
+             "status": np.zeros(B, dtype=np.int32)}
+        so = PoSpeedOut(*[_np(r[k]) for k in ("v", "a", "t", "total_time", "status")])
+        sp = params if params is not None else default_speed_params()
+        _check(lib().po_speed_batch(self._h, C.byref(sp), C.byref(si), C.byref(so)))
+        return r
+
+    def speed_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: states [B,N,5] f64, v0 [B] f64 (+ n_states, ok i32, v_end [B], v_limit [B,N]); out: v, a [B,N] f64, status [B] i32 (+ t [B,N],
+        total_time [B]).  Enqueued on the handle's stream, no synchronisation."""
+        from .abi import PoSpeedIn, PoSpeedOut
+
+        B, N = t["states"].shape[0], t["states"].shape[1]
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        si = PoSpeedIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "v0"), p(t, "v_end"), p(t, "v_limit"))
+        so = PoSpeedOut(*[p(out, k) for k in ("v", "a", "t", "total_time", "status")])
+        sp = params if params is not None else default_speed_params()
+        _check(lib().po_speed_batch_device(self._h, C.byref(sp), C.byref(si), C.byref(so)))
 
     def map_sample(self, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)

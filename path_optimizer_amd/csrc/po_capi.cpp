@@ -1298,6 +1298,64 @@ int po_select_batch(po_handle h, const po_select_params *p, const po_select_in *
     return PO_OK;  // B = 0 or G = 0: nothing is staged, launched or written
 }
 
+// ---- speed profile -----------------------------------------------------------------------------
+void po_default_speed_params(po_speed_params *p) {
+    if (!p) return;
+    *p = po_speed_params{15.0, 3.0, 2.0, 3.0, 1.0, 2.0, 0};  // a starting point nobody has tuned
+}
+
+static bool speed_args_ok(po_handle h, const po_speed_params *p, const po_speed_in *in, const po_speed_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0) return false;
+    // (every comparison is false for a NaN, so each range is written as the condition that must HOLD)
+    if (!(p->v_max > 0) || !std::isfinite(p->v_max) || !(p->a_lat_max > 0) || !(p->a_lat_max <= h->params.mu * 9.8)) return false;
+    if (!(p->a_max > 0) || !(p->b_max > 0) || !(p->clear_v0 >= 0) || !(p->clear_gain >= 0)) return false;
+    if (in->B == 0) return true;
+    return in->states && in->v0 && out->v && out->a && out->status;
+}
+
+int po_speed_batch_device(po_handle h, const po_speed_params *p, const po_speed_in *in, const po_speed_out *out) {
+    if (!speed_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing to profile: no launch, whatever the handle holds
+    std::lock_guard<std::mutex> g(h->mu);
+    if (p->use_map && (!h->maps.d || !assignment_covers(h, in->B))) return PO_ERR_INVALID;  // po_set_map first; an assignment covers every path
+    HIP_TRY(hipSetDevice(h->device));
+    po::DevSpeed D{};
+    D.B = in->B; D.N = in->N; D.use_map = p->use_map ? 1 : 0;
+    D.states = in->states; D.n_states = in->n_states; D.ok = in->ok; D.v0 = in->v0; D.v_end = in->v_end; D.v_limit = in->v_limit;
+    D.v_max = p->v_max; D.a_lat_max = p->a_lat_max; D.a_max = p->a_max; D.b_max = p->b_max; D.clear_v0 = p->clear_v0; D.clear_gain = p->clear_gain;
+    D.A = h->params.mu * 9.8;  // one multiply, as updateLimits forms it
+    D.R = h->params.max_curvature_rate;
+    D.v = out->v; D.a = out->a; D.t = out->t; D.total_time = out->total_time; D.status = out->status;
+    const po::DevMaps maps = p->use_map ? h->maps : po::DevMaps{};  // use_map = 0: the kernels get no map to read
+    const po::DevCar car = make_car(h->params);
+    HIP_TRY(po_launch_speed(&maps, &car, &D, h->stream));
+    return PO_OK;
+}
+
+int po_speed_batch(po_handle h, const po_speed_params *p, const po_speed_in *in, const po_speed_out *out) {
+    if (!speed_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
+    const size_t B = in->B, bn = B * (size_t)in->N;
+    Stage S;
+    const Slot<double> states = S.in(in->states, 5 * bn), v0 = S.in(in->v0, B), ve = S.in(in->v_end, B), vl = S.in(in->v_limit, bn);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B);
+    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernels skip it
+    const Slot<double> v = S.out(out->v, bn), a = S.out(out->a, bn), t = out->t ? S.out(out->t, bn) : Slot<double>{};
+    const Slot<double> tt = out->total_time ? S.out(out->total_time, B) : Slot<double>{};
+    const Slot<int> status = S.out(out->status, B);
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        HIP_TRY(hipSetDevice(h->device));
+        PO_TRY(S.upload(h, h->post_buf));
+    }
+    const po_speed_in d{in->B, in->N, states, ns, ok, v0, ve, vl};
+    const po_speed_out o{v, a, t, tt, status};
+    PO_TRY(po_speed_batch_device(h, p, &d, &o));
+    std::lock_guard<std::mutex> g(h->mu);
+    return S.copy_out(h);
+}
+
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------
 static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bounds, const int *n_valid) {
     if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return false;

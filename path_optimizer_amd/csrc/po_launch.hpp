@@ -10,7 +10,7 @@
 namespace po {
 struct DevBatch; struct DevParams;                                                   // po_device.hpp
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
-struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect;
+struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
 
@@ -102,4 +102,7 @@ hipError_t po_launch_scene(const po_scene *scene, int M, const double *pos_xy, c
 
 // ---- po_select.hip: score and select (the clamped group table into a->gs, then one wave per candidate, then one wave per group; device pointers) ----
 hipError_t po_launch_select(const po::DevMaps *m, const po::DevCar *c, const po::DevSelect *a, hipStream_t st);
+
+// ---- po_speed.hip: the speed profile (caps: one wave per path; then the three sweeps: one lane per path, 64 paths per workgroup; device pointers) ----
+hipError_t po_launch_speed(const po::DevMaps *m, const po::DevCar *c, const po::DevSpeed *a, hipStream_t st);
 }  // extern "C"

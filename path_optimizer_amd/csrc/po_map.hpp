@@ -109,6 +109,15 @@ struct DevSelect {
     int *best; double *best_cost; int *n_feasible; double *sel_states; int *sel_n;
 };
 
+// speed-profile launch arguments (po_speed.hip): po_speed_in / po_speed_out, the knobs of po_speed_params, A = mu * 9.8 and R = max_curvature_rate
+struct DevSpeed {
+    int B, N, use_map;
+    const double *states; const int *n_states, *ok; const double *v0, *v_end, *v_limit;
+    double v_max, a_lat_max, a_max, b_max, clear_v0, clear_gain, A, R;
+    double *v, *a, *t, *total_time;  // v also carries W and w between the kernels; t and total_time may be null
+    int *status;
+};
+
 #ifdef PO_MAP_DEVICE_CODE  // kernels and device functions: po_kernels.hip only (po_capi.cpp needs just the structs)
 // Layer k of the stack as a DevMap.  k is clamped into [0, M - 1] HERE, where it is read: a table that arrived through a device pointer was never validated, and a
 // bad entry must select a wrong layer, never an address outside the stack.
