@@ -374,19 +374,8 @@ int po_solve_batch_device(po_handle h, const po_batch_in *in, const po_batch_out
     // refine = 2: plain warm-start launches, the Newton refinement as its own launch, then the (nearly always empty) fallback launch for the later rounds
     const bool split = h->params.refine == 2 && D.pol_state != nullptr && rounds_total < 32;
     if (split && ((rc = h->fb_buf.ensure(sizeof(int) * ((size_t)in->B + 1))) || (rc = h->fb_host.ensure(64)))) return rc;
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    h->timed_phases = false;
-    // per-path equilibration (h->params.scaling class-level Ruiz passes; 0 -> identity), then the fused solve
-    HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, static_cast<double *>(h->scale_buf.p), h->stream));
+    int pd = 0;  // doubles of a path's parking block when the Newton launch is sliced, else 0
     if (split) {
-        po::DevParams P1 = P;  // the warm start: the plain solve kernels, stopped where round 0 of the rounds stops (10^(R-1) x eps)
-        for (int r = 1; r < (h->params.refine_rounds > 1 ? h->params.refine_rounds : 1); ++r) { P1.eps_abs *= 10.0; P1.eps_rel *= 10.0; }
-        D.nw_follows = 1;  // (newton_kernel writes the outputs of the paths this launch reports SOLVED)
-        HIP_TRY(po_launch_solve(in->formulation, &D, &P1, h->stream, nullptr));
-        D.nw_follows = 0;
-        HIP_TRY(hipEventRecord(h->evp[0], h->stream));
-        D.fb_list = static_cast<int *>(h->fb_buf.p);
-        HIP_TRY(hipMemsetAsync(D.fb_list, 0, sizeof(int), h->stream));
         // SLICED LAUNCHES (engine-internal scheduling): the Newton launch is two — every path for nw_slice steps, the unfinished ones parked with a
         // priority key; a one-workgroup sort; the parked paths in order of expected remaining work, longest first.  One launch in engine order ends on a tail of a few
         // long paths (30 % of it on BASELINE config 3).  The operations and their order are unchanged: statuses and certificates do not depend on the slicing, solutions agree to round-off.
@@ -394,7 +383,7 @@ int po_solve_batch_device(po_handle h, const po_batch_in *in, const po_batch_out
         // 4.76 -> 4.06 ms, K 5.41 -> 4.85, keep 8 6.15 -> 5.75, 2 048 paths of config 3 2.62 -> 2.53; two-wave shapes gain or lose 1 % (keep 2 / 3) or lose 10 % (KPC at N = 400:
         // eight rounds, the re-entry of a 2 x 36 KB state per path), a batch of one round has no queueing tail to remove (config 2: + 10 % for the re-entry).
         const bool slice_auto = in->B >= 2 * h->wave_slots && po_shape_threads(in->formulation, in->N, C, in->keep) == 64;
-        int pd = (h->nw_slice > 0 && (slice_auto || h->nw_slice_forced)) ? po_newton_park_doubles(in->formulation, in->N, C, in->keep) : 0;
+        pd = (h->nw_slice > 0 && (slice_auto || h->nw_slice_forced)) ? po_newton_park_doubles(in->formulation, in->N, C, in->keep) : 0;
         // (the parking blocks are 39 KB per path on top of the state block: a batch they do not fit beside is solved unsliced — scheduling is not worth an out-of-memory error)
         if (pd > 0 && (h->nw_state_buf.ensure(sizeof(double) * (size_t)pd * (size_t)in->B) || h->nw_idx_buf.ensure(sizeof(int) * (2 * (size_t)in->B + 1)))) {
             (void)hipGetLastError();
@@ -402,11 +391,25 @@ int po_solve_batch_device(po_handle h, const po_batch_in *in, const po_batch_out
             pd = 0;
         }
         h->nw_last_B = pd > 0 ? in->B : 0;
+    }
+    HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    h->timed_phases = false;
+    // per-path equilibration (h->params.scaling class-level Ruiz passes; 0 -> identity), then the fused solve.  The same launch resets what the Newton launches count in:
+    // the fall-back work list's count, and the park keys to -1 (a path no workgroup of the first sliced launch reaches — a malformed caller-side order — is not parked)
+    HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, static_cast<double *>(h->scale_buf.p), pd > 0 ? static_cast<int *>(h->nw_idx_buf.p) : nullptr,
+                            split ? static_cast<int *>(h->fb_buf.p) : nullptr, h->stream));
+    if (split) {
+        po::DevParams P1 = P;  // the warm start: the plain solve kernels, stopped where round 0 of the rounds stops (10^(R-1) x eps)
+        for (int r = 1; r < (h->params.refine_rounds > 1 ? h->params.refine_rounds : 1); ++r) { P1.eps_abs *= 10.0; P1.eps_rel *= 10.0; }
+        D.nw_follows = 1;  // (newton_kernel writes the outputs of the paths this launch reports SOLVED)
+        HIP_TRY(po_launch_solve(in->formulation, &D, &P1, h->stream, nullptr));
+        D.nw_follows = 0;
+        HIP_TRY(hipEventRecord(h->evp[0], h->stream));
+        D.fb_list = static_cast<int *>(h->fb_buf.p);  // (its count: zeroed by scale_kernel)
         if (pd > 0) {
             D.nw_state = static_cast<double *>(h->nw_state_buf.p); D.nw_stride = pd;
             D.nw_keys = static_cast<int *>(h->nw_idx_buf.p); D.nw_list = D.nw_keys + in->B;
             P.ref_nw_slice = h->nw_slice;
-            HIP_TRY(hipMemsetAsync(D.nw_keys, 0xFF, sizeof(int) * (size_t)in->B, h->stream));  // (a path no workgroup of the first launch reaches — a malformed caller-side order — is not parked)
             D.nw_phase = 1;
             HIP_TRY(po_launch_newton(in->formulation, &D, &P, h->stream));
             HIP_TRY(po_launch_nw_sort(D.nw_keys, in->B, D.nw_list, h->stream));
@@ -655,7 +658,7 @@ int po_scaling_batch(po_handle h, const po_batch_in *in, double *out) {
     make_dev_params(h, in->formulation, in->keep, &P);
     po::DevBatch D;
     fill_dev_batch(h, &D, &din, nullptr, n, m, C);
-    HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, sc, h->stream));
+    HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, sc, nullptr, nullptr, h->stream));  // (diagnostic: no solve follows, nothing to reset)
     return O.copy_out(h);
 }
 

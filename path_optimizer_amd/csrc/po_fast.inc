@@ -223,10 +223,12 @@ struct ReclassFn {
 // NWX (what the kernels are instantiated with): 1 = one lane per chunk, 2 = role-split, 3 = role-split of an odd keep.
 // NFIX: the path length at COMPILE time (0: at run time), for the LDS LAYOUT and the global offsets: LayoutF — TP, every table offset, the row counts of the scans — is then a
 // constant of the instantiation and the LDS addresses are immediates; the same LayoutF / state block / parking block as at run time, so a path may cross between a fixed and a
-// generic kernel (fall-back rounds, polish, a resumed path).  N and C THEMSELVES stay run-time values on purpose: with N a constant the compiler merges the per-stage
+// generic kernel (fall-back rounds, polish, a resumed path).  C, the number of controls, is the constant kFixC as well: it only decides which lanes own a control
+// (`cidx(g) < C`), no floating-point block hangs on it.  N ITSELF stays a run-time value on purpose: with N a constant the compiler merges the per-stage
 // `stage(q) < N` regions and drops the copies of the final-stage rows that cannot occur, which changes where multiply-adds are contracted — 10 % fewer instructions still, but the
-// results then differ from the generic kernels' in the last bits and a path in 4 096 takes one Newton step more (DESIGN.md section 19).  Layout only: bit for bit the generic
-// kernels' results.  The launchers take such an instantiation only for a non-ragged batch of exactly that length.
+// results then differ from the generic kernels' in the last bits and a path in 4 096 takes one Newton step more (DESIGN.md section 19).  The fixed instantiations also keep the
+// wave-uniform row steps of a pass in scalar registers (eq_row_step() / eq_row_scale()).  Layout, C and where uniform values live: bit for bit the generic kernels' results.
+// The launchers take such an instantiation only for a non-ragged batch of exactly that length.
 template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fast {
     static_assert(NFIX == 0 || (F == F_KP && TWO && NWX == 1 && NFIX >= 2 && NFIX <= NT * SPL), "fixed length: KP, one lane per chunk, a length the shape covers");
     static constexpr int kFixC = NFIX > 0 ? (NFIX + SPL - 2) / SPL : 0;  // controls of a path of NFIX points (keep == SPL on this shape: path_c())
@@ -275,7 +277,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
     // through S degrades to a flat load: 17.5 -> 41.7 ms per BASELINE batch)
     __device__ __forceinline__ Fast(const DevParams &P_, const DevBatch &in_, double *S_, int b_)
         : P(P_), in(in_), L(NFIX > 0 ? NFIX : path_n(in_, b_), NFIX > 0 ? kFixC : path_c<F>(in_, b_), SPL, TWO, NT, NW, CH, NG), S(S_), N(path_n(in_, b_)),
-          C(path_c<F>(in_, b_)), keep(in_.keep), tid(threadIdx.x), b(b_), po((size_t)b_ * (NFIX > 0 ? NFIX : in_.N)) {
+          C(NFIX > 0 ? kFixC : path_c<F>(in_, b_)), keep(in_.keep), tid(threadIdx.x), b(b_), po((size_t)b_ * (NFIX > 0 ? NFIX : in_.N)) {
         sc = in_.scale + (size_t)b_ * kScStride;
         elo = -kInf; ehi = kInf;
         if (P.end_heading) {  // solver_kp_as_input.cpp:193-202
@@ -347,6 +349,10 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
     __device__ __forceinline__ double cD(int v, int j) const { return sc[kScCD + ((v == 2 && k_end(j)) ? kKEndVar : v)]; }
     __device__ __forceinline__ const double *Wdyn() const { return sc + kScW + T::NLOC; }
     __device__ __forceinline__ const double *Edyn() const { return sc + kScE + T::NLOC; }
+    // a pass's step of dynamics row r (rho_eq x its weight) and the row's equilibration factor: the same for every lane and alive for the whole pass.  The fixed-length
+    // kernels keep them in scalar registers (uni(), po_device.hpp) — fewer vector registers to spill around the row loops; the generic kernels leave them where they were.
+    __device__ __forceinline__ double eq_row_step(double rho_eq, int r) const { const double v = rho_eq * Wdyn()[r]; if constexpr (NFIX > 0) return uni(v); else return v; }
+    __device__ __forceinline__ double eq_row_scale(int r) const { const double v = Edyn()[r]; if constexpr (NFIX > 0) return uni(v); else return v; }
     __device__ __forceinline__ const double *Wctl() const { return sc + kScW + T::NLOC + T::NDYN; }
     __device__ __forceinline__ const double *Ectl() const { return sc + kScE + T::NLOC + T::NDYN; }
     __device__ __forceinline__ const double *Wend() const { return sc + kScW + T::NLOC + T::NDYN + T::NCTL; }
@@ -484,7 +490,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
             double re[T::NDYN];  // equality rows: rho_eq * E^2 / c per dynamics row
 #pragma unroll
             for (int r = 0; r < T::NDYN; ++r) {
-                re[r] = rho_eq * Wdyn()[r];
+                re[r] = eq_row_step(rho_eq, r);
                 const int t = dyn_tau<F>(r);
                 G[t == 0 ? 0 : (t == 1 ? 3 : 5)] += re[r];
             }
@@ -628,7 +634,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
             if (T::NEND && si.last) { fn.v = st.vend; fn.W = Wend(); fn.E = Eend(); fn.cls = st.clse; end_rows<F>(si, P, fn); }
             double re[T::NDYN];
 #pragma unroll
-            for (int r = 0; r < T::NDYN; ++r) re[r] = rho_eq * Wdyn()[r];
+            for (int r = 0; r < T::NDYN; ++r) re[r] = eq_row_step(rho_eq, r);
             // rows into stage j
             double tkj = 0;
             if (j == 0) {
@@ -873,7 +879,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         Cert ct = {0, 0, 0};
         double re[T::NDYN], dy_next[T::NDYN];  // dy of the rows into the stage processed just before (q+1)
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) { re[r] = rho_eq * Wdyn()[r]; dy_next[r] = 0; }
+        for (int r = 0; r < T::NDYN; ++r) { re[r] = eq_row_step(rho_eq, r); dy_next[r] = 0; }
 #pragma unroll
         for (int q = SPL - 1; q >= 0; --q) {  // descending: the rows OUT of stage q are the rows INTO q+1, handled one step earlier
             const int j = stage(q);
@@ -1022,7 +1028,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         int bad = 0;    // a non-finite primal or dual value anywhere (see nonfinite_bits)
         double re[T::NDYN], ed[T::NDYN];
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) { re[r] = rho_eq * Wdyn()[r]; ed[r] = Edyn()[r]; }
+        for (int r = 0; r < T::NDYN; ++r) { re[r] = eq_row_step(rho_eq, r); ed[r] = eq_row_scale(r); }
 #pragma unroll
         for (int q = 0; q < SPL; ++q) {
             const int j = stage(q);
@@ -1327,7 +1333,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         for (int g = 0; g < NG; ++g) huu_dyn[g] = 0;
         double re[T::NDYN];
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) re[r] = rho_eq * Wdyn()[r];
+        for (int r = 0; r < T::NDYN; ++r) re[r] = eq_row_step(rho_eq, r);
 #pragma unroll
         for (int q = 0; q < SPL; ++q) {
             const int j = stage(q);
@@ -2061,7 +2067,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         const double rho_eq = eq_step(rho);
         double re[T::NDYN];
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) re[r] = rho_eq * Wdyn()[r];
+        for (int r = 0; r < T::NDYN; ++r) re[r] = eq_row_step(rho_eq, r);
 #ifndef PO_SEQ_FACTOR  // the pivot chain as a scan over chunks (factor_pivots_scan); -DPO_SEQ_FACTOR: the sequential recursion everywhere (A/B)
         constexpr bool kScanPivots = true;
 #else
@@ -2595,7 +2601,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         const double rho_eq = eq_step(rho);
         double re[T::NDYN];
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) re[r] = rho_eq * Wdyn()[r];
+        for (int r = 0; r < T::NDYN; ++r) re[r] = eq_row_step(rho_eq, r);
         const int tfull = (N - 1) / CH;
         const bool fullc = nq_chunk() == CH;
         const double zero3[3] = {0, 0, 0};
@@ -2652,7 +2658,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         for (int g = 0; g < NG; ++g) tku[g] = 0;
         double re[T::NDYN];
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) re[r] = rho_eq * Wdyn()[r];
+        for (int r = 0; r < T::NDYN; ++r) re[r] = eq_row_step(rho_eq, r);
         const double tgt = NWT ? 1.0 : 2.0;  // target of an equality row: 2 b - v (ADMM) / b - v (Newton)
         double nwp[2] = {0, 0}, nwn = 0;     // K, Newton: steering of the neighbouring stages (tridiagonal R block of P)
         if constexpr (NWT && F == F_K) {
@@ -2818,7 +2824,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         const double rho_eq = eq_step(rho);
         double re[T::NDYN];
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) re[r] = rho_eq * Wdyn()[r];
+        for (int r = 0; r < T::NDYN; ++r) re[r] = eq_row_step(rho_eq, r);
         const int nq = nq_own(), nst = nst_own();
         const bool full = (nq == SPL);
         double fu[NG][4];  // own controls' factor entries, one read per solve
@@ -3107,7 +3113,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
 #pragma unroll
         for (int g = 0; g < NG; ++g) dytk[g] = 0;
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) { re[r] = rho_eq * Wdyn()[r]; dy_next[r] = 0; }
+        for (int r = 0; r < T::NDYN; ++r) { re[r] = eq_row_step(rho_eq, r); dy_next[r] = 0; }
 #pragma unroll
         for (int q = SPL - 1; q >= 0; --q) {  // descending: the rows OUT of stage q are the rows INTO q+1, handled one step earlier
             const int j = stage(q);
@@ -3289,7 +3295,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         for (int g = 0; g < NG; ++g) ytku[g] = 0;
         int bad = 0;
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) { re[r] = rho_eq * Wdyn()[r]; ed[r] = Edyn()[r]; }
+        for (int r = 0; r < T::NDYN; ++r) { re[r] = eq_row_step(rho_eq, r); ed[r] = eq_row_scale(r); }
 #pragma unroll
         for (int q = 0; q < SPL; ++q) {
             const int j = stage(q);
@@ -3611,7 +3617,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         const double rho_eq = eq_step(rho);
         double re[T::NDYN];
 #pragma unroll
-        for (int r = 0; r < T::NDYN; ++r) re[r] = rho_eq * Wdyn()[r];
+        for (int r = 0; r < T::NDYN; ++r) re[r] = eq_row_step(rho_eq, r);
         double xp2 = 0, xn2 = 0;  // K, MODE 0: steering of the neighbouring stages at x (tridiagonal R block of P)
         if constexpr (MODE == 0 && F == F_K) {
             const int nst = nst_own();

@@ -23,7 +23,7 @@ hipError_t po_launch_polish(int form, const po::DevBatch *in, const po::DevParam
 hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_t st);
 hipError_t po_launch_mark_unavailable(po_info *info, int B, int refine, int polish, hipStream_t st);
 hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipStream_t st);
-hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, hipStream_t st);
+hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, int *nw_keys, int *fb_count, hipStream_t st);
 hipError_t po_launch_assemble(int form, const po::DevBatch *in, const po::DevParams *P, double *l, double *u, double *dyn, hipStream_t st);
 size_t po_lds_bytes(int form, int N, int C, int keep);
 int po_shape_threads(int form, int N, int C, int keep);
