@@ -5,11 +5,13 @@
 //                                   in ONE launch, per-path state resident in VGPRs / LDS
 //   assemble_kernel                 diagnostic: the assembled bounds / data-dependent A entries in the
 //                                   reference row order, for bit-exact comparison with the oracle
+// and the DISPATCHER of the solve kernels, which live in objects of their own (po_solve_form.hip): the shape of a batch and its LDS bytes are resolved once per launch,
+// the table of shapes (po_solve_common.hpp) names the group of the row that equals it, the list of objects (po_launch.hpp) the one object to call.  The size and
+// capability queries (po_polish_state_doubles, ...) are answered here from the same table.
 //
 // Replaces, per path, the work behind /root/reference/src/solver/solver.cpp:46-77 (setHessianMatrix,
 // setConstraintMatrix, osqp_setup, osqp_solve, getOptimizedPath).
 #include "po_solve_common.hpp"
-#include "po_launch.hpp"
 
 namespace po {
 
@@ -52,8 +54,6 @@ template <int F> __global__ __launch_bounds__(64) void assemble_kernel(DevBatch 
 
 }  // namespace po
 
-// the solve kernels of one formulation and one loop variant live in their own object (po_solve_form.hip; its entries are declared in po_launch.hpp)
-
 namespace po {
 // After the launches of a solve that hands paths from launch to launch (the Newton refinement's rounds): no internal "in flight" status may reach the caller
 // (a path that a malformed caller-side order skipped): anything at or below kStatusDeferred becomes UNSOLVED.
@@ -75,24 +75,51 @@ extern "C" hipError_t po_launch_mark_unavailable(po_info *info, int B, int refin
     hipLaunchKernelGGL(po::mark_unavailable_kernel, dim3((B + 255) / 256), dim3(256), 0, st, info, B, refine, polish);
     return hipGetLastError();
 }
-// Two launches on the same stream for the two-level mapping: the uniform-row-class variant first (solves what it can, defers the rest),
-// then the general variant (po_fast.inc, solve_kernel_fast).
+// ---- the dispatcher of the solve kernels.  Every launch resolves the shape of the batch and its LDS bytes ONCE, finds the group of the table row that equals the shape
+// (po_solve_common.hpp) and calls the ONE object that holds that formulation, kind and group (po_launch.hpp) with both; what that entry returns is the result.
+namespace po {
+namespace {
+using Entry = hipError_t(int, const Shape &, size_t, const DevBatch *, const DevParams *, hipStream_t);
+struct Object { Entry *entry; int form, kind, groups; };
+#define PO_X(name, form, kind, groups) {&name, form, kind, groups},
+const Object kObjects[] = {PO_SOLVE_OBJECTS(PO_X)};
+#undef PO_X
+struct Resolved { Shape s; size_t lds; int group; bool fixed; };
+// lds is set whenever the shape resolves (po_launch_solve reports it even when it is over the limit)
+hipError_t resolve(int form, const DevBatch *in, Resolved *r) {
+    r->lds = 0;
+    if (!resolve_shape(form, in->N, in->C, in->keep, &r->s)) return hipErrorInvalidValue;
+    r->lds = lds_of(form, in->N, in->C, r->s);
+    r->group = group_of(form, r->s);
+#ifdef PO_DEV_HEADLINE  // (the KP objects of `make dev` hold their one shape whatever its group: the first linked object of the kind is asked)
+    if (form == F_KP && r->group) r->group = ~0;
+#endif
+    // a listed length (DevBatch::fixed_len, set from po_has_fixed_length): the kernels compiled for that length
+    r->fixed = in->fixed_len && in->n_points == nullptr && is_fixed_shape(form, in->N, in->C, in->keep, r->s);
+    return r->lds > 160 * 1024 ? hipErrorInvalidValue : hipSuccess;
+}
+hipError_t call(int form, int kind, int launch, const Resolved &r, const DevBatch *in, const DevParams *P, hipStream_t st) {
+    for (const Object &o : kObjects)
+        if (o.form == form && o.kind == kind && (o.groups & r.group) && o.entry) return o.entry(launch, r.s, r.lds, in, P, st);
+    return hipErrorNotSupported;  // no row equals the shape, or (dev builds) the object is not linked
+}
+}  // namespace
+}  // namespace po
+// Two launches on the same stream for the two-level mapping: the uniform-row-class variant first (solves what it can, defers the rest; a listed length: the one compiled
+// for that length), then the general variant, which solves only what the first deferred (po_fast.inc, solve_kernel_fast).  Shapes without a uniform variant (the
+// single-level mapping, K on multi-wave blocks): the general variant alone.
 extern "C" hipError_t po_launch_solve(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out) {
     using namespace po;
-    hipError_t e;
-    if (form == F_KP) {
-        // a listed length (DevBatch::fixed_len): the uniform warm start compiled for that length; the general variant behind it picks up what it deferred, as always
-        e = in->fixed_len ? po_launch_solve_kp_fix_uni(in, P, st, lds_out) : kNotMyShape;
-        if (e == kNotMyShape) e = po_launch_solve_kp_uni(in, P, st, lds_out);
-        if (e == kNotMyShape) {  // not a shape of keep 1 .. 8: the wide objects
-            e = po_launch_solve_kp_w_uni(in, P, st, lds_out);
-            return e != hipSuccess ? e : po_launch_solve_kp_w(in, P, st, lds_out);
-        }
-        return e != hipSuccess ? e : po_launch_solve_kp(in, P, st, lds_out);
-    }
-    if (form == F_KPC) { e = po_launch_solve_kpc_uni(in, P, st, lds_out); return e != hipSuccess ? e : po_launch_solve_kpc(in, P, st, lds_out); }
-    e = po_launch_solve_k_uni(in, P, st, lds_out);
-    return e != hipSuccess ? e : po_launch_solve_k(in, P, st, lds_out);
+    Resolved r;
+    hipError_t e = resolve(form, in, &r);
+    if (lds_out && r.lds) *lds_out = r.lds;
+    if (e != hipSuccess) return e;
+    const bool uni = form == F_K ? has_uni_variant<F_K>(r.s) : has_uni_variant<F_KP>(r.s);
+    DevBatch copy = *in;
+    copy.only_deferred = 0;
+    if (uni && (e = call(form, r.fixed ? kObjFixUni : kObjUni, kLaunchSolve, r, &copy, P, st)) != hipSuccess) return e;
+    copy.only_deferred = uni ? 1 : 0;
+    return call(form, kObjGen, kLaunchSolve, r, &copy, P, st);
 }
 // no internal "in flight" status reaches the caller (finalize_status_kernel)
 extern "C" hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_t st) {
@@ -100,42 +127,22 @@ extern "C" hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_
     return hipGetLastError();
 }
 
-// the Newton refinement of round 0 as its own launch (po_params.refine = 2), and the fallback launch for what it hands back
-extern "C" hipError_t po_launch_newton(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
+// the launches that pick up the state block of a two-level shape: the Newton refinement of round 0 (po_params.refine = 2; a listed length: the kernel compiled for it), the
+// fallback launch for what it hands back, and the polish
+static hipError_t launch_two_level(int form, int launch, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
     using namespace po;
-    if (form == F_KP) {  // (an object answers kNotMyShape for a shape it does not hold; any other code is that launch's own failure and is returned as it is)
-        hipError_t e = !in->fixed_len ? kNotMyShape : (in->nw_phase == 2 ? po_launch_newton_kp_fix2(in, P, st) : po_launch_newton_kp_fix1(in, P, st));
-        if (e == kNotMyShape) e = po_launch_newton_kp(in, P, st);
-        if (e == kNotMyShape) e = po_launch_newton_kp_b(in, P, st);
-        if (e == kNotMyShape) e = po_launch_newton_kp_c(in, P, st);
-        if (e == kNotMyShape) e = po_launch_newton_kp_w1(in, P, st);
-        if (e == kNotMyShape) e = po_launch_newton_kp_w2(in, P, st);
-        return e == kNotMyShape ? po_launch_newton_kp_w3(in, P, st) : e;
-    }
-    return form == F_KPC ? po_launch_newton_kpc(in, P, st) : po_launch_newton_k(in, P, st);
+    Resolved r;
+    const hipError_t e = resolve(form, in, &r);
+    if (!r.lds || !r.s.two) return hipErrorInvalidValue;
+    if (launch == kLaunchPolish && !has_polish_kernel(r.s)) return hipSuccess;
+    if (e != hipSuccess) return e;
+    const int kind = (launch == kLaunchNewton && r.fixed) ? (in->nw_phase == 2 ? kObjFixNewton2 : kObjFixNewton1) : (launch == kLaunchPolish ? kObjGen : kObjNewton);
+    return call(form, kind, launch, r, in, P, st);
 }
-extern "C" hipError_t po_launch_newton_fallback(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
-    using namespace po;
-    if (form == F_KP) {
-        hipError_t e = po_launch_newton_kp_fb(in, P, st);
-        if (e == kNotMyShape) e = po_launch_newton_kp_b_fb(in, P, st);
-        if (e == kNotMyShape) e = po_launch_newton_kp_c_fb(in, P, st);
-        if (e == kNotMyShape) e = po_launch_newton_kp_w1_fb(in, P, st);
-        if (e == kNotMyShape) e = po_launch_newton_kp_w2_fb(in, P, st);
-        return e == kNotMyShape ? po_launch_newton_kp_w3_fb(in, P, st) : e;
-    }
-    return form == F_KPC ? po_launch_newton_kpc_fb(in, P, st) : po_launch_newton_k_fb(in, P, st);
-}
-// OSQP's polish (po_params.polish) on the paths the two solve launches reported solved; same stream, after them
-extern "C" hipError_t po_launch_polish(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
-    using namespace po;
-    return form == F_KP ? po_launch_polish_kp(in, P, st) : (form == F_KPC ? po_launch_polish_kpc(in, P, st) : po_launch_polish_k(in, P, st));
-}
-extern "C" int po_newton_park_doubles(int form, int N, int C, int keep) {
-    using namespace po;
-    if (form == F_KP) { const int d = po_polish_state_doubles_kp_park(N, C, keep); return d ? d : po_polish_state_doubles_kp_w_park(N, C, keep); }
-    return form == F_KPC ? po_polish_state_doubles_kpc_park(N, C, keep) : po_polish_state_doubles_k_park(N, form == F_K ? 0 : C, keep);
-}
+extern "C" hipError_t po_launch_newton(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchNewton, in, P, st); }
+extern "C" hipError_t po_launch_newton_fallback(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchFallback, in, P, st); }
+// OSQP's polish (po_params.polish) on the paths the two solve launches reported solved; same stream, after them (a shape without a polish kernel: nothing to do)
+extern "C" hipError_t po_launch_polish(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchPolish, in, P, st); }
 namespace po {
 // the parked paths (keys[b] >= 0) in descending key order, ties in path order (a stable counting sort: deterministic): list[0] = count, list[1 ..] = path ids.
 // One workgroup of kNwSortThreads threads, thread t owns the contiguous range of paths [t * per, (t + 1) * per).
@@ -207,12 +214,35 @@ extern "C" hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipSt
     hipLaunchKernelGGL(po::nw_sort_kernel, dim3(1), dim3(po::kNwSortThreads), 0, st, keys, B, list);
     return hipGetLastError();
 }
-// is there a length-specialised instantiation for a (non-ragged) batch of this shape?  (KP only)
-extern "C" int po_has_fixed_length(int form, int N, int C, int keep) { return form == po::F_KP ? po_has_fixed_length_kp(N, C, keep) : 0; }
-extern "C" int po_polish_state_doubles(int form, int N, int C, int keep) {
-    using namespace po;
-    if (form == F_KP) { const int d = po_polish_state_doubles_kp(N, C, keep); return d ? d : po_polish_state_doubles_kp_w(N, C, keep); }
-    return form == F_KPC ? po_polish_state_doubles_kpc(N, C, keep) : po_polish_state_doubles_k(N, form == F_K ? 0 : C, keep);
+// ---- the size and capability queries: functions of the resolved shape and of class constants of its table row; no object is asked.  (K has no held controls: C = 0)
+namespace po {
+namespace {
+template <int F, bool TWO, int SPL, int NT, int NWX> struct RowSizes { static constexpr int state = 0, park = 0; };  // the single-level mapping: neither Newton nor polish
+template <int F, int SPL, int NT, int NWX> struct RowSizes<F, true, SPL, NT, NWX> {
+    static constexpr int state = Fast<F, SPL, NT, true, NWX>::kStateDoubles * NT, park = Fast<F, SPL, NT, true, NWX>::kParkDoubles * NT + kNwParkScalars;
+};
+int row_doubles(int form, int N, int C, int keep, bool park) {
+    Shape s;
+    if (!resolve_shape(form, N, form == F_K ? 0 : C, keep, &s)) return 0;
+#define PO_X(F_, TWO_, SPL_, NT_, NWX_, G_) if (form == F_ && is_shape(s, TWO_, SPL_, NT_, NWX_)) return park ? RowSizes<F_, TWO_, SPL_, NT_, NWX_>::park : RowSizes<F_, TWO_, SPL_, NT_, NWX_>::state;
+    PO_SHAPE_ROWS(PO_X)
+#undef PO_X
+    return 0;
+}
+}  // namespace
+}  // namespace po
+// doubles per path of the state block the solve kernels leave for the Newton refinement and the polish (0: shape without either: the single-level mapping)
+extern "C" int po_polish_state_doubles(int form, int N, int C, int keep) { return po::row_doubles(form, N, C, keep, false); }
+// doubles per path of the block a PARKED Newton path lives in between the two sliced launches (Fast::park_io + kNwParkScalars)
+extern "C" int po_newton_park_doubles(int form, int N, int C, int keep) { return po::row_doubles(form, N, C, keep, true); }
+// is there a length-specialised instantiation for a (non-ragged) batch of this shape?  (KP only; this object is built with the list of lengths, PO_FIXED_LIST)
+extern "C" int po_has_fixed_length(int form, int N, int C, int keep) {
+    po::Shape s;
+    if (!po::resolve_shape(form, N, C, keep, &s) || !po::is_fixed_shape(form, N, C, keep, s) || po::lds_of(form, N, C, s) > 160 * 1024) return 0;
+#define PO_X(N_) if (N == N_) return 1;
+    PO_FIXED_LIST(PO_X)
+#undef PO_X
+    return 0;
 }
 // threads per path of the shape this batch runs in (0: unsupported)
 extern "C" int po_shape_threads(int form, int N, int C, int keep) {
@@ -221,8 +251,8 @@ extern "C" int po_shape_threads(int form, int N, int C, int keep) {
 }
 // does the shape of this batch have a polish kernel?  (the role-split shapes of keep 6 .. 16 and the single-level mapping do not)
 extern "C" int po_has_polish_kernel(int form, int N, int C, int keep) {
-    using namespace po;
-    return form == F_KP ? po_has_polish_kernel_kp(N, C, keep) : (form == F_KPC ? po_has_polish_kernel_kpc(N, C, keep) : po_has_polish_kernel_k(N, form == F_K ? 0 : C, keep));
+    po::Shape s;
+    return po::resolve_shape(form, N, form == po::F_K ? 0 : C, keep, &s) && po::has_polish_kernel(s);
 }
 
 // nw_keys ([B]) / fb_count (one int), when set: reset by the same launch (scale_kernel) — the solve needs no fill of its own between its launches

@@ -9,6 +9,13 @@
 
 namespace po {
 struct DevBatch; struct DevParams;                                                   // po_device.hpp
+struct Shape;                                                                        // po_solve_common.hpp
+// what an object of the solve kernels holds: the uniform-row-class / general variant of the solve kernels (the general object: also the polish kernels), the Newton
+// kernels (both phases and the fallback), or the length-specialised uniform warm start / first / second Newton launch
+enum { kObjUni, kObjGen, kObjNewton, kObjFixUni, kObjFixNewton1, kObjFixNewton2 };
+enum { kLaunchSolve, kLaunchNewton, kLaunchFallback, kLaunchPolish };  // what an entry is asked to launch (Newton: phase 1 or 2 by DevBatch::nw_phase)
+// the groups the shapes are dealt to the objects in (KP's two-level shapes: one lane per chunk / role-split / multi-group / the wide role-split shapes by SPL; the single-level mapping)
+enum { kGrpLane = 1, kGrpSplit = 2, kGrpMulti = 4, kGrpW56 = 8, kGrpW7 = 16, kGrpW8 = 32, kGrpOne = 64 };
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
 struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed;
 struct DevSmooth;                                                                    // po_smooth.hpp
@@ -32,32 +39,38 @@ int po_newton_park_doubles(int form, int N, int C, int keep);
 int po_has_polish_kernel(int form, int N, int C, int keep);
 int po_has_fixed_length(int form, int N, int C, int keep);
 
-// ---- po_solve_form.hip: one object per formulation, loop variant and shape group; the names are pasted together there (PO_G / PO_CAT) ----
-#define PO_DECL_SOLVE(name) hipError_t name(const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out)
-#define PO_DECL_LAUNCH(name) hipError_t name(const po::DevBatch *in, const po::DevParams *P, hipStream_t st)
-#define PO_DECL_NEWTON(name) PO_DECL_LAUNCH(name); PO_DECL_LAUNCH(name##_fb)
-#define PO_DECL_SIZES(name) int name(int N, int C, int keep); int name##_park(int N, int C, int keep)
-PO_DECL_SOLVE(po_launch_solve_kp); PO_DECL_SOLVE(po_launch_solve_kp_uni);
-PO_DECL_SOLVE(po_launch_solve_kp_w); PO_DECL_SOLVE(po_launch_solve_kp_w_uni);  // the wide role-split shapes of keep 9 .. 16
-PO_DECL_SOLVE(po_launch_solve_kpc); PO_DECL_SOLVE(po_launch_solve_kpc_uni);
-PO_DECL_SOLVE(po_launch_solve_k); PO_DECL_SOLVE(po_launch_solve_k_uni);
-PO_DECL_NEWTON(po_launch_newton_kp); PO_DECL_NEWTON(po_launch_newton_kpc); PO_DECL_NEWTON(po_launch_newton_k);
-PO_DECL_NEWTON(po_launch_newton_kp_b);  // KP's role-split shapes (second Newton object)
-PO_DECL_NEWTON(po_launch_newton_kp_c);  // KP's multi-group shapes (third)
-PO_DECL_NEWTON(po_launch_newton_kp_w1); PO_DECL_NEWTON(po_launch_newton_kp_w2); PO_DECL_NEWTON(po_launch_newton_kp_w3);  // keep 9 .. 16
-// the length-specialised kernels of KP's headline shape (Makefile: PO_FIXED_N), objects of their own: the uniform warm start; the first / second Newton launch
-PO_DECL_SOLVE(po_launch_solve_kp_fix_uni); PO_DECL_LAUNCH(po_launch_newton_kp_fix1); PO_DECL_LAUNCH(po_launch_newton_kp_fix2);
-int po_has_fixed_length_kp(int N, int C, int keep);
-PO_DECL_LAUNCH(po_launch_polish_kp); PO_DECL_LAUNCH(po_launch_polish_kpc); PO_DECL_LAUNCH(po_launch_polish_k);
-PO_DECL_SIZES(po_polish_state_doubles_kp); PO_DECL_SIZES(po_polish_state_doubles_kp_w);
-PO_DECL_SIZES(po_polish_state_doubles_kpc); PO_DECL_SIZES(po_polish_state_doubles_k);
-int po_has_polish_kernel_kp(int N, int C, int keep);
-int po_has_polish_kernel_kpc(int N, int C, int keep);
-int po_has_polish_kernel_k(int N, int C, int keep);
-#undef PO_DECL_SOLVE
-#undef PO_DECL_LAUNCH
-#undef PO_DECL_NEWTON
-#undef PO_DECL_SIZES
+// ---- po_solve_form.hip: the objects that hold the solve kernels.  X(object, formulation, kind, shape groups it holds): ONE entry per object, named like the object (the
+// Makefile compiles <object>.o with -DPO_ENTRY=<object>), one signature for all.  The object reads its own row here; the dispatcher (po_kernels.hip) builds its route
+// table from the same list, and the link fails on an object the Makefile's list lacks.  The groups are those of po_solve_common.hpp's table of shapes.
+#define PO_SOLVE_OBJECTS(X)                                                     \
+    X(po_solve_kp_uni, F_KP, kObjUni, kGrpLane | kGrpSplit | kGrpMulti)         \
+    X(po_solve_kp, F_KP, kObjGen, kGrpLane | kGrpSplit | kGrpMulti | kGrpOne)   \
+    X(po_solve_kp_w_uni, F_KP, kObjUni, kGrpW56 | kGrpW7 | kGrpW8)              \
+    X(po_solve_kp_w, F_KP, kObjGen, kGrpW56 | kGrpW7 | kGrpW8)                  \
+    X(po_solve_kpc_uni, F_KPC, kObjUni, kGrpLane)                               \
+    X(po_solve_kpc, F_KPC, kObjGen, kGrpLane | kGrpOne)                         \
+    X(po_solve_k_uni, F_K, kObjUni, kGrpLane)                                   \
+    X(po_solve_k, F_K, kObjGen, kGrpLane | kGrpOne)                             \
+    X(po_newton_kp, F_KP, kObjNewton, kGrpLane)                                 \
+    X(po_newton_kp_b, F_KP, kObjNewton, kGrpSplit)                              \
+    X(po_newton_kp_c, F_KP, kObjNewton, kGrpMulti)                              \
+    X(po_newton_kp_w1, F_KP, kObjNewton, kGrpW56)                               \
+    X(po_newton_kp_w2, F_KP, kObjNewton, kGrpW7)                                \
+    X(po_newton_kp_w3, F_KP, kObjNewton, kGrpW8)                                \
+    X(po_newton_kpc, F_KPC, kObjNewton, kGrpLane)                               \
+    X(po_newton_k, F_K, kObjNewton, kGrpLane)                                   \
+    X(po_solve_kp_fix_uni, F_KP, kObjFixUni, kGrpLane)                          \
+    X(po_newton_kp_fix1, F_KP, kObjFixNewton1, kGrpLane)                        \
+    X(po_newton_kp_fix2, F_KP, kObjFixNewton2, kGrpLane)
+#if defined(PO_DEV_HEADLINE) && !defined(PO_ENTRY)  // `make dev` links three of the KP objects: the dispatcher built for it answers hipErrorNotSupported for the others
+#define PO_OBJECT_ATTR __attribute__((weak))
+#else
+#define PO_OBJECT_ATTR
+#endif
+#define PO_X(name, form, kind, groups) \
+    PO_OBJECT_ATTR hipError_t name(int launch, const po::Shape &s, size_t lds, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+PO_SOLVE_OBJECTS(PO_X)
+#undef PO_X
 
 // ---- po_post.hip: map stages, spline stages, the glue of po_plan ----
 hipError_t po_launch_postcheck(const po::DevMaps *m, const po::DevCar *c, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid,

@@ -1,6 +1,6 @@
 // po_solve_common.hpp — what every translation unit that sees the solve kernels shares: the per-path context, the fused solve kernel
-// (po_fast.inc) and its launch / shape-selection wrappers.  The instantiations themselves are compiled per formulation
-// (po_solve_form.hip, -DPO_FORM=0/1/2) so that the three sets build in parallel; po_kernels.hip holds the dispatcher.
+// (po_fast.inc), the selection of its shape and THE TABLE of the shapes that are instantiated.  The instantiations themselves are compiled in nineteen objects
+// (po_solve_form.hip; po_launch.hpp lists them) that build in parallel; po_kernels.hip holds the dispatcher.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 
 #include "../../include/po_hip.h"
 #include "po_device.hpp"
+#include "po_launch.hpp"
 #include "po_scale.hpp"
 
 namespace po {
@@ -89,7 +90,7 @@ struct Resid { double rp, rd, nAx, nz, nPx, nAty, rps, rds, nAxs, nzs, nPxs, nAt
 
 }  // namespace po
 
-// ---- launch wrappers used by the C ABI (po_capi.cpp) ----
+// ---- launch wrappers and the choice of a shape ----
 namespace po {
 template <class K> hipError_t launch_grid(K kern, const DevBatch *in, const DevParams *P, int grid, int nt, size_t lds, hipStream_t st) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -106,10 +107,6 @@ template <class K> hipError_t launch1(K kern, const DevBatch *in, const DevParam
 // thread-block shape: NT threads x SPL stages per thread must cover N, and NT >= C (one control per thread).
 // Two-level mode needs chunk == control group, or no held controls at all (K): one lane per chunk (SPL == keep, keep <= 5), or — round 5, keep 6 .. 8 — the
 // ROLE-SPLIT mapping: two lanes per chunk, SPL = ceil(keep / 2) stages each (nwx = 2; 3 when keep is odd), NT = 64 for up to 32 chunks, 128 for up to 64.
-// What an object answers for a shape it does not hold (the dispatcher in po_kernels.hip then asks the next object).  NOT hipErrorInvalidValue: that is a code a
-// genuine hipFuncSetAttribute / launch failure produces (e.g. an LDS size over the limit), and a real failure must reach the caller from the launch that failed
-// instead of being retried through the other objects.  launch1 / launch_grid never produce hipErrorNotSupported.
-constexpr hipError_t kNotMyShape = hipErrorNotSupported;
 struct Shape { int nt, spl; bool two; int nwx; };
 inline bool pick_shape(int form, int N, int C, int keep, Shape *s) {
     const bool no_u = (form == F_K);
@@ -155,203 +152,41 @@ inline bool resolve_shape(int form, int N, int C, int keep, Shape *s) {
 }
 // UNI = true: the uniform-row-class variant of the two-level kernels (no-op for shapes that use the single-level mapping and for K on multi-wave blocks); UNI = false: the general variant.  po_launch_solve issues them in this order on one stream.
 template <int F> inline bool has_uni_variant(const Shape &s) { return s.two && (F != F_K || s.nt == 64); }  // K: one-wave blocks only (Fast::classify)
-// the shapes of the two-level mapping that are instantiated: X(SPL, NT, NWX)
-#ifndef PO_SHAPE_GROUP
-#define PO_SHAPE_GROUP 0
-#endif
-#ifdef PO_DEV_HEADLINE  // dev builds: only the BASELINE config-3 variant (seconds to compile); -DPO_DEV_SPL=k -DPO_DEV_NWX=x: that one-wave variant instead
-#ifndef PO_DEV_SPL
-#define PO_DEV_SPL 4
-#endif
-#ifndef PO_DEV_NWX
-#define PO_DEV_NWX 1
-#endif
-#ifndef PO_DEV_NT
-#define PO_DEV_NT 64
-#endif
-#define PO_TWO_SHAPES(X) if (s.spl == PO_DEV_SPL && s.nt == PO_DEV_NT && s.nwx == PO_DEV_NWX) X(PO_DEV_SPL, PO_DEV_NT, PO_DEV_NWX);
-#else
-// (KP: keep 1 / 2 multi-group (4, ., 4 / 5), keep 3 / 4 / 5 one lane per chunk, keep 6 / 7 / 8 role-split; KPC: keep 4; K: 2 or 4 stages per lane)
-// -DPO_SHAPE_GROUP: which of KP's shapes an object holds (the dispatcher in po_kernels.hip asks the objects in turn; an object answers kNotMyShape / 0 for a shape it does not hold).
-//   0  the shapes of keep 1 .. 8 (the solve objects);  1 / 2 / 3  of those only one lane per chunk / role-split / multi-group (the Newton objects: as ONE object their 15 shapes x 3
-//   kernels were the 5-minute pole of the build);  7  the WIDE role-split shapes of keep 9 .. 16 (5 .. 8 stages per lane; solve objects `_w`);  4 / 5 / 6  of those only SPL 5, 6 / 7 / 8.
-#if PO_SHAPE_GROUP == 0 || PO_SHAPE_GROUP == 1
-#define PO_KP_SHAPES_A(X)                                                                                                           \
-        if (s.nwx == 1 && s.spl == 5) X(5, 64, 1);                                                                                  \
-        if (s.nwx == 1 && s.spl == 3 && s.nt == 64) X(3, 64, 1); if (s.nwx == 1 && s.spl == 3) X(3, 128, 1);                        \
-        if (s.nwx == 1 && s.spl == 4 && s.nt == 64) X(4, 64, 1); if (s.nwx == 1 && s.spl == 4) X(4, 128, 1);
-#else
-#define PO_KP_SHAPES_A(X)
-#endif
-#if PO_SHAPE_GROUP == 0 || PO_SHAPE_GROUP == 3
-#define PO_KP_SHAPES_C(X)                                                                                                           \
-        if (s.nwx == 4 && s.nt == 64) X(4, 64, 4); if (s.nwx == 4) X(4, 128, 4);                                                    \
-        if (s.nwx == 5 && s.nt == 64) X(4, 64, 5); if (s.nwx == 5) X(4, 128, 5);
-#else
-#define PO_KP_SHAPES_C(X)
-#endif
-#if PO_SHAPE_GROUP == 0 || PO_SHAPE_GROUP == 2
-#define PO_KP_SHAPES_B(X)                                                                                                           \
-        if (s.nwx == 2 && s.spl == 3 && s.nt == 64) X(3, 64, 2); if (s.nwx == 2 && s.spl == 3) X(3, 128, 2);                        \
-        if (s.nwx == 2 && s.spl == 4 && s.nt == 64) X(4, 64, 2); if (s.nwx == 2 && s.spl == 4) X(4, 128, 2);                        \
-        if (s.nwx == 3 && s.spl == 4 && s.nt == 64) X(4, 64, 3); if (s.nwx == 3 && s.spl == 4) X(4, 128, 3);
-#else
-#define PO_KP_SHAPES_B(X)
-#endif
-#define PO_WIDE_SPL(X, S_) if (s.nwx == 2 && s.spl == S_ && s.nt == 64) X(S_, 64, 2); if (s.nwx == 3 && s.spl == S_ && s.nt == 64) X(S_, 64, 3);
-#if PO_SHAPE_GROUP == 7 || PO_SHAPE_GROUP == 4
-#define PO_KP_SHAPES_W1(X) PO_WIDE_SPL(X, 5) PO_WIDE_SPL(X, 6)
-#else
-#define PO_KP_SHAPES_W1(X)
-#endif
-#if PO_SHAPE_GROUP == 7 || PO_SHAPE_GROUP == 5
-#define PO_KP_SHAPES_W2(X) PO_WIDE_SPL(X, 7)
-#else
-#define PO_KP_SHAPES_W2(X)
-#endif
-#if PO_SHAPE_GROUP == 7 || PO_SHAPE_GROUP == 6
-#define PO_KP_SHAPES_W3(X) PO_WIDE_SPL(X, 8)
-#else
-#define PO_KP_SHAPES_W3(X)
-#endif
-#define PO_TWO_SHAPES(X)                                                                                                            \
-    if constexpr (F == F_KP) {                                                                                                      \
-        PO_KP_SHAPES_A(X)                                                                                                           \
-        PO_KP_SHAPES_C(X)                                                                                                           \
-        PO_KP_SHAPES_B(X)                                                                                                           \
-        PO_KP_SHAPES_W1(X) PO_KP_SHAPES_W2(X) PO_KP_SHAPES_W3(X)                                                                    \
-    }                                                                                                                               \
-    if constexpr (F == F_K) {                                                                                                       \
-        if (s.nwx == 1 && s.spl == 2 && s.nt == 64) X(2, 64, 1);  /* (SPL 2 only for N <= 128: one wave) */                        \
-    }                                                                                                                               \
-    if constexpr (F != F_KP) {                                                                                                      \
-        if (s.nwx == 1 && s.spl == 4 && s.nt == 64) X(4, 64, 1); if (s.nwx == 1 && s.spl == 4) X(4, 128, 1);                        \
-    }
-#endif
-template <int F, bool UNI, int G = PO_SHAPE_GROUP> hipError_t launch_form(const DevBatch *in_, const DevParams *P, hipStream_t st, size_t *lds_out) {
-    Shape s;
-    if (!resolve_shape(F, in_->N, in_->C, in_->keep, &s)) return hipErrorInvalidValue;
-    const size_t lds = lds_of(F, in_->N, in_->C, s);
-    if (lds_out) *lds_out = lds;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    DevBatch copy = *in_;
-    copy.only_deferred = (!UNI && has_uni_variant<F>(s)) ? 1 : 0;
-    const DevBatch *in = &copy;
-    if constexpr (UNI) {
-        if (!has_uni_variant<F>(s)) return hipSuccess;
-    }
-    if (s.two) {
-#define PO_L(SPL_, NT_, NWX_) return launch1(&solve_kernel_fast<F, SPL_, NT_, true, UNI, NWX_>, in, P, NT_, lds, st)
-        PO_TWO_SHAPES(PO_L)
-#undef PO_L
-        return kNotMyShape;
-    }
-#if !defined(PO_DEV_HEADLINE) && PO_SHAPE_GROUP == 0  // (the single-level mapping lives in the objects of the keep 1 .. 8 shapes)
-    if constexpr (!UNI) {
-#define PO_L1(SPL_, NT_) return launch1(&solve_kernel_fast<F, SPL_, NT_, false, false, 1>, in, P, NT_, lds, st)
-        if (s.nt == 64 && s.spl == 2) PO_L1(2, 64);
-        if (s.nt == 64) PO_L1(4, 64);
-        if (s.nt == 128) PO_L1(4, 128);
-        if (s.spl == 2) PO_L1(2, 256);
-        PO_L1(4, 256);
-#undef PO_L1
-    }
-#endif
-    return kNotMyShape;
-}
-// ---- state block / polish (po_params.polish): same shape as the solve launch; two-level shapes only (every case the reference produces) ----
-template <int F, int SPL_, int NT_, int NWX_> inline int state_doubles_of() { return Fast<F, SPL_, NT_, true, NWX_>::kStateDoubles * NT_; }
-// doubles per path of the state block the solve kernels leave for the Newton refinement and the polish (0: shape without either: the single-level mapping)
-template <int F, int G = PO_SHAPE_GROUP> inline int polish_state_doubles(int N, int C, int keep) {
-    Shape s;
-    if (!resolve_shape(F, N, C, keep, &s) || !s.two) return 0;
-#define PO_X(SPL_, NT_, NWX_) return state_doubles_of<F, SPL_, NT_, NWX_>()
-    PO_TWO_SHAPES(PO_X)
+// ---- THE TABLE of the shapes that are instantiated: X(formulation, two-level, SPL, NT, NWX, group), one row per shape, matched by EQUALITY on (two, spl, nt, nwx): no
+// order, no default.  The group says which objects hold the row (po_launch.hpp: PO_SOLVE_OBJECTS lists the groups of every object; KPC and K: one object of each kind).
+// KP: keep 3 / 4 / 5 one lane per chunk, keep 1 / 2 multi-group (4, ., 4 / 5), keep 6 / 7 / 8 role-split, keep 9 .. 16 the WIDE role-split shapes (5 .. 8 stages per lane, one
+// wave; as ONE Newton object KP's shapes were the 5-minute pole of the build); KPC: keep 4; K: 2 (N <= 128: one wave) or 4 stages per lane; then the single-level mapping.
+// tests/test_shape_table.py reads the rows and compares them with the shapes pick_shape can return.
+#define PO_SHAPE_ROWS(X)                                                                                                            \
+    X(F_KP, true, 5, 64, 1, kGrpLane) X(F_KP, true, 3, 64, 1, kGrpLane) X(F_KP, true, 3, 128, 1, kGrpLane)                          \
+    X(F_KP, true, 4, 64, 1, kGrpLane) X(F_KP, true, 4, 128, 1, kGrpLane)                                                            \
+    X(F_KP, true, 4, 64, 4, kGrpMulti) X(F_KP, true, 4, 128, 4, kGrpMulti) X(F_KP, true, 4, 64, 5, kGrpMulti) X(F_KP, true, 4, 128, 5, kGrpMulti) \
+    X(F_KP, true, 3, 64, 2, kGrpSplit) X(F_KP, true, 3, 128, 2, kGrpSplit) X(F_KP, true, 4, 64, 2, kGrpSplit) X(F_KP, true, 4, 128, 2, kGrpSplit) \
+    X(F_KP, true, 4, 64, 3, kGrpSplit) X(F_KP, true, 4, 128, 3, kGrpSplit)                                                          \
+    X(F_KP, true, 5, 64, 2, kGrpW56) X(F_KP, true, 5, 64, 3, kGrpW56) X(F_KP, true, 6, 64, 2, kGrpW56) X(F_KP, true, 6, 64, 3, kGrpW56) \
+    X(F_KP, true, 7, 64, 2, kGrpW7) X(F_KP, true, 7, 64, 3, kGrpW7) X(F_KP, true, 8, 64, 2, kGrpW8) X(F_KP, true, 8, 64, 3, kGrpW8)  \
+    X(F_K, true, 2, 64, 1, kGrpLane) X(F_K, true, 4, 64, 1, kGrpLane) X(F_K, true, 4, 128, 1, kGrpLane)                             \
+    X(F_KPC, true, 4, 64, 1, kGrpLane) X(F_KPC, true, 4, 128, 1, kGrpLane)                                                          \
+    X(F_KP, false, 2, 64, 1, kGrpOne) X(F_KP, false, 4, 64, 1, kGrpOne) X(F_KP, false, 4, 128, 1, kGrpOne) X(F_KP, false, 2, 256, 1, kGrpOne) X(F_KP, false, 4, 256, 1, kGrpOne) \
+    X(F_KPC, false, 2, 64, 1, kGrpOne) X(F_KPC, false, 4, 64, 1, kGrpOne) X(F_KPC, false, 4, 128, 1, kGrpOne) X(F_KPC, false, 2, 256, 1, kGrpOne) X(F_KPC, false, 4, 256, 1, kGrpOne) \
+    X(F_K, false, 2, 64, 1, kGrpOne) X(F_K, false, 4, 64, 1, kGrpOne) X(F_K, false, 4, 128, 1, kGrpOne) X(F_K, false, 2, 256, 1, kGrpOne) X(F_K, false, 4, 256, 1, kGrpOne)
+constexpr bool is_shape(const Shape &s, bool two, int spl, int nt, int nwx) { return s.two == two && s.spl == spl && s.nt == nt && s.nwx == nwx; }
+// the group of the row that equals (form, s); 0: no row (nothing is instantiated for s)
+inline int group_of(int form, const Shape &s) {
+#define PO_X(F_, TWO_, SPL_, NT_, NWX_, G_) if (form == F_ && is_shape(s, TWO_, SPL_, NT_, NWX_)) return G_;
+    PO_SHAPE_ROWS(PO_X)
 #undef PO_X
     return 0;
 }
-// doubles per path of the block a PARKED Newton path lives in between the two sliced launches (Fast::park_io + kNwParkScalars)
-template <int F, int G = PO_SHAPE_GROUP> inline int newton_park_doubles(int N, int C, int keep) {
-    Shape s;
-    if (!resolve_shape(F, N, C, keep, &s) || !s.two) return 0;
-#define PO_X(SPL_, NT_, NWX_) return Fast<F, SPL_, NT_, true, NWX_>::kParkDoubles * NT_ + kNwParkScalars
-    PO_TWO_SHAPES(PO_X)
-#undef PO_X
-    return 0;
-}
-// the Newton refinement of round 0 as its own launch (po_params.refine = 2): same shapes.  FB: the fallback launch behind it
-// (newton_fallback_kernel walks the work list of the paths newton_kernel handed back; a small fixed grid)
-// (G: the object's shape group is part of the function's identity — three objects instantiate this template with three different bodies, and the linker would fold them into one)
-template <int F, bool FB, int G = PO_SHAPE_GROUP> hipError_t launch_newton(const DevBatch *in, const DevParams *P, hipStream_t st) {
-    Shape s;
-    if (!resolve_shape(F, in->N, in->C, in->keep, &s) || !s.two) return hipErrorInvalidValue;
-    const size_t lds = lds_of(F, in->N, in->C, s);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-#define PO_X(SPL_, NT_, NWX_) { if constexpr (FB) return launch_grid(&newton_fallback_kernel<F, SPL_, NT_, NWX_>, in, P, kFallbackGrid, NT_, lds, st); else if (in->nw_phase == 2) return launch1(&newton_kernel<F, SPL_, NT_, NWX_, 2>, in, P, NT_, lds, st); else return launch1(&newton_kernel<F, SPL_, NT_, NWX_, 1>, in, P, NT_, lds, st); }
-    PO_TWO_SHAPES(PO_X)
-#undef PO_X
-    return kNotMyShape;
-}
-// ---- the length-specialised kernels (Fast's NFIX): KP, the shape (SPL 4, NT 64, one lane per chunk), the lengths of the Makefile's PO_FIXED_N.  Objects of their own
-// (-DPO_FIX=1 the uniform warm start, 2 / 3 the first / second Newton launch), which get the list as -D'PO_FIXED_LIST(X)=X(200) ...'.  Everything else — the general
-// warm-start variant, newton_fallback_kernel, the polish, every other shape, ragged batches, unlisted lengths — runs the generic kernels; the layouts are the same.
-#ifdef PO_FIX
+// OSQP's polish: one-lane-per-chunk and multi-group shapes (the role-split shapes of keep 6 .. 16 have no polish kernel: status_polish stays 0 = not attempted, like the single-level mapping)
+constexpr bool has_polish_kernel(const Shape &s) { return s.two && s.nwx != 2 && s.nwx != 3; }
+// the length-specialised kernels (Fast's NFIX): KP, the shape (SPL 4, NT 64, one lane per chunk), the lengths of the Makefile's PO_FIXED_N (objects of their own, and
+// po_kernels.o, get the list as -D'PO_FIXED_LIST(X)=X(200) ...').  Everything else — the general warm-start variant, newton_fallback_kernel, the polish, every other
+// shape, ragged batches, unlisted lengths — runs the generic kernels; the layouts are the same.
 #ifndef PO_FIXED_LIST
 #define PO_FIXED_LIST(X)
 #endif
 constexpr int kFixSpl = 4, kFixNt = 64;
-// the batch is one the fixed instantiations are built for: KP's keep 4 on one lane per chunk, C what path_c() gives a path of N points; returns its LDS bytes (0: not that shape)
-static inline size_t fixed_shape_lds(int N, int C, int keep) {
-    Shape s;
-    if (keep != kFixSpl || C != (N + keep - 2) / keep || !resolve_shape(F_KP, N, C, keep, &s)) return 0;
-    if (!s.two || s.nt != kFixNt || s.spl != kFixSpl || s.nwx != 1) return 0;
-    const size_t lds = lds_of(F_KP, N, C, s);
-    return lds <= 160 * 1024 ? lds : 0;
-}
-#if PO_FIX == 1
-static inline bool has_fixed_length(int N, int C, int keep) {
-    if (!fixed_shape_lds(N, C, keep)) return false;
-#define PO_X(N_) if (N == N_) return true;
-    PO_FIXED_LIST(PO_X)
-#undef PO_X
-    return false;
-}
-static inline hipError_t launch_form_fixed(const DevBatch *in_, const DevParams *P, hipStream_t st, size_t *lds_out) {
-    const size_t lds = (in_->fixed_len && in_->n_points == nullptr) ? fixed_shape_lds(in_->N, in_->C, in_->keep) : 0;
-    if (!lds) return kNotMyShape;
-    DevBatch copy = *in_;
-    copy.only_deferred = 0;
-    const DevBatch *in = &copy;
-#define PO_X(N_) if (in->N == N_) { if (lds_out) *lds_out = lds; return launch1(&solve_kernel_fast<F_KP, kFixSpl, kFixNt, true, true, 1, N_>, in, P, kFixNt, lds, st); }
-    PO_FIXED_LIST(PO_X)
-#undef PO_X
-    return kNotMyShape;
-}
-#else
-template <int PH> static inline hipError_t launch_newton_fixed(const DevBatch *in, const DevParams *P, hipStream_t st) {
-    const size_t lds = (in->fixed_len && in->n_points == nullptr) ? fixed_shape_lds(in->N, in->C, in->keep) : 0;
-    if (!lds || (in->nw_phase == 2) != (PH == 2)) return kNotMyShape;
-#define PO_X(N_) if (in->N == N_) return launch1(&newton_kernel<F_KP, kFixSpl, kFixNt, 1, PH, N_>, in, P, kFixNt, lds, st);
-    PO_FIXED_LIST(PO_X)
-#undef PO_X
-    return kNotMyShape;
-}
-#endif
-#endif
-// OSQP's polish: one-lane-per-chunk shapes (the role-split shapes of keep 6 .. 8 have no polish kernel: status_polish stays 0 = not attempted, like the single-level mapping)
-template <int F> inline bool has_polish_kernel(int N, int C, int keep) {
-    Shape s;
-    return resolve_shape(F, N, C, keep, &s) && s.two && s.nwx != 2 && s.nwx != 3;
-}
-template <int F, int G = PO_SHAPE_GROUP> hipError_t launch_polish(const DevBatch *in, const DevParams *P, hipStream_t st) {
-    Shape s;
-    if (!resolve_shape(F, in->N, in->C, in->keep, &s) || !s.two) return hipErrorInvalidValue;
-    if (s.nwx == 2 || s.nwx == 3) return hipSuccess;
-    const size_t lds = lds_of(F, in->N, in->C, s);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-#define PO_X(SPL_, NT_, NWX_) { if constexpr (NWX_ != 2 && NWX_ != 3) return launch1(&polish_kernel<F, SPL_, NT_, NWX_>, in, P, NT_, lds, st); }
-    PO_TWO_SHAPES(PO_X)
-#undef PO_X
-    return kNotMyShape;
-}
+// the batch is one the fixed instantiations are built for: KP's keep 4 on one lane per chunk, C what path_c() gives a path of N points
+inline bool is_fixed_shape(int form, int N, int C, int keep, const Shape &s) { return form == F_KP && keep == kFixSpl && C == (N + keep - 2) / keep && is_shape(s, true, kFixSpl, kFixNt, 1); }
 }  // namespace po

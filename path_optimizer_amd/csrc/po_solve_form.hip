@@ -1,100 +1,102 @@
-// po_solve_form.hip — the kernel instantiations of ONE formulation (-DPO_FORM=0 KP, 1 KPC, 2 K) and ONE kind:
-//   -DPO_UNI=1 / 0            the solve kernels, uniform-row-class / general loop variant (the general object also holds the polish kernels);
-//   -DPO_UNI=0 -DPO_REF=3     the Newton refinement (po_params.refine = 2): newton_kernel + newton_fallback_kernel, nothing else.
-//   -DPO_FIX=1 / 2 / 3        KP only: the length-specialised kernels of the headline shape (Makefile: PO_FIXED_N) — the uniform warm start / the first / the second Newton launch.
-// Nineteen objects that build in parallel (KP: its shapes in groups — keep 1 .. 8 / the wide role-split shapes of keep 9 .. 16 — and the Newton refinement of each group by kind of shape).  -DPO_DEV_HEADLINE (dev builds only) keeps just one shape (po_solve_common.hpp).
+// po_solve_form.hip — the kernel instantiations of ONE object of po_launch.hpp's PO_SOLVE_OBJECTS (-DPO_ENTRY=<object>): the rows of po_solve_common.hpp's table whose
+// formulation and group the object holds, in the kind of kernel it holds —
+//   kObjUni / kObjGen    the solve kernels, uniform-row-class / general loop variant (the general object also holds the polish kernels);
+//   kObjNewton           the Newton refinement (po_params.refine = 2): newton_kernel + newton_fallback_kernel, nothing else (built with -DPO_REF=3: po_device.hpp);
+//   kObjFix...           KP only: the length-specialised kernels of the headline shape (Makefile: PO_FIXED_N) — the uniform warm start / the first / the second Newton launch.
+// Each object exports ONE entry, named like the object.  The dispatcher (po_kernels.hip) has resolved the shape and its LDS bytes and calls the one object that holds the
+// row; the entry launches the instance that EQUALS the shape, and answers hipErrorNotSupported when it has none.  -DPO_DEV_HEADLINE (dev builds only) keeps just one shape.
 #include "po_solve_common.hpp"
-#include "po_launch.hpp"
 
-#if !defined(PO_FORM) || !defined(PO_UNI)
-#error "compile with -DPO_FORM=0|1|2 -DPO_UNI=0|1"
+#ifndef PO_ENTRY
+#error "compile with -DPO_ENTRY=<an object of PO_SOLVE_OBJECTS (po_launch.hpp)>"
 #endif
-#define PO_CAT2(a, b) a##b
-#define PO_CAT(a, b) PO_CAT2(a, b)
-#if PO_FORM == 0
-#define PO_ENTRY_BASE po_launch_solve_kp
-#define PO_NEWTON_ENTRY po_launch_newton_kp
-#define PO_POLISH_ENTRY po_launch_polish_kp
-#define PO_POLISH_SIZE po_polish_state_doubles_kp
-#define PO_POLISH_HAS po_has_polish_kernel_kp
-#elif PO_FORM == 1
-#define PO_ENTRY_BASE po_launch_solve_kpc
-#define PO_NEWTON_ENTRY po_launch_newton_kpc
-#define PO_POLISH_ENTRY po_launch_polish_kpc
-#define PO_POLISH_SIZE po_polish_state_doubles_kpc
-#define PO_POLISH_HAS po_has_polish_kernel_kpc
-#else
-#define PO_ENTRY_BASE po_launch_solve_k
-#define PO_NEWTON_ENTRY po_launch_newton_k
-#define PO_POLISH_ENTRY po_launch_polish_k
-#define PO_POLISH_SIZE po_polish_state_doubles_k
-#define PO_POLISH_HAS po_has_polish_kernel_k
-#endif
-#ifndef PO_REF
-#define PO_REF 0
-#endif
-// entries of an object that holds only a group of KP's shapes (-DPO_SHAPE_GROUP, po_solve_common.hpp) carry the group's suffix
-#if PO_SHAPE_GROUP == 2
-#define PO_G(name) PO_CAT(name, _b)
-#elif PO_SHAPE_GROUP == 3
-#define PO_G(name) PO_CAT(name, _c)
-#elif PO_SHAPE_GROUP == 4
-#define PO_G(name) PO_CAT(name, _w1)
-#elif PO_SHAPE_GROUP == 5
-#define PO_G(name) PO_CAT(name, _w2)
-#elif PO_SHAPE_GROUP == 6
-#define PO_G(name) PO_CAT(name, _w3)
-#elif PO_SHAPE_GROUP == 7
-#define PO_G(name) PO_CAT(name, _w)
-#else
-#define PO_G(name) name
-#endif
+#define PO_STR2(x) #x
+#define PO_STR(x) PO_STR2(x)
 
-#ifdef PO_FIX  // the length-specialised kernels of KP's headline shape (po_solve_common.hpp): 1 the uniform warm start, 2 / 3 the first / second Newton launch
-#if PO_FORM != 0
-#error "-DPO_FIX: KP only"
-#endif
-#if PO_FIX == 1
-extern "C" hipError_t po_launch_solve_kp_fix_uni(const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out) { return po::launch_form_fixed(in, P, st, lds_out); }
-extern "C" int po_has_fixed_length_kp(int N, int C, int keep) { return po::has_fixed_length(N, C, keep) ? 1 : 0; }
-#elif PO_FIX == 2
-extern "C" hipError_t po_launch_newton_kp_fix1(const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return po::launch_newton_fixed<1>(in, P, st); }
-#else
-extern "C" hipError_t po_launch_newton_kp_fix2(const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return po::launch_newton_fixed<2>(in, P, st); }
-#endif
-#elif PO_REF == 3  // the Newton refinement as its own kernels: one object per formulation (KP: three + three for the wide shapes, by shape group)
-extern "C" hipError_t PO_G(PO_NEWTON_ENTRY)(const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return po::launch_newton<PO_FORM, false>(in, P, st); }
-extern "C" hipError_t PO_CAT(PO_G(PO_NEWTON_ENTRY), _fb)(const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return po::launch_newton<PO_FORM, true>(in, P, st); }
-#if defined(PO_DEV_HEADLINE) && PO_FORM == 0  // dev builds hold one shape in one object of each kind: the entries of the other groups answer "not mine"
-#define PO_STUB(name) extern "C" hipError_t name(const po::DevBatch *, const po::DevParams *, hipStream_t) { return po::kNotMyShape; }
-PO_STUB(po_launch_newton_kp_b) PO_STUB(po_launch_newton_kp_b_fb) PO_STUB(po_launch_newton_kp_c) PO_STUB(po_launch_newton_kp_c_fb)
-PO_STUB(po_launch_newton_kp_fix1) PO_STUB(po_launch_newton_kp_fix2)
-PO_STUB(po_launch_newton_kp_w1) PO_STUB(po_launch_newton_kp_w1_fb) PO_STUB(po_launch_newton_kp_w2) PO_STUB(po_launch_newton_kp_w2_fb) PO_STUB(po_launch_newton_kp_w3) PO_STUB(po_launch_newton_kp_w3_fb)
-#undef PO_STUB
-#endif
-#elif PO_UNI
-extern "C" hipError_t PO_CAT(PO_G(PO_ENTRY_BASE), _uni)(const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out) {
-    return po::launch_form<PO_FORM, true>(in, P, st, lds_out);
+namespace {  // (unnamed: every object instantiates these templates with a body of its own, and the linker would fold same-named ones into one)
+using namespace po;
+struct Object { int form, kind, groups; };
+constexpr bool same(const char *a, const char *b) { return *a == *b && (!*a || same(a + 1, b + 1)); }
+constexpr Object me() {
+#define PO_X(name, form, kind, groups) if (same(#name, PO_STR(PO_ENTRY))) return {form, kind, groups};
+    PO_SOLVE_OBJECTS(PO_X)
+#undef PO_X
+    return {-1, -1, 0};
 }
-#if defined(PO_DEV_HEADLINE) && PO_FORM == 0
-extern "C" hipError_t po_launch_solve_kp_w_uni(const po::DevBatch *, const po::DevParams *, hipStream_t, size_t *) { return po::kNotMyShape; }
-extern "C" hipError_t po_launch_solve_kp_fix_uni(const po::DevBatch *, const po::DevParams *, hipStream_t, size_t *) { return po::kNotMyShape; }
-extern "C" int po_has_fixed_length_kp(int, int, int) { return 0; }  // (dev builds hold no length-specialised kernel)
-#endif
+static_assert(me().form >= 0, "PO_ENTRY names no object of PO_SOLVE_OBJECTS");
+#ifdef PO_REF
+static_assert(me().kind == kObjNewton || me().kind == kObjFixNewton1 || me().kind == kObjFixNewton2, "-DPO_REF=3 is for the Newton objects");
 #else
-extern "C" hipError_t PO_G(PO_ENTRY_BASE)(const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out) {
-    return po::launch_form<PO_FORM, false>(in, P, st, lds_out);
+static_assert(me().kind != kObjNewton && me().kind != kObjFixNewton1 && me().kind != kObjFixNewton2, "the Newton objects build with -DPO_REF=3");
+#endif
+// does an object of groups G instantiate this row?  (dev builds: the one shape of -DPO_DEV_SPL / NT / NWX — default BASELINE config 3 — whatever its group)
+[[maybe_unused]] constexpr bool holds(int G, bool two, int spl, int nt, int nwx, int g) {
+#ifdef PO_DEV_HEADLINE
+#ifndef PO_DEV_SPL
+#define PO_DEV_SPL 4
+#endif
+#ifndef PO_DEV_NWX
+#define PO_DEV_NWX 1
+#endif
+#ifndef PO_DEV_NT
+#define PO_DEV_NT 64
+#endif
+    return two && spl == PO_DEV_SPL && nt == PO_DEV_NT && nwx == PO_DEV_NWX;
+#else
+    return (G & g) != 0;
+#endif
 }
-extern "C" int PO_G(PO_POLISH_SIZE)(int N, int C, int keep) { return po::polish_state_doubles<PO_FORM>(N, C, keep); }
-extern "C" int PO_CAT(PO_G(PO_POLISH_SIZE), _park)(int N, int C, int keep) { return po::newton_park_doubles<PO_FORM>(N, C, keep); }
-#if PO_SHAPE_GROUP == 0
-// the polish kernels of this formulation build with the general-variant object (the wide role-split shapes have none)
-extern "C" hipError_t PO_POLISH_ENTRY(const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return po::launch_polish<PO_FORM>(in, P, st); }
-extern "C" int PO_POLISH_HAS(int N, int C, int keep) { return po::has_polish_kernel<PO_FORM>(N, C, keep) ? 1 : 0; }
-#endif
-#if defined(PO_DEV_HEADLINE) && PO_FORM == 0
-extern "C" hipError_t po_launch_solve_kp_w(const po::DevBatch *, const po::DevParams *, hipStream_t, size_t *) { return po::kNotMyShape; }
-extern "C" int po_polish_state_doubles_kp_w(int, int, int) { return 0; }
-extern "C" int po_polish_state_doubles_kp_w_park(int, int, int) { return 0; }
-#endif
-#endif
+// K is one of: solve (UNI or not), Newton phase 1 / 2, fallback, polish.  F and G are template parameters so that every `if constexpr` below is DEPENDENT: a row the
+// object does not hold is discarded before its kernel is named, and instantiates nothing.
+template <int F, int G, bool UNI> hipError_t launch_rows(int launch, const Shape &s, size_t lds, const DevBatch *in, const DevParams *P, hipStream_t st) {
+#define PO_X(F_, TWO_, SPL_, NT_, NWX_, G_)                                                                                                     \
+    if constexpr (F == F_ && holds(G, TWO_, SPL_, NT_, NWX_, G_) && (TWO_ || !UNI)) {                                                           \
+        if (is_shape(s, TWO_, SPL_, NT_, NWX_)) return launch1(&solve_kernel_fast<F, SPL_, NT_, TWO_, TWO_ && UNI, NWX_>, in, P, NT_, lds, st); \
+    }
+    if (launch == kLaunchSolve) { PO_SHAPE_ROWS(PO_X) }
+#undef PO_X
+#define PO_X(F_, TWO_, SPL_, NT_, NWX_, G_)                                                                                                     \
+    if constexpr (!UNI && F == F_ && TWO_ && holds(G, TWO_, SPL_, NT_, NWX_, G_) && has_polish_kernel(Shape{NT_, SPL_, TWO_, NWX_})) {          \
+        if (is_shape(s, TWO_, SPL_, NT_, NWX_)) return launch1(&polish_kernel<F, SPL_, NT_, NWX_>, in, P, NT_, lds, st);                         \
+    }
+    if (launch == kLaunchPolish) { PO_SHAPE_ROWS(PO_X) }
+#undef PO_X
+    return hipErrorNotSupported;
+}
+// FB: the fallback launch behind the Newton launches (newton_fallback_kernel walks the work list of the paths newton_kernel handed back; a small fixed grid)
+template <int F, int G, bool FB> hipError_t launch_newton(const Shape &s, size_t lds, const DevBatch *in, const DevParams *P, hipStream_t st) {
+#define PO_X(F_, TWO_, SPL_, NT_, NWX_, G_)                                                                                                     \
+    if constexpr (F == F_ && TWO_ && holds(G, TWO_, SPL_, NT_, NWX_, G_)) {                                                                     \
+        if (is_shape(s, TWO_, SPL_, NT_, NWX_)) {                                                                                               \
+            if constexpr (FB) return launch_grid(&newton_fallback_kernel<F, SPL_, NT_, NWX_>, in, P, kFallbackGrid, NT_, lds, st);              \
+            else if (in->nw_phase == 2) return launch1(&newton_kernel<F, SPL_, NT_, NWX_, 2>, in, P, NT_, lds, st);                             \
+            else return launch1(&newton_kernel<F, SPL_, NT_, NWX_, 1>, in, P, NT_, lds, st);                                                    \
+        }                                                                                                                                       \
+    }
+    PO_SHAPE_ROWS(PO_X)
+#undef PO_X
+    return hipErrorNotSupported;
+}
+// the length-specialised kernels: the dispatcher has checked is_fixed_shape; a length that is not on the list is an error
+template <int F, int KIND> hipError_t launch_fixed(const DevBatch *in, const DevParams *P, size_t lds, hipStream_t st) {
+#define PO_X(N_)                                                                                                                                \
+    if (in->N == N_) {                                                                                                                          \
+        if constexpr (KIND == kObjFixUni) return launch1(&solve_kernel_fast<F, kFixSpl, kFixNt, true, true, 1, N_>, in, P, kFixNt, lds, st);    \
+        else return launch1(&newton_kernel<F, kFixSpl, kFixNt, 1, KIND == kObjFixNewton2 ? 2 : 1, N_>, in, P, kFixNt, lds, st);                 \
+    }
+    PO_FIXED_LIST(PO_X)
+#undef PO_X
+    return hipErrorNotSupported;
+}
+template <int F, int KIND, int G> hipError_t entry(int launch, const Shape &s, size_t lds, const DevBatch *in, const DevParams *P, hipStream_t st) {
+    if constexpr (KIND == kObjUni || KIND == kObjGen) return launch_rows<F, G, KIND == kObjUni>(launch, s, lds, in, P, st);
+    else if constexpr (KIND == kObjNewton) {
+        if (launch == kLaunchNewton) return launch_newton<F, G, false>(s, lds, in, P, st);
+        if (launch == kLaunchFallback) return launch_newton<F, G, true>(s, lds, in, P, st);
+        return hipErrorNotSupported;
+    } else return launch_fixed<F, KIND>(in, P, lds, st);
+}
+}  // namespace
+extern "C" hipError_t PO_ENTRY(int launch, const po::Shape &s, size_t lds, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
+    return entry<me().form, me().kind, me().groups>(launch, s, lds, in, P, st);
+}

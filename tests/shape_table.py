@@ -2,9 +2,10 @@
 
 A shape is (two, nt, spl, nwx): two-level or single-level mapping, threads per path, stages per lane and lane mapping (1 one lane per chunk, 2 / 3 role-split,
 4 / 5 multi-group; 1 on the single-level mapping).  Every two-level shape is its own instance of the solve, Newton, fallback and polish kernels, with its own
-register allocation, so every reachable shape needs a test that runs it.  tests/test_shape_table.py checks this twin against the library's host-side
-queries over every length; MATRIX below lists one row per reachable (formulation, shape) with its boundary lengths, and tests/test_shape_matrix.py runs every
-row against the oracle on the GPU.
+register allocation, so every reachable shape needs a test that runs it.  The library states the shapes it instantiates as data (PO_SHAPE_ROWS in
+po_solve_common.hpp: one row per shape, matched by equality, with the group of objects that holds it).  tests/test_shape_table.py checks this twin against the
+library's host-side queries over every length, and that table against the shapes the twin can reach; MATRIX below lists one row per reachable (formulation, shape)
+with its boundary lengths, and tests/test_shape_matrix.py runs every row against the oracle on the GPU.
 
 The LDS bytes of a shape are not restated: `lds_bytes` asks the library (po_lds_bytes, the size of the shape it resolved).  Where the library keeps the
 two-level shape that is the size of the candidate, which is what resolve_shape's fallback tests; at the lengths tested (2 .. 1100) the fallback to the

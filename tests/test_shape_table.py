@@ -1,6 +1,7 @@
 """CPU checks of the kernel-shape table (tests/shape_table.py): the Python twin of pick_shape / resolve_shape agrees with the library's host-side queries at every
-length, PO_TWO_SHAPES instantiates exactly the reachable two-level shapes and routes each one to its own instance, MATRIX (the rows tests/test_shape_matrix.py runs
-on the GPU) has a row for every reachable shape, and the largest accepted length of each formulation / keep is pinned."""
+length, the table PO_SHAPE_ROWS instantiates exactly the reachable two-level shapes and every reachable shape equals exactly one of its rows, the size and capability
+queries answer what they answered before the table, MATRIX (the rows tests/test_shape_matrix.py runs on the GPU) has a row for every reachable shape, and the largest
+accepted length of each formulation / keep is pinned."""
 import ctypes
 import functools
 import os
@@ -66,58 +67,50 @@ def test_twin_agrees_with_the_library_at_every_length(L, lds):
 
 
 def _instances():
-    """{form: [(guard, (spl, nt, nwx)), ...]} in dispatch order, parsed from the full build's PO_TWO_SHAPES (po_solve_common.hpp) with every shape group's macros expanded."""
-    src = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_solve_common.hpp")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S).replace("\\\n", " ")
-    defs = {}
-    for name, args, body in re.findall(r"^#define (PO_\w+)\(([^)]*)\)(.*)$", src, flags=re.M):
-        if "X(" in body or "PO_" in body:
-            defs.setdefault(name, []).append(([a.strip() for a in args.split(",")], body))
-    # PO_TWO_SHAPES: the full build's definition (the dev build's one-shape variant has no `if constexpr`); the group macros: their non-empty definitions
-    two = [b for _, b in defs.pop("PO_TWO_SHAPES") if "if constexpr" in b]
-    assert len(two) == 1
-
-    def expand(text, depth=0):
-        assert depth < 5
-        def sub(m):
-            name, actual = m.group(1), [a.strip() for a in m.group(2).split(",")]
-            if name not in defs:
-                return m.group(0)
-            (formal, body), = defs[name]
-            for f, a in zip(formal, actual):
-                body = re.sub(rf"\b{f}\b", a, body)
-            return expand(body, depth + 1)
-        return re.sub(r"\b(PO_\w+)\(([^()]*)\)", sub, text)
-
+    """{form: [(two, spl, nt, nwx, group), ...]}: the rows of PO_SHAPE_ROWS (po_solve_common.hpp), the table of the shapes the library instantiates."""
+    src = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_solve_common.hpp")).read().replace("\\\n", " ")
+    body, = re.findall(r"^#define PO_SHAPE_ROWS\(X\)(.*)$", src, flags=re.M)
+    rows = re.findall(r"X\(F_(KPC|KP|K), (true|false), (\d+), (\d+), (\d+), (kGrp\w+)\)", body)
+    assert len(rows) == body.count("X(") and rows, body
     out = {}
-    for cond, body in re.findall(r"if constexpr \(([^)]*)\)\s*\{([^{}]*)\}", two[0]):
-        body = expand(body)
-        stmts = re.findall(r"if \(([^)]*)\)\s*X\((\d+),\s*(\d+),\s*(\d+)\)\s*;", body)
-        assert len(stmts) == body.count("X("), body
-        for form in (S.KP, S.KPC, S.K):
-            if eval(cond, {"F": form, "F_KP": S.KP, "F_KPC": S.KPC, "F_K": S.K}):
-                out.setdefault(form, []).extend((g, tuple(int(v) for v in x)) for g, *x in stmts)
+    for form, two, spl, nt, nwx, group in rows:
+        out.setdefault({"KP": S.KP, "KPC": S.KPC, "K": S.K}[form], []).append((two == "true", int(spl), int(nt), int(nwx), group))
     return out
-
-
-def _routes(guard, shape):
-    _, nt, spl, nwx = shape
-    return eval(guard.replace("&&", " and ").replace("s.", ""), {"nt": nt, "spl": spl, "nwx": nwx})
 
 
 def test_two_level_instances_are_exactly_the_reachable_shapes(reach):
     inst = _instances()
     assert set(inst) == {S.KP, S.KPC, S.K}
-    for form, stmts in inst.items():
-        have = {(spl, nt, nwx) for _, (spl, nt, nwx) in stmts}
+    for form, rows in inst.items():
+        have = {(spl, nt, nwx) for two, spl, nt, nwx, _ in rows if two}
         want = {(spl, nt, nwx) for (f, (two, nt, spl, nwx)) in reach if f == form and two}
         assert have - want == set(), (S.FORM_NAMES[form], "instantiated but never reached (dead kernels in every kind of object):", sorted(have - want))
-        assert want - have == set(), (S.FORM_NAMES[form], "reachable but not instantiated (the launch answers not-my-shape):", sorted(want - have))
-        # the dispatch: the first guard a reachable shape satisfies names that very shape
+        assert want - have == set(), (S.FORM_NAMES[form], "reachable but not instantiated (the launch answers not-supported):", sorted(want - have))
+        # the dispatch is by equality: every reachable shape, single-level ones included, equals exactly one row, and no row appears twice
+        keys = [(two, nt, spl, nwx) for two, spl, nt, nwx, _ in rows]
+        assert len(set(keys)) == len(keys), (S.FORM_NAMES[form], sorted(k for k in set(keys) if keys.count(k) > 1))
         for (f, s) in reach:
-            if f == form and s[0]:
-                first = next((x for g, x in stmts if _routes(g, s)), None)
-                assert first == (s[2], s[1], s[3]), (S.FORM_NAMES[form], s, first)
+            if f == form:
+                assert keys.count(s) == 1, (S.FORM_NAMES[form], s)
+        # the single-level rows are pick_shape's five candidates
+        assert {(nt, spl) for two, nt, spl, nwx in keys if not two} == {(64, 2), (64, 4), (128, 4), (256, 2), (256, 4)}, S.FORM_NAMES[form]
+
+
+def test_size_and_capability_queries_are_pinned(L):
+    """The library's answers at every MATRIX row's boundary lengths and at the headline (KP, keep 4, N = 200) equal tests/golden/shape_queries.json, recorded with
+    tools/shape_query_dump.py from the library as it was before the shape table replaced the dispatch chains.  po_polish_state_doubles and po_newton_park_doubles size
+    device buffers: a value that comes out smaller is an out-of-bounds write on the GPU."""
+    import json
+    import sys
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import shape_query_dump as D
+
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "shape_queries.json")))
+    points = D.golden_points()
+    assert [tuple(r[:3]) for r in want] == points and (S.KP, 4, 200) in points
+    got = D.query(L, points)
+    assert got == want, [(g, w) for g, w in zip(got, want) if g != w][:5]
 
 
 def test_matrix_has_a_row_for_every_reachable_shape(reach, lds):

@@ -1,5 +1,5 @@
 """Dev tool: static instruction mix of the headline solve kernel per phase of one ADMM iteration.
-  hipcc -O3 -std=c++20 --offload-arch=gfx950 -ffp-contract=fast -fno-signed-zeros -fno-honor-nans -DPO_DEV_HEADLINE -DPO_FORM=0 -DPO_UNI=1 -DPO_MARKS \
+  hipcc -O3 -std=c++20 --offload-arch=gfx950 -ffp-contract=fast -fno-signed-zeros -fno-honor-nans -DPO_DEV_HEADLINE -DPO_ENTRY=po_solve_kp_uni -DPO_MARKS \
         -S --cuda-device-only -o /tmp/kdev.s path_optimizer_amd/csrc/po_solve_form.hip ; python tools/isa_phase_hist.py [/tmp/kdev.s]
 The PO_MARK comments (po_fast.inc) delimit the phases; loops (scan row carries) are counted once."""
 import re,collections,sys
