@@ -52,7 +52,12 @@ enum {
  * (reference touches only verbosity/warm_start, src/solver/solver.cpp:48-49; the rest are
  * OSQP defaults, except eps which this project's metric fixes at 1e-4). Immutable after po_create. */
 typedef struct po_params {
-    double d[4];            /* FLAGS_d1..d4: rear-axle -> covering-circle centre offsets          */
+    double d[4];            /* FLAGS_d1..d4: rear-axle -> covering-circle centre offsets.  NOT derived by the library: a caller that changes car_length or
+                               rear_axle_to_center sets d[j] = ((2 j - 3) / 8) * car_length + rear_axle_to_center itself (the reference's updateConfig,
+                               planning_flags.cpp:10-13); the path QP and po_bounds_batch* read d as given.  The covering-circle radius of po_bounds_batch* IS
+                               derived, from car_length, car_width and safety_margin (FLAGS_circle_radius, planning_flags.cpp:9), at every call.
+                               The vehicle fields (d, car_width, car_length, rear_axle_to_center, safety_margin) are not validated anywhere: a non-positive
+                               or NaN value is used as it stands and the results of the stages that read it are unspecified (tests/test_settings.py).     */
     double w_curv;          /* FLAGS_KP_curvature_weight       (10)                                */
     double w_curv_rate;     /* FLAGS_KP_curvature_rate_weight  (200)                               */
     double w_dev;           /* FLAGS_KP_deviation_weight       (0)                                 */
@@ -488,7 +493,7 @@ int po_postcheck_batch_device(po_handle h, int B, int N, const int *n_points, co
  * solved states, sampled every FLAGS_output_spacing with heading and curvature from the spline, each sample collision-checked; the walk
  * stops at the first colliding sample.  out_states [B][M][5]; n_out[b] samples kept; ok[b] as po_postcheck_batch (0 for an unsolved QP;
  * the reference dereferences back() of an empty vector when the very first sample collides: reported as ok = 0, n_out = 0);
- * n_out[b] = -2 when M is too small. */
+ * n_out[b] = -2 (and ok[b] = 0) when M is too small.  An output_spacing that is not positive (NaN included): PO_ERR_INVALID, no kernel launched, outputs not written. */
 int po_densify_batch(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int M, double *out_states, int *n_out,
                      int *ok);
 int po_densify_batch_device(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int M, double *out_states,
@@ -579,7 +584,10 @@ int po_limits_batch_device(po_handle h, int B, int N, const int *n_points, const
  * min-cost recursion and walk back from the cheapest node of the last reachable layer widening each node's rough corridor in 0.2 m
  * steps.  start [B][3] = start_state (x, y, heading).  Outputs, [B][L]: layer_s = layers_s_list_, lb / ub = layers_bounds_
  * (.first / .second); l0[b] = vehicle_l_wrt_smoothed_ref_; n_layers[b] = layers kept, -1 when the reference returns false (vehicle
- * further than the lateral range from the spline), -2 when more than L layers are needed.  These are the inputs of PO_SMOOTH_POST. */
+ * further than the lateral range from the spline), -2 when more than L layers are needed.  These are the inputs of PO_SMOOTH_POST.
+ * One wave carries the lateral samples of a layer: search_lateral_range, search_long_spacing or search_lat_spacing that is not positive (NaN included), or
+ * 2 * search_lateral_range / search_lat_spacing + 1 > 64, returns PO_ERR_UNSUPPORTED before any kernel is launched (the outputs are not written).  The number of
+ * samples is the reference's running sum from -range in steps of the spacing while <= range, at most 64. */
 int po_dp_search_batch(po_handle h, const po_spline_in *in, const double *start, int L, double *layer_s, double *lb, double *ub, double *l0,
                        int *n_layers);
 int po_dp_search_batch_device(po_handle h, const po_spline_in *in, const double *start, int L, double *layer_s, double *lb, double *ub,
@@ -616,9 +624,16 @@ int po_segment_init_batch_device(po_handle h, const po_spline_in *spline, const 
  *   hold the truncated path), 9 capacity (N / max_length too small or the QP does not fit the on-chip tile).
  *   max_length: upper bound of the waypoint polyline lengths (sizes the intermediate buffers); <= 0: computed from the waypoints
  *   (host-pointer entry only).
- *   Limits (the reference has none): max_length up to about 540 m (the spline stages keep 120 x knots bytes in LDS, knots = ceil(max_length) + 6 <= 546;
- *   beyond that the call returns PO_ERR_UNSUPPORTED for the whole batch); the path QP of an instance must fit the on-chip tile — at the default 0.15 ... 0.3 m
- *   re-sampling that is a route of roughly 75 m (keep_control_steps_ <= 4: N <= 512) to 150 m; longer instances come back with stage 9, the others are unaffected. */
+ *   Limits (the reference has none): max_length up to 316 m — the tension smoothing QP over ceil(max_length) + 6 points must fit the on-chip tile, which every size
+ *   up to 322 points does (TENSION2; some sizes up to 344 fit too; TENSION: 349); the spline stages, which keep 120 x knots bytes in LDS, would allow 546.
+ *   Beyond that the call returns PO_ERR_UNSUPPORTED for the whole batch, from the smoothing stage; the path QP of an instance must fit the on-chip tile — at the default 0.15 ... 0.3 m
+ *   re-sampling that is a route of roughly 75 m (keep_control_steps_ <= 4: N <= 512) to 150 m; longer instances come back with stage 9, the others are unaffected.
+ *   The lattice search inside the chain has room for max(ceil((max_length + 3) / search_long_spacing), 14) + 8 layers, as long as the post-smoothing QP over that
+ *   many layers fits the on-chip tile (473 layers at most): an instance that needs more (at search_long_spacing = 0.5 a route beyond about 230 m) comes back with
+ *   stage 9 as well, the others are unaffected.
+ *   Settings: the search refuses its settings as po_dp_search_batch* does (PO_ERR_UNSUPPORTED for the call).  With enable_raw_output the reference is re-sampled at
+ *   0.15 m / output_spacing: an output_spacing below 0.15, not positive or NaN is the reference's CHECK_LE(delta_s_smaller, delta_s_larger) and returns
+ *   PO_ERR_INVALID for the call — from the re-sampling stage, i.e. after the stages before it were enqueued; the outputs are unspecified then. */
 typedef struct po_plan_in {
     int B, W;
     const int    *n_way;          /* optional [B] */

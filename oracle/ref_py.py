@@ -182,6 +182,41 @@ def post_smooth(params, layer_s, lb, ub, l0, ks, kx, ky):
     return out
 
 
+# ---- the reference's gflags away from their defaults (tests/test_settings.py) ----
+# po_params field -> FLAGS_<name> of planning_flags.cpp (doubles only; the shim turns every flag into a plain exported global).
+FLAG_OF = dict(car_width="car_width", car_length="car_length", rear_axle_to_center="rear_axle_to_center", safety_margin="safety_margin",
+               search_lateral_range="search_lateral_range", search_long_spacing="search_longitudial_spacing", search_lat_spacing="search_lateral_spacing",
+               t2_w_dev="tension_2_deviation_weight", t2_w_curv="tension_2_curvature_weight", t2_w_curv_rate="tension_2_curvature_rate_weight",
+               cart_w_curv="cartesian_curvature_weight", cart_w_curv_rate="cartesian_curvature_rate_weight", cart_w_dev="cartesian_deviation_weight",
+               output_spacing="output_spacing", mu="mu", max_curvature_rate="max_curvature_rate")
+
+
+class flags_from:
+    """with ref_py.flags_from(p): ...   Sets the flags named in FLAG_OF from the po_params `p` in ALL THREE reference libraries (each is linked with its own copy
+    of planning_flags.cpp) and restores the previous values on exit.  The derived flags circle_radius and d1 .. d4 are written with their primaries — the reference
+    recomputes them only in updateConfig() — from the reference's own formulas, except that d1 .. d4 are taken from p.d, which a caller is expected to have set by
+    the same formula (po_hip.h at po_params.d)."""
+
+    def __init__(self, p):
+        v = {flag: float(getattr(p, field)) for field, flag in FLAG_OF.items()}
+        v["circle_radius"] = float(np.sqrt((p.car_length / 8) ** 2 + (p.car_width / 2) ** 2) + p.safety_margin)
+        v.update({f"d{j + 1}": float(p.d[j]) for j in range(4)})
+        self.values = v
+
+    def __enter__(self):
+        self.saved = []
+        for L in (lib(), lib_bounds(), lib_smooth()):
+            for flag, val in self.values.items():
+                g = C.c_double.in_dll(L, "FLAGS_" + flag)
+                self.saved.append((g, g.value))
+                g.value = val
+        return self
+
+    def __exit__(self, *a):
+        for g, val in reversed(self.saved):
+            g.value = val
+
+
 # ---- f-4: the reference's own graphSearchDp / buildReferenceFromSpline / updateLimits (same library) ----
 def dp_search(m_map, ks, kx, ky, length, start, cap=512):
     f = lambda a: np.ascontiguousarray(a, np.float64)

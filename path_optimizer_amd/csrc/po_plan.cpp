@@ -63,6 +63,18 @@ static bool plan_args_ok(po_handle h, const po_plan_in *in, const po_plan_out *o
     return in->B == 0 || (in->way_x && in->way_y && in->start && in->goal && out->states && out->n_states && out->ok);
 }
 
+// Layer capacity of the chain.  What the search may fill is the stride of postSmooth's QP, and that QP has to fit the on-chip tile: a capacity whose QP does not fit
+// made po_smooth_batch_device refuse the whole batch (at search_long_spacing = 0.5 from max_length = 213 m on; never at the default 1.5, whose capacities stay below
+// 370).  The footprint is not monotone in the size (chunk padding: 440 does not fit, 473 does), so: the smallest capacity >= want that fits, else the largest below
+// it.  An instance that needs more layers than that comes back from the search with -2, i.e. stage 9, and the others are unaffected.
+static int plan_layer_capacity(int want) {
+    const size_t tile = 160 * 1024;
+    want = std::min(want, 512);  // kDpMaxLayers of the search itself
+    for (int L = want; L <= 512; ++L) if (po_smooth_lds_bytes(PO_SMOOTH_POST, L) <= tile) return L;
+    for (int L = want - 1; L >= 4; --L) if (po_smooth_lds_bytes(PO_SMOOTH_POST, L) <= tile) return L;
+    return want;
+}
+
 static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_out *out) {
     if (!plan_args_ok(h, in, out)) return PO_ERR_INVALID;
     if (!(in->max_length > 0)) return PO_ERR_INVALID;  // the device entry cannot look at the waypoints
@@ -76,7 +88,8 @@ static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_o
     // capacities from the waypoint polyline length: a B-spline is never longer than its control polygon
     const double Lmax = in->max_length;
     const int M = (int)std::ceil(Lmax) + 6, P = (int)std::ceil(Lmax) + 6;
-    const int Lc = std::min(512, std::max((int)std::ceil((Lmax + 3) / prm->search_long_spacing), 14) + 8);  // layers every search_long_spacing (0.5 m when <= 6 m long)
+    if (!(prm->search_long_spacing > 0)) return PO_ERR_UNSUPPORTED;  // (what the search stage would answer; here it would size Lc)
+    const int Lc = plan_layer_capacity(std::max((int)std::ceil(std::min((Lmax + 3) / prm->search_long_spacing, 1e6)), 14) + 8);  // layers every search_long_spacing (0.5 m when <= 6 m long)
     const int N = in->N;
     const size_t bM = (size_t)B * M, bP = (size_t)B * P, bL = (size_t)B * Lc, bN = (size_t)B * N;
     const bool raw_out = prm->enable_raw_output != 0;
