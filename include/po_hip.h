@@ -796,6 +796,98 @@ typedef struct po_speed_out {
 int po_speed_batch(po_handle h, const po_speed_params *p, const po_speed_in *in, const po_speed_out *out);         /* host pointers, synchronous */
 int po_speed_batch_device(po_handle h, const po_speed_params *p, const po_speed_in *in, const po_speed_out *out);  /* device pointers, on the stream, no synchronisation */
 
+/* ---- moving obstacles: B timed paths against predicted agents (csrc/po_dynamic.hip) ----
+ * Every obstacle of the stages above is static, and nothing reads the t po_speed_batch* writes.  This stage takes B timed paths (states and po_speed_out.t) and,
+ * per instance, a SET of agents that move along piecewise-linear predicted trajectories; it computes the continuous-time closest approach between the six
+ * footprint circles and every agent of the set, reports the first conflict and writes the v_limit rows that make po_speed_batch* stop short of it.  out->v_limit
+ * has the layout of po_speed_in.v_limit and out->ok_out that of po_select_in.ok, so speed -> dynamic -> speed (yield) and speed -> dynamic -> select (prefer the
+ * conflict-free candidates) stay on one stream.  The stage reads no map and works on a handle without one.  The reference has no such stage.
+ *
+ * Definition (the bar is BIT equality).  Every operation is one rounded IEEE double operation in the order written, nothing contracted; sqrt and / are the
+ * correctly rounded ones; a comparison with a NaN is false; min(a, b) = b < a ? b : a; max(a, b) = b > a ? b : a.  n = n_states[b] clamped into [0, N] (N when
+ * NULL); row i = (x_i, y_i, z_i, k_i, s_i); t_i = t[b][i].  L(i) = v_limit_in[b][i], -1 when v_limit_in is NULL.
+ *   Not checked: status = 0, ok_out = 0, gap_min = DBL_MAX, first_state = first_agent = stop_state = -1, first_time = 0, every entry of the gap row DBL_MAX and
+ *       v_limit[i] = L(i) for every i < N, when ok[b] == 0, or n < 2, or any x, y, z or t of rows < n is non-finite.
+ *   Circle centres, per state i < n and circle q = 0 .. 5 (po_select_batch's, the bounding circle is not used):  cz = pcos(z_i), sz = psin(z_i);
+ *       gx_iq = (cx_q * cz - cy_q * sz) + x_i,  gy_iq = (cx_q * sz + cy_q * cz) + y_i.
+ *   The agents of path b: k = set_of[b] clamped into [0, S - 1] (0 when NULL); lo = first[k], hi = first[k + 1], each clamped into [0, n_agents]; agents lo .. hi - 1
+ *       of agents[], ascending (none when hi <= lo).  Agent a has np = n_pts points (T_j, X_j, Y_j), j < np, and radius R.  It covers nothing when np < 1, np > 8,
+ *       !(R >= 0), or any T_j, X_j, Y_j with j < np is non-finite.  Otherwise its pieces are, in this order:
+ *       before (flags & PO_AGENT_HOLD_BEFORE):  stationary at point 0 for all times <= T_0;
+ *       segment j = 0 .. np - 2:  D = T_{j+1} - T_j, skipped unless D > 0; linear in time on [T_j, T_{j+1}];
+ *       after (flags & PO_AGENT_HOLD_AFTER):  stationary at point np - 1 for all times >= T_{np-1}.
+ *   Interval i < n - 1 is CHECKED when dt = t_{i+1} - t_i > 0.  An interval of zero duration is skipped — so the states that share their time with a predecessor
+ *       are never reached, which is what makes a yielded profile (v = 0 from the stop state on) end at its stop — and so is one of negative duration.  What arrives
+ *       at a vehicle after it has stopped for good is outside this stage.
+ *   Per checked interval i and piece, the window [ta, tb] and the agent's positions (ax_a, ay_a) at ta and (ax_b, ay_b) at tb:
+ *       before:   ta = t_i;  tb = min(t_{i+1}, T_0);  both positions (X_0, Y_0).
+ *       segment:  ta = max(t_i, T_j);  tb = min(t_{i+1}, T_{j+1});  wa = (ta - T_j) / D, wb = (tb - T_j) / D;
+ *                 ax_a = X_j + wa * (X_{j+1} - X_j), ay_a = Y_j + wa * (Y_{j+1} - Y_j), and the same with wb for (ax_b, ay_b).
+ *       after:    ta = max(t_i, T_{np-1});  tb = t_{i+1};  both positions (X_{np-1}, Y_{np-1}).
+ *       The piece is skipped unless ta <= tb.  ua = (ta - t_i) / dt, ub = (tb - t_i) / dt.  Then for q = 0 .. 5:
+ *       ex_a = gx_iq + ua * (gx_{i+1,q} - gx_iq), ey_a = gy_iq + ua * (gy_{i+1,q} - gy_iq), and the same with ub for (ex_b, ey_b);
+ *       rax = ex_a - ax_a, ray = ey_a - ay_a, rbx = ex_b - ax_b, rby = ey_b - ay_b;   dx = rbx - rax, dy = rby - ray, px = -rax, py = -ray;
+ *       L2 = dx * dx + dy * dy, dot = px * dx + py * dy;   u = L2 > 0 ? dot / L2 : 0, then u = u < 0 ? 0 : u, then u = u > 1 ? 1 : u   (the form of select's e_i);
+ *       qx = px - u * dx, qy = py - u * dy;   dist = sqrt(qx * qx + qy * qy);   gap = (dist - cr_q) - R.
+ *   Reductions.  gap_i = DBL_MAX and arg_i = -1; then for every evaluation on interval i, agents ascending, pieces in the order above, q ascending:
+ *       if gap < gap_i: gap_i = gap, arg_i = a (the index into agents[]) — so arg_i is the agent with the smallest gap, the smallest index among equals.  gap_i stays
+ *       DBL_MAX for an interval that is not checked and for every i >= n - 1.  gap_min = the minimum of the gap_i (never a NaN and never -0: any order gives the
+ *       same bits).  f = the smallest i with gap_i < margin.  None: the path is FREE — status = 1, ok_out = 1, first_state = first_agent = stop_state = -1,
+ *       first_time = 0, v_limit[i] = L(i) for every i < N.  Otherwise first_state = f, first_agent = arg_f, first_time = t_f, ok_out = 0, and
+ *   the stop rule:  s_stop = s_f - stop_distance;  stop_state = j = the largest i <= f with s_i <= s_stop, 0 when there is none;  status = 3 when !(s_0 <= s_stop)
+ *       (the conflict is nearer than stop_distance), else 2;  v_limit[i] = 0 for j <= i < n and L(i) for every other i < N.
+ * Sets.  agents->first[S + 1]: set k = agents [first[k], first[k+1]).  Agents come in sets so that one call serves many vehicles or perception hypotheses, as the
+ *   map stack does; set_of is an argument and not the handle's map assignment because the stage reads no map — a caller who wants "the agents of my layer"
+ *   passes the same array to both.  Empty sets and n_agents = 0 are valid: every checked path is free.
+ * Return codes, both entries.  PO_ERR_INVALID: a NULL handle, struct or required pointer (B > 0: states, t, status, agents; inside agents: first, and agents when
+ *   n_agents > 0); a negative B, N, S or n_agents; S = 0 with B > 0; a margin that is not finite; a stop_distance that is negative or not finite.  The HOST entry
+ *   reads the lists and refuses, before it touches the handle: first[0] != 0, a decreasing first, first[S] > n_agents; a set_of[b] outside [0, S); an agent with
+ *   n_pts outside 1 .. 8, a negative or non-finite radius, a non-finite t, x or y among its points, t that is not strictly increasing, or unknown flag bits.
+ *   The DEVICE entry cannot look at the lists: its kernel reads set_of, first and n_pts as the definition says (clamped, or covering nothing), so a bad list
+ *   checks wrongly and never reads outside the buffers.  B = 0: PO_OK, nothing is launched and nothing is written — decided after the argument checks.
+ * `p`, `in->agents` (the struct) are host pointers in both entries; the arrays inside are device pointers for the device entry.  Deterministic: no atomics, no
+ * scratch, and a path's results depend neither on the batch size nor on its position in the batch.
+ * po_default_dynamic_params: {0.3, 5.0} — a starting point nobody has tuned. */
+#define PO_AGENT_MAX_PTS 8
+#define PO_AGENT_HOLD_BEFORE 1   /* present at (x[0], y[0]) for all times before t[0] */
+#define PO_AGENT_HOLD_AFTER  2   /* present at the last point for all times after the last t */
+typedef struct po_agent {        /* 208 bytes */
+    int n_pts, flags;            /* 1 .. PO_AGENT_MAX_PTS points; PO_AGENT_HOLD_* */
+    double radius;               /* >= 0 */
+    double t[PO_AGENT_MAX_PTS], x[PO_AGENT_MAX_PTS], y[PO_AGENT_MAX_PTS];  /* t strictly increasing */
+} po_agent;
+typedef struct po_agent_lists {
+    const po_agent *agents;      /* [n_agents] */
+    const int *first;            /* [S+1]: set k = agents [first[k], first[k+1]) */
+    int n_agents, S;
+} po_agent_lists;
+typedef struct po_dynamic_params {
+    double margin;               /* conflict <=> gap < margin; finite */
+    double stop_distance;        /* >= 0, finite: stop this far (arc length) before the conflict */
+} po_dynamic_params;
+void po_default_dynamic_params(po_dynamic_params *p);
+typedef struct po_dynamic_in {
+    int B, N;                    /* paths, rows per path (stride) */
+    const double *states;        /* [B][N][5] x, y, heading, k, s */
+    const int    *n_states;      /* optional [B] (NULL: N) */
+    const int    *ok;            /* optional [B] (NULL: all 1) */
+    const double *t;             /* [B][N]: po_speed_out.t */
+    const int    *set_of;        /* optional [B] (NULL: set 0): instance b meets agents [first[set_of[b]], first[set_of[b]+1]) */
+    const po_agent_lists *agents;
+    const double *v_limit_in;    /* optional [B][N], merged into v_limit */
+} po_dynamic_in;
+typedef struct po_dynamic_out {
+    int    *status;              /* [B] 0 not checked, 1 free, 2 conflict, 3 conflict nearer than stop_distance */
+    int    *ok_out;              /* optional [B]: status == 1, the layout of po_select_in.ok */
+    double *gap_min;             /* optional [B] */
+    int    *first_state, *first_agent, *stop_state; /* optional [B]; -1 when free */
+    double *first_time;          /* optional [B] */
+    double *gap;                 /* optional [B][N]: per interval, min over agents */
+    double *v_limit;             /* optional [B][N]: the layout of po_speed_in.v_limit */
+} po_dynamic_out;
+int po_dynamic_batch(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out);         /* host pointers, synchronous */
+int po_dynamic_batch_device(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -827,7 +919,8 @@ const char *po_last_hip_error(void);
  * entry and no field's meaning changed, so a binding written against 7 drives this library unchanged; one that needs the new entries looks the symbols up.  The
  * obstacle-list entries (po_obstacle, po_obstacle_lists, po_rasterize_batch*, po_set_map_stack_obstacles*) and the static-world entries (po_rings, po_scene, po_set_world_occupancy*, po_rasterize_scene_batch*, po_set_map_stack_scene*,
  * po_debug_get "world_cells") and the score-and-select entries (po_select_params, po_select_in, po_select_out, po_default_select_params, po_select_batch*) and
- * the speed-profile entries (po_speed_params, po_speed_in, po_speed_out, po_default_speed_params, po_speed_batch*) were added under 7 by the same rule.  A binding should compare
+ * the speed-profile entries (po_speed_params, po_speed_in, po_speed_out, po_default_speed_params, po_speed_batch*) and the moving-obstacle entries (po_agent, po_agent_lists, po_dynamic_params, po_dynamic_in, po_dynamic_out,
+ * po_default_dynamic_params, po_dynamic_batch*) were added under 7 by the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7
 const char *po_version(void);

@@ -155,3 +155,30 @@ class PoSpeedIn(C.Structure):
 
 class PoSpeedOut(C.Structure):
     _fields_ = [("v", C.c_void_p), ("a", C.c_void_p), ("t", C.c_void_p), ("total_time", C.c_void_p), ("status", C.c_void_p)]
+
+
+# ---- moving obstacles (po_dynamic_batch*) ----
+PO_AGENT_MAX_PTS, PO_AGENT_HOLD_BEFORE, PO_AGENT_HOLD_AFTER = 8, 1, 2
+
+
+class PoAgent(C.Structure):  # 208 bytes; binding.AGENT_DTYPE is the same layout as a numpy record
+    _fields_ = [("n_pts", C.c_int), ("flags", C.c_int), ("radius", C.c_double), ("t", C.c_double * PO_AGENT_MAX_PTS), ("x", C.c_double * PO_AGENT_MAX_PTS),
+                ("y", C.c_double * PO_AGENT_MAX_PTS)]
+
+
+class PoAgentLists(C.Structure):
+    _fields_ = [("agents", C.c_void_p), ("first", C.c_void_p), ("n_agents", C.c_int), ("S", C.c_int)]
+
+
+class PoDynamicParams(C.Structure):
+    _fields_ = [("margin", C.c_double), ("stop_distance", C.c_double)]
+
+
+class PoDynamicIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("t", C.c_void_p), ("set_of", C.c_void_p),
+                ("agents", C.POINTER(PoAgentLists)), ("v_limit_in", C.c_void_p)]
+
+
+class PoDynamicOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("ok_out", C.c_void_p), ("gap_min", C.c_void_p), ("first_state", C.c_void_p), ("first_agent", C.c_void_p),
+                ("stop_state", C.c_void_p), ("first_time", C.c_void_p), ("gap", C.c_void_p), ("v_limit", C.c_void_p)]

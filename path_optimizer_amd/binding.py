@@ -32,7 +32,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_set_world_occupancy", "po_set_world_occupancy_device", "po_rasterize_scene_batch", "po_rasterize_scene_batch_device",
            "po_set_map_stack_scene", "po_set_map_stack_scene_device",
            "po_default_select_params", "po_select_batch", "po_select_batch_device",
-           "po_default_speed_params", "po_speed_batch", "po_speed_batch_device"]
+           "po_default_speed_params", "po_speed_batch", "po_speed_batch_device",
+           "po_default_dynamic_params", "po_dynamic_batch", "po_dynamic_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -103,6 +104,10 @@ def lib():
         L.po_default_speed_params.restype = None
         L.po_speed_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_speed_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_default_dynamic_params.argtypes = [C.c_void_p]
+        L.po_default_dynamic_params.restype = None
+        L.po_dynamic_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_dynamic_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -137,6 +142,15 @@ def default_speed_params():
 
     p = PoSpeedParams()
     lib().po_default_speed_params(C.byref(p))
+    return p
+
+
+def default_dynamic_params():
+    """po_default_dynamic_params: margin and stop distance of po_dynamic_batch* (a starting point nobody has tuned)."""
+    from .abi import PoDynamicParams
+
+    p = PoDynamicParams()
+    lib().po_default_dynamic_params(C.byref(p))
     return p
 
 
@@ -214,6 +228,32 @@ def pack_obstacles(layers):
             obs[n] = o
             n += 1
     return obs, first
+
+
+# ---- moving agents (po_agent) ----
+AGENT_DTYPE = np.dtype([("n_pts", np.int32), ("flags", np.int32), ("radius", np.float64), ("t", np.float64, (8,)), ("x", np.float64, (8,)),
+                        ("y", np.float64, (8,))])  # po_agent, 208 bytes
+
+
+def pack_agents(sets):
+    """S sets of agents -> (agents [n_agents] of AGENT_DTYPE, first [S + 1] int32): set k owns agents[first[k]:first[k + 1]].  An agent is (radius, flags,
+    [(t, x, y), ...]) with 1 .. 8 points; flags are abi.PO_AGENT_HOLD_BEFORE / PO_AGENT_HOLD_AFTER.  A tuple (agents, first) that is packed already passes through.
+    Converted, not checked (a point list that is too long is refused here: it has no place in the record): the library checks."""
+    if isinstance(sets, tuple) and len(sets) == 2:
+        return np.ascontiguousarray(sets[0], dtype=AGENT_DTYPE).reshape(-1), np.ascontiguousarray(sets[1], dtype=np.int32).reshape(-1)
+    first = np.zeros(len(sets) + 1, dtype=np.int32)
+    first[1:] = np.cumsum([len(s) for s in sets])
+    agents = np.zeros(int(first[-1]), dtype=AGENT_DTYPE)
+    i = 0
+    for s in sets:
+        for radius, flags, pts in s:
+            if len(pts) > 8:
+                raise ValueError("an agent has at most 8 points (t, x, y)")
+            agents[i]["n_pts"], agents[i]["flags"], agents[i]["radius"] = len(pts), int(flags), radius
+            for j, (t, x, y) in enumerate(pts):
+                agents[i]["t"][j], agents[i]["x"][j], agents[i]["y"][j] = t, x, y
+            i += 1
+    return agents, first
 
 
 def pack_rings(shared, layers=None):
@@ -873,6 +913,46 @@ class Engine:
         so = PoSpeedOut(*[p(out, k) for k in ("v", "a", "t", "total_time", "status")])
         sp = params if params is not None else default_speed_params()
         _check(lib().po_speed_batch_device(self._h, C.byref(sp), C.byref(si), C.byref(so)))
+
+    # ---- moving obstacles: timed paths against predicted agents ----
+    DYNAMIC_KEYS = ("status", "ok_out", "gap_min", "first_state", "first_agent", "stop_state", "first_time", "gap", "v_limit")
+
+    def dynamic_batch(self, states, t, agents, n_states=None, ok=None, set_of=None, v_limit_in=None, params=None, want_rows=True):
+        """Host-pointer entry of po_dynamic_batch.  states [B,N,5], t [B,N] (speed_batch's t), agents: what pack_agents takes; optional n_states [B], ok [B],
+        set_of [B] (None: set 0), v_limit_in [B,N].  Returns a dict: status, ok_out, first_state, first_agent, stop_state [B] i32, gap_min, first_time [B], gap and
+        v_limit [B,N] (None without want_rows)."""
+        from .abi import PoAgentLists, PoDynamicIn, PoDynamicOut
+
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        B, N = states.shape[0], states.shape[1]
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        tt, vin = f(t), f(v_limit_in)
+        ns, okk, so = _i32(n_states), _i32(ok), _i32(set_of)
+        ag, first = pack_agents(agents)
+        lists = PoAgentLists(_np(ag) if len(ag) else None, _np(first), len(ag), len(first) - 1)
+        di = PoDynamicIn(B, N, _np(states), _np(ns), _np(okk), _np(tt), _np(so), C.pointer(lists), _np(vin))
+        i32 = lambda: np.zeros(B, dtype=np.int32)
+        r = {"status": i32(), "ok_out": i32(), "gap_min": np.zeros(B), "first_state": i32(), "first_agent": i32(), "stop_state": i32(), "first_time": np.zeros(B),
+             "gap": np.zeros((B, N)) if want_rows else None, "v_limit": np.zeros((B, N)) if want_rows else None}
+        do = PoDynamicOut(*[_np(r[k]) for k in self.DYNAMIC_KEYS])
+        dp = params if params is not None else default_dynamic_params()
+        _check(lib().po_dynamic_batch(self._h, C.byref(dp), C.byref(di), C.byref(do)))
+        return r
+
+    def dynamic_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: states [B,N,5] f64, t [B,N] f64, agents (a uint8 tensor over AGENT_DTYPE records, or None when there are none), first [S+1] i32
+        (+ n_states, ok, set_of i32 [B], v_limit_in [B,N]); out: status [B] i32 (+ any of DYNAMIC_KEYS).  Enqueued on the handle's stream, no synchronisation."""
+        from .abi import PoAgentLists, PoDynamicIn, PoDynamicOut
+
+        B, N = t["states"].shape[0], t["states"].shape[1]
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        ag = t.get("agents")
+        n_agents = 0 if ag is None else ag.numel() * ag.element_size() // AGENT_DTYPE.itemsize
+        lists = PoAgentLists(p(t, "agents") if n_agents else None, p(t, "first"), n_agents, t["first"].shape[0] - 1)
+        di = PoDynamicIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "t"), p(t, "set_of"), C.pointer(lists), p(t, "v_limit_in"))
+        do = PoDynamicOut(*[p(out, k) for k in self.DYNAMIC_KEYS])
+        dp = params if params is not None else default_dynamic_params()
+        _check(lib().po_dynamic_batch_device(self._h, C.byref(dp), C.byref(di), C.byref(do)))
 
     def map_sample(self, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)

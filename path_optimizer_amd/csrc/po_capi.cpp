@@ -1359,6 +1359,90 @@ int po_speed_batch(po_handle h, const po_speed_params *p, const po_speed_in *in,
     return S.copy_out(h);
 }
 
+// ---- moving obstacles (po_dynamic.hip) ----------------------------------------------------------
+void po_default_dynamic_params(po_dynamic_params *p) {
+    if (!p) return;
+    *p = po_dynamic_params{0.3, 5.0};  // a starting point nobody has tuned
+}
+
+// What both entries can check without reading through a pointer of the structs (testable without a GPU)
+static bool dynamic_args_ok(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0) return false;
+    if (!std::isfinite(p->margin) || !std::isfinite(p->stop_distance) || p->stop_distance < 0) return false;
+    const po_agent_lists *L = in->agents;
+    if (L && (L->S < 0 || L->n_agents < 0)) return false;
+    if (in->B == 0) return true;
+    if (!in->states || !in->t || !out->status || !L) return false;
+    return L->S >= 1 && L->first && (L->n_agents == 0 || L->agents);
+}
+// The host entry reads the lists themselves: everything the device entry can only clamp is refused here, before the handle is touched
+static bool dynamic_lists_ok(const po_dynamic_in *in) {
+    const po_agent_lists *L = in->agents;
+    if (L->first[0] != 0) return false;
+    for (int k = 0; k < L->S; ++k)
+        if (L->first[k + 1] < L->first[k]) return false;
+    if (L->first[L->S] > L->n_agents) return false;
+    if (in->set_of)
+        for (int b = 0; b < in->B; ++b)
+            if (in->set_of[b] < 0 || in->set_of[b] >= L->S) return false;
+    for (int i = 0; i < L->n_agents; ++i) {
+        const po_agent &g = L->agents[i];
+        if (g.n_pts < 1 || g.n_pts > PO_AGENT_MAX_PTS || (g.flags & ~(PO_AGENT_HOLD_BEFORE | PO_AGENT_HOLD_AFTER))) return false;
+        if (!std::isfinite(g.radius) || g.radius < 0) return false;
+        for (int j = 0; j < g.n_pts; ++j) {
+            if (!std::isfinite(g.t[j]) || !std::isfinite(g.x[j]) || !std::isfinite(g.y[j])) return false;
+            if (j > 0 && !(g.t[j] > g.t[j - 1])) return false;
+        }
+    }
+    return true;
+}
+
+int po_dynamic_batch_device(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out) {
+    if (!dynamic_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing to check: no launch, whatever the handle holds
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    po::DevDynamic D{};
+    D.B = in->B; D.N = in->N; D.S = in->agents->S; D.n_agents = in->agents->n_agents;
+    D.states = in->states; D.n_states = in->n_states; D.ok = in->ok; D.t = in->t; D.set_of = in->set_of;
+    D.agents = in->agents->agents; D.first = in->agents->first; D.v_limit_in = in->v_limit_in;
+    D.margin = p->margin; D.stop_distance = p->stop_distance;
+    D.status = out->status; D.ok_out = out->ok_out; D.gap_min = out->gap_min; D.first_state = out->first_state; D.first_agent = out->first_agent;
+    D.stop_state = out->stop_state; D.first_time = out->first_time; D.gap = out->gap; D.v_limit = out->v_limit;
+    const po::DevCar car = make_car(h->params);
+    HIP_TRY(po_launch_dynamic(&car, &D, h->stream));
+    return PO_OK;
+}
+
+int po_dynamic_batch(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out) {
+    if (!dynamic_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
+    if (!dynamic_lists_ok(in)) return PO_ERR_INVALID;
+    const po_agent_lists *L = in->agents;
+    const size_t B = in->B, bn = B * (size_t)in->N;
+    Stage S;
+    const Slot<double> states = S.in(in->states, 5 * bn), t = S.in(in->t, bn), vin = S.in(in->v_limit_in, bn);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B), first = S.in(L->first, (size_t)L->S + 1);
+    const Slot<po_agent> agents = S.in(L->n_agents > 0 ? L->agents : nullptr, (size_t)L->n_agents);
+    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernel skips it
+    auto opt_i = [&](int *host) { return host ? S.out(host, B) : Slot<int>{}; };
+    auto opt_d = [&](double *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<double>{}; };
+    const Slot<int> status = S.out(out->status, B), ok_out = opt_i(out->ok_out), fs = opt_i(out->first_state), fa = opt_i(out->first_agent), ss = opt_i(out->stop_state);
+    const Slot<double> gmin = opt_d(out->gap_min, B), ft = opt_d(out->first_time, B), gap = opt_d(out->gap, bn), vl = opt_d(out->v_limit, bn);
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        HIP_TRY(hipSetDevice(h->device));
+        PO_TRY(S.upload(h, h->post_buf));
+    }
+    const po_agent_lists dl{agents, first, L->n_agents, L->S};
+    const po_dynamic_in d{in->B, in->N, states, ns, ok, t, set_of, &dl, vin};
+    const po_dynamic_out o{status, ok_out, gmin, fs, fa, ss, ft, gap, vl};
+    PO_TRY(po_dynamic_batch_device(h, p, &d, &o));
+    std::lock_guard<std::mutex> g(h->mu);
+    return S.copy_out(h);
+}
+
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------
 static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bounds, const int *n_valid) {
     if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return false;

@@ -118,6 +118,17 @@ struct DevSpeed {
     int *status;
 };
 
+// moving-obstacle launch arguments (po_dynamic.hip): po_dynamic_in / po_dynamic_out with the lists of po_agent_lists flattened, and the two
+// knobs of po_dynamic_params.  Every output but status may be null.
+struct DevDynamic {
+    int B, N, S, n_agents;
+    const double *states; const int *n_states, *ok; const double *t; const int *set_of;
+    const po_agent *agents; const int *first;
+    const double *v_limit_in;
+    double margin, stop_distance;
+    int *status, *ok_out; double *gap_min; int *first_state, *first_agent, *stop_state; double *first_time, *gap, *v_limit;
+};
+
 #ifdef PO_MAP_DEVICE_CODE  // kernels and device functions: po_kernels.hip only (po_capi.cpp needs just the structs)
 // Layer k of the stack as a DevMap.  k is clamped into [0, M - 1] HERE, where it is read: a table that arrived through a device pointer was never validated, and a
 // bad entry must select a wrong layer, never an address outside the stack.

@@ -1,0 +1,871 @@
+"""Moving obstacles: po_dynamic_batch* (csrc/po_dynamic.hip; include/po_hip.h states the definition).
+
+Every gap, index, status and v_limit entry is a fixed sequence of rounded IEEE double operations, so every comparison with the device here is BIT equality on byte
+views against tests/dynamic_ref.py (numpy, one ufunc per operation).  The only tolerance is CLOSED_TOL of the closed forms, derived at its definition below.
+
+CPU: the reference against a scalar loop over the definition, closed forms (a static disc beside a path, a crossing whose closest approach falls inside an interval,
+an agent that has passed before the ego arrives), properties of the reference on random inputs, the yield closure speed -> dynamic -> speed -> dynamic on the two
+references, exports and the ABI mirror, argument checks without a device, the kernel's chunk constant, the host mirror's header and test program compile and link.
+GPU: path lengths around one and two waves of intervals, agent counts around the LDS chunk, batch sizes, position in the batch, sets, every kind of piece with piece
+boundaries on state times, zero and negative durations, a conflict on interval 0, the margin one ulp either side of a gap, index ties, status-0 triggers, NULL
+optional outputs, empty calls, the yield chain and the select chain on one stream, the C++ mirror's program against the Python call, host validation."""
+import ctypes
+import math
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import dynamic_ref
+import select_ref
+import speed_ref
+from path_optimizer_amd import abi, binding
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_ENTRIES = ["po_default_dynamic_params", "po_dynamic_batch", "po_dynamic_batch_device"]
+KEYS = ("status", "ok_out", "gap_min", "first_state", "first_agent", "stop_state", "first_time", "gap", "v_limit")
+DBL_MAX = select_ref.DBL_MAX
+BEFORE, AFTER = abi.PO_AGENT_HOLD_BEFORE, abi.PO_AGENT_HOLD_AFTER
+DYN_CHUNK = 32  # kDynChunk of po_dynamic.hip: agents per LDS chunk
+# The closed forms.  A gap is reached from the inputs through at most 32 roundings (centre 3, interpolation 2, relative vector 1, difference 1, L2 and dot 3 each,
+# quotient 1, closest point 2 per axis, squares and sum 3, sqrt 1, two subtractions; the window parameters add 2 each), every one on a quantity of magnitude
+# below 64 m (the cases below keep all coordinates inside +-32 m), so below 2^-53 * 64 each.  No cancellation amplifies them: every step is Lipschitz 1 in its inputs
+# (u is clamped into [0, 1] and multiplies a difference shorter than one interval).
+CLOSED_TOL = 32 * 2.0 ** -53 * 64
+
+
+def test_boundary_cases_follow_the_kernel_constant():
+    """The agent counts below are built from DYN_CHUNK: it must be the kernel's own constant."""
+    src = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_dynamic.hip")).read()
+    assert int(re.search(r"constexpr int kDynChunk = (\d+);", src).group(1)) == DYN_CHUNK
+
+
+def same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def assert_same(got, want, keys=KEYS, tag=""):
+    for k in keys:
+        if not same(got[k], want[k]):
+            g, w = np.asarray(got[k]), np.asarray(want[k])
+            assert g.shape == w.shape and g.dtype == w.dtype, (tag, k, g.shape, w.shape, g.dtype, w.dtype)
+            bad = np.flatnonzero((g.view(np.uint8).reshape(len(g), -1) != w.view(np.uint8).reshape(len(w), -1)).any(axis=1))
+            raise AssertionError(f"{tag} {k}: paths {bad[:8]} differ; got {g[bad[0]]} want {w[bad[0]]}")
+
+
+def params_of(margin=None, stop_distance=None):
+    dp = binding.default_dynamic_params()
+    if margin is not None:
+        dp.margin = margin
+    if stop_distance is not None:
+        dp.stop_distance = stop_distance
+    return dp
+
+
+def straight(n, ds, v=2.0, y=0.0, N=None):
+    """One straight path along +x from the origin at constant speed v: states [1, N, 5] and t [1, N]."""
+    N = N or n
+    st, t = np.zeros((1, N, 5)), np.zeros((1, N))
+    st[0, :n, 0] = ds * np.arange(n); st[0, :n, 1] = y; st[0, :n, 4] = ds * np.arange(n)
+    t[0, :n] = (ds * np.arange(n)) / v
+    return st, t
+
+
+def disc(x, y, r, flags=BEFORE | AFTER, t=0.0):
+    return (r, flags, [(t, x, y)])
+
+
+def make_paths(seed, B, N, ds=0.3, box=4.0):
+    """B smooth paths of N states around the origin with times that increase by 0.05 .. 0.3 s a state."""
+    rng = np.random.default_rng([26, seed])
+    st, t = np.zeros((B, N, 5)), np.zeros((B, N))
+    for b in range(B):
+        step = ds * rng.uniform(0.7, 1.3, N - 1) if N > 1 else np.zeros(0)
+        s = np.concatenate(([0.0], np.cumsum(step)))
+        k = rng.uniform(0, 0.15) * np.sin(s / rng.uniform(3, 9) + rng.uniform(0, 6.28))
+        z = rng.uniform(-math.pi, math.pi) + np.concatenate(([0.0], np.cumsum(0.5 * (k[1:] + k[:-1]) * step)))
+        x = rng.uniform(-box, box) + np.concatenate(([0.0], np.cumsum(np.cos(z[:-1]) * step)))
+        y = rng.uniform(-box, box) + np.concatenate(([0.0], np.cumsum(np.sin(z[:-1]) * step)))
+        st[b] = np.stack([x, y, z, k, s], axis=1)
+        t[b] = np.concatenate(([0.0], np.cumsum(rng.uniform(0.05, 0.3, N - 1)))) if N > 1 else 0.0
+    return st, t
+
+
+def random_agents(rng, count, box=8.0, horizon=8.0):
+    """Agents with 1 .. 8 points, every flag combination, radii 0.1 .. 0.8, walking about the box within the horizon."""
+    out = []
+    for _ in range(count):
+        npts = int(rng.integers(1, 9))
+        tt = rng.uniform(-1.0, horizon / 2) + np.concatenate(([0.0], np.cumsum(rng.uniform(0.2, horizon / 8, npts - 1))))
+        x = rng.uniform(-box, box) + np.concatenate(([0.0], np.cumsum(rng.uniform(-2, 2, npts - 1))))
+        y = rng.uniform(-box, box) + np.concatenate(([0.0], np.cumsum(rng.uniform(-2, 2, npts - 1))))
+        out.append((rng.uniform(0.1, 0.8), int(rng.integers(0, 4)), list(zip(tt, x, y))))
+    return out
+
+
+def random_case(seed, B, N, per_set=(5, 0, 9), ragged=True, limits=True):
+    """Ragged timed paths, S sets of agents, a set per path, a v_limit_in with negative and NaN entries."""
+    rng = np.random.default_rng([27, seed])
+    st, t = make_paths(seed, B, N)
+    n = rng.integers(0, N + 1, B).astype(np.int32) if ragged else np.full(B, N, dtype=np.int32)
+    n[rng.integers(0, B)] = N
+    sets = [random_agents(rng, c) for c in per_set]
+    set_of = rng.integers(0, len(per_set), B).astype(np.int32)
+    c = dict(states=st, t=t, n_states=n, agents=binding.pack_agents(sets), set_of=set_of)
+    if limits:
+        lim = rng.uniform(1, 9, (B, N))
+        lim[rng.random((B, N)) < 0.5] = -1.0
+        lim[rng.random((B, N)) < 0.1] = np.nan
+        c["v_limit_in"] = lim
+    return c
+
+
+def ref(oracle, dp=None, **c):
+    c = dict(c)
+    agents, first = binding.pack_agents(c.pop("agents"))
+    return dynamic_ref.check(oracle.default_params(), c.pop("states"), c.pop("t"), agents, first, dp or params_of(), **c)
+
+
+# ---------------------------------------------------------------- CPU ----------------------------------------------------------------
+def _scalar_check(params, st, t, n, okb, agents, first, k, lim, margin, stop_distance):
+    """The definition as a plain scalar Python loop over ONE path (Python floats are IEEE doubles; every operation rounds once).  st [N, 5], t [N]."""
+    N = len(st)
+    n = min(max(int(n), 0), N)
+    L = [-1.0 if lim is None else float(v) for v in (lim if lim is not None else range(N))]
+    out = dict(status=0, ok_out=0, gap_min=DBL_MAX, first_state=-1, first_agent=-1, stop_state=-1, first_time=0.0, gap=[DBL_MAX] * N, v_limit=list(L))
+    fin = lambda v: abs(v) <= DBL_MAX
+    mn = lambda a, b: b if b < a else a
+    mx = lambda a, b: b if b > a else a
+    x, y, z, _, s = ([float(v) for v in st[:n, c]] for c in range(5))
+    tt = [float(v) for v in t[:n]]
+    if okb == 0 or n < 2 or not all(fin(v) for v in x + y + z + tt):
+        return out
+    T = select_ref.trig_lib()
+    cx, cy, cr = ([float(v) for v in arr] for arr in select_ref.car_circles(params))
+    gx, gy = [], []
+    for i in range(n):
+        cz, sz = T.po_oracle_pcos(z[i]), T.po_oracle_psin(z[i])
+        gx.append([(cx[q] * cz - cy[q] * sz) + x[i] for q in range(6)])
+        gy.append([(cx[q] * sz + cy[q] * cz) + y[i] for q in range(6)])
+    S, n_agents = len(first) - 1, len(agents)
+    cl = lambda v, hi: min(max(int(v), 0), hi)
+    k = cl(k, S - 1)
+    lo, hi = cl(first[k], n_agents), cl(first[k + 1], n_agents)
+    arg = [-1] * N
+    for i in range(n - 1):
+        dt = tt[i + 1] - tt[i]
+        if not dt > 0:
+            continue
+        for a in range(lo, hi):
+            ag = agents[a]
+            npts, R, flags = int(ag["n_pts"]), float(ag["radius"]), int(ag["flags"])
+            if npts < 1 or npts > 8 or not R >= 0:
+                continue
+            AT, AX, AY = ([float(v) for v in ag[f][:npts]] for f in ("t", "x", "y"))
+            if not all(fin(v) for v in AT + AX + AY):
+                continue
+            pieces = ([-1] if flags & 1 else []) + list(range(npts - 1)) + ([npts - 1] if flags & 2 else [])
+            for p in pieces:
+                if p < 0:
+                    ta, tb = tt[i], mn(tt[i + 1], AT[0])
+                    pa = pb = (AX[0], AY[0])
+                elif p == npts - 1:
+                    ta, tb = mx(tt[i], AT[p]), tt[i + 1]
+                    pa = pb = (AX[p], AY[p])
+                else:
+                    D = AT[p + 1] - AT[p]
+                    if not D > 0:
+                        continue
+                    ta, tb = mx(tt[i], AT[p]), mn(tt[i + 1], AT[p + 1])
+                    wa, wb = (ta - AT[p]) / D, (tb - AT[p]) / D
+                    pa = (AX[p] + wa * (AX[p + 1] - AX[p]), AY[p] + wa * (AY[p + 1] - AY[p]))
+                    pb = (AX[p] + wb * (AX[p + 1] - AX[p]), AY[p] + wb * (AY[p + 1] - AY[p]))
+                if not ta <= tb:
+                    continue
+                ua, ub = (ta - tt[i]) / dt, (tb - tt[i]) / dt
+                for q in range(6):
+                    rax = (gx[i][q] + ua * (gx[i + 1][q] - gx[i][q])) - pa[0]
+                    ray = (gy[i][q] + ua * (gy[i + 1][q] - gy[i][q])) - pa[1]
+                    rbx = (gx[i][q] + ub * (gx[i + 1][q] - gx[i][q])) - pb[0]
+                    rby = (gy[i][q] + ub * (gy[i + 1][q] - gy[i][q])) - pb[1]
+                    dx, dy, px, py = rbx - rax, rby - ray, -rax, -ray
+                    L2, dot = dx * dx + dy * dy, px * dx + py * dy
+                    u = dot / L2 if L2 > 0 else 0.0
+                    u = 0.0 if u < 0 else u
+                    u = 1.0 if u > 1 else u
+                    qx, qy = px - u * dx, py - u * dy
+                    gap = (math.sqrt(qx * qx + qy * qy) - cr[q]) - R
+                    if gap < out["gap"][i]:
+                        out["gap"][i] = gap; arg[i] = a
+    out["gap_min"] = min(out["gap"][:n - 1])
+    f = next((i for i in range(n - 1) if out["gap"][i] < margin), None)
+    if f is None:
+        out.update(status=1, ok_out=1)
+        return out
+    s_stop = s[f] - stop_distance
+    j = max([i for i in range(f + 1) if s[i] <= s_stop] + [0])
+    out.update(status=2 if s[0] <= s_stop else 3, first_state=f, first_agent=arg[f], stop_state=j, first_time=tt[f])
+    for i in range(j, n):
+        out["v_limit"][i] = 0.0
+    return out
+
+
+def test_reference_agrees_with_a_scalar_loop_over_the_definition(oracle):
+    params = oracle.default_params()
+    seen = set()
+    for case, (B, N, dp) in enumerate([(10, 21, params_of()), (8, 30, params_of(0.6, 1.0)), (6, 7, params_of(-0.05, 0.0))]):
+        c = random_case(case, B, N)
+        st, t = c["states"], c["t"]
+        if N > 8:
+            t[1, 3] = t[1, 2]  # a zero duration
+            t[1, 6] = t[1, 5] - 0.05  # a negative one
+            st[2, 4, 4] = np.nan  # s is not among the triggers of 'not checked': comparisons with it are false
+        ok = np.ones(B, dtype=np.int32); ok[3] = 0
+        agents, first = c["agents"]
+        agents[1]["x"][0] = np.nan  # covers nothing
+        got = dynamic_ref.check(params, st, t, agents, first, dp, n_states=c["n_states"], ok=ok, set_of=c["set_of"], v_limit_in=c["v_limit_in"])
+        for b in range(B):
+            want = _scalar_check(params, st[b], t[b], c["n_states"][b], ok[b], agents, first, c["set_of"][b], c["v_limit_in"][b], dp.margin, dp.stop_distance)
+            for key in KEYS:
+                dtype = got[key].dtype
+                assert same(got[key][b], np.array(want[key], dtype=dtype)), (case, b, key)
+        seen |= set(got["status"].tolist())
+    assert seen == {0, 1, 2, 3}
+
+
+def test_closed_form_static_disc_beside_a_straight_path(oracle):
+    """A held disc at (6, 3.5) of radius 0.5 beside a path along the x axis: every circle passes it at its lateral distance."""
+    params = oracle.default_params()
+    cx, cy, cr = select_ref.car_circles(params)
+    st, t = straight(60, 0.25)
+    X, Y, R = 6.0, 3.5, 0.5
+    assert ((cx + st[0, 0, 0] < X) & (X < cx + st[0, -1, 0])).all()  # every circle centre passes x = X inside the path
+    r = ref(oracle, states=st, t=t, agents=[[disc(X, Y, R)]])
+    want = (np.abs(Y - cy) - cr - R).min()
+    assert abs(r["gap_min"][0] - want) <= CLOSED_TOL and r["status"][0] == 1 and want > 0.3
+    # the same disc on the path: a conflict, and the gap is the two radii below zero
+    r = ref(oracle, params_of(0.3, 1.0), states=st, t=t, agents=[[disc(X, 0.0, R)]])
+    assert abs(r["gap_min"][0] - (-cr[4:].max() - R)) <= CLOSED_TOL and r["status"][0] == 2  # the two centre-line circles reach the disc's centre
+
+
+def crossing(T0):
+    """An agent that drives up the line x = 9.1 from y = -8 at T0 with 4 m/s (no hold flags: it exists for 4 s), against straight(80, 0.25, v=2)."""
+    return [[(0.4, 0, [(T0, 9.1, -8.0), (T0 + 4.0, 9.1, 8.0)])]]
+
+
+def test_closed_form_crossing_inside_an_interval(oracle):
+    """Ego at 2 m/s along x, the agent at 4 m/s along y: the relative motion is a straight line, the closest approach of circle q is the distance of that line from
+    the origin, and it falls inside an interval, where a per-state sample misses it."""
+    params = oracle.default_params()
+    cx, cy, cr = select_ref.car_circles(params)
+    st, t = straight(80, 0.25)
+    v, w, Xc, Y0, R, T0 = 2.0, 4.0, 9.1, -8.0, 0.4, 2.03
+    r = ref(oracle, states=st, t=t, agents=crossing(T0))
+    # circle q at (cx_q + v t, cy_q), agent at (Xc, Y0 + w (t - T0)): relative r(t) = r0 + (v, -w) t with r0 = (cx_q - Xc, cy_q - Y0 + w T0)
+    r0x, r0y = cx - Xc, cy - Y0 + w * T0
+    tstar = -(r0x * v - r0y * w) / (v * v + w * w)
+    d = np.abs(r0x * (-w) - r0y * v) / math.hypot(v, w)
+    assert ((tstar > T0) & (tstar < T0 + 4.0) & (tstar < t[0, -1])).all()  # every circle's closest approach lies inside the agent's life and the path
+    want = (d - cr - R).min()
+    assert abs(r["gap_min"][0] - want) <= CLOSED_TOL
+    i = int(np.argmin(r["gap"][0]))
+    ts = tstar[np.argmin(d - cr - R)]
+    assert t[0, i] < ts < t[0, i + 1]  # strictly inside interval i
+    at_state = lambda j: (np.hypot(cx + v * t[0, j] - Xc, cy - (Y0 + w * (t[0, j] - T0))) - cr - R).min()
+    assert r["gap_min"][0] < at_state(i) - 1e-3 and r["gap_min"][0] < at_state(i + 1) - 1e-3
+    assert r["status"][0] in (2, 3) and r["first_agent"][0] == 0
+
+
+def test_an_agent_that_has_passed_is_no_conflict(oracle):
+    """The two tracks intersect in space at (9.1, 0); the ego is there around t = 4.5.  An agent that crosses at t = 0 .. 4 - 2 is gone: free."""
+    st, t = straight(80, 0.25)
+    early, late = ref(oracle, states=st, t=t, agents=crossing(-2.0)), ref(oracle, states=st, t=t, agents=crossing(2.5))
+    assert early["status"][0] == 1 and early["ok_out"][0] == 1 and early["gap_min"][0] > 0.3 and early["first_state"][0] == -1
+    assert late["status"][0] == 2 and late["ok_out"][0] == 0
+    held = ref(oracle, states=st, t=t, agents=[[(0.4, AFTER, crossing(-2.0)[0][0][2])]])  # ... unless it stays at its last point (9.1, 8): still free, 8 m away
+    assert held["status"][0] == 1 and held["gap_min"][0] <= early["gap_min"][0]
+    assert (early["gap"][0, 17:] == DBL_MAX).all() and (held["gap"][0, :79] < DBL_MAX).all()  # t_16 = 2.0 is the agent's last moment
+
+
+def test_properties_of_the_reference(oracle):
+    params = oracle.default_params()
+    seen = set()
+    for seed, dp in ((1, params_of()), (2, params_of(0.8, 1.5)), (3, params_of(0.0, 0.0))):
+        c = random_case(10 + seed, 40, 45, per_set=(7, 0, 12))
+        c["t"][5, 10] = c["t"][5, 9]; c["t"][6, 20] = c["t"][6, 19] - 0.01
+        r = ref(oracle, dp, **c)
+        n = np.clip(c["n_states"], 0, 45)
+        L = c["v_limit_in"]
+        for b in range(40):
+            nb, st = int(n[b]), r["status"][b]
+            assert r["ok_out"][b] == (st == 1)
+            if st == 0:
+                assert nb < 2 and (r["gap"][b] == DBL_MAX).all() and r["gap_min"][b] == DBL_MAX and same(r["v_limit"][b], L[b])
+                continue
+            assert r["gap_min"][b] == r["gap"][b].min() and (r["gap"][b, nb - 1:] == DBL_MAX).all()
+            dur = np.diff(c["t"][b, :nb])
+            assert (r["gap"][b, :nb - 1][~(dur > 0)] == DBL_MAX).all()  # zero and negative durations contribute nothing
+            below = np.flatnonzero(r["gap"][b] < dp.margin)
+            if st == 1:
+                assert not len(below) and r["first_state"][b] == r["first_agent"][b] == r["stop_state"][b] == -1 and same(r["v_limit"][b], L[b])
+                assert c["set_of"][b] != 1 or r["gap_min"][b] == DBL_MAX  # set 1 is empty
+                continue
+            f, j = int(r["first_state"][b]), int(r["stop_state"][b])
+            s = c["states"][b, :, 4]
+            assert f == below[0] and 0 <= j <= f and r["first_time"][b] == c["t"][b, f]
+            lo, hi = c["agents"][1][c["set_of"][b]], c["agents"][1][c["set_of"][b] + 1]
+            assert lo <= r["first_agent"][b] < hi
+            s_stop = s[f] - dp.stop_distance
+            assert (st == 3) == (not s[0] <= s_stop) and (st == 3 or s[j] <= s_stop) and (st != 3 or j == 0) and not (s[j + 1:f + 1] <= s_stop).any()
+            assert (r["v_limit"][b, j:nb] == 0).all() and same(r["v_limit"][b, :j], L[b, :j]) and same(r["v_limit"][b, nb:], L[b, nb:])
+        seen |= set(r["status"].tolist())
+    assert seen == {0, 1, 2, 3}
+
+
+def status0_cases(N=12):
+    """(tag, keyword change, whether the path is still checked) of every trigger of 'not checked', and inputs that must NOT trigger it."""
+    def poke(key, val, row=5, col=None):
+        def f(c):
+            c[key] = c[key].copy()
+            if col is None:
+                c[key][1, row] = val
+            else:
+                c[key][1, row, col] = val
+        return f
+
+    def setk(key, val):
+        def f(c):
+            c[key] = np.array(c[key], dtype=np.int32); c[key][1] = val
+        return f
+
+    return [("ok", setk("ok", 0), 0), ("n=1", setk("n_states", 1), 0), ("n=0", setk("n_states", 0), 0), ("n<0", setk("n_states", -3), 0),
+            ("x nan", poke("states", np.nan, col=0), 0), ("y inf", poke("states", np.inf, col=1), 0), ("z -inf", poke("states", -np.inf, col=2), 0),
+            ("t nan", poke("t", np.nan), 0), ("t inf", poke("t", np.inf), 0),
+            ("k nan", poke("states", np.nan, col=3), 1), ("s nan", poke("states", np.nan, col=4), 1), ("x nan beyond n", poke("states", np.nan, N - 1, 0), 1),
+            ("t nan beyond n", poke("t", np.nan, N - 1), 1), ("n > N", setk("n_states", N + 40), 1)]
+
+
+def status0_inputs(N=12):
+    st, t = make_paths(30, 3, N, box=1.0)
+    agents = [[disc(st[b, N // 2, 0], st[b, N // 2, 1], 0.3) for b in range(3)]]
+    return dict(states=st, t=t, n_states=np.array([N, N - 1, N], dtype=np.int32), ok=np.ones(3, dtype=np.int32), agents=agents, v_limit_in=np.full((3, N), 4.5))
+
+
+def test_status_zero_triggers_of_the_reference(oracle):
+    clean = ref(oracle, **status0_inputs())
+    assert (clean["status"] >= 2).all()
+    for tag, change, still in status0_cases():
+        c = status0_inputs()
+        change(c)
+        r = ref(oracle, **c)
+        assert (r["status"][1] > 0) == bool(still), tag
+        if not still:
+            assert r["ok_out"][1] == 0 and r["gap_min"][1] == DBL_MAX and r["first_state"][1] == r["first_agent"][1] == r["stop_state"][1] == -1, tag
+            assert r["first_time"][1] == 0 and (r["gap"][1] == DBL_MAX).all() and (r["v_limit"][1] == 4.5).all(), tag
+        for k in KEYS:  # the neighbours do not notice
+            assert same(r[k][[0, 2]], clean[k][[0, 2]]), (tag, k)
+
+
+def test_agents_that_cover_nothing_and_the_hold_flags(oracle):
+    st, t = straight(40, 0.25)  # 9.75 m in 4.875 s
+    on_path = lambda flags, T: [[(0.3, flags, [(T, 5.0, 0.0)])]]
+    free = ref(oracle, states=st, t=t, agents=[[]])
+    assert free["status"][0] == 1 and free["gap_min"][0] == DBL_MAX
+    # one point: present before T with HOLD_BEFORE, after T with HOLD_AFTER, never without a flag
+    assert ref(oracle, states=st, t=t, agents=on_path(0, 2.0))["gap_min"][0] == DBL_MAX
+    for flags, T, hit in ((BEFORE, 9.0, True), (BEFORE, -1.0, False), (AFTER, -1.0, True), (AFTER, 9.0, False), (BEFORE | AFTER, 2.0, True)):
+        r = ref(oracle, states=st, t=t, agents=on_path(flags, T))
+        assert (r["status"][0] >= 2) == hit and (hit or r["gap_min"][0] == DBL_MAX), (flags, T)
+    # HOLD_BEFORE ends at T_0 and HOLD_AFTER starts at the last T: the intervals outside stay unevaluated
+    r = ref(oracle, states=st, t=t, agents=on_path(BEFORE, 1.0))
+    assert (r["gap"][0, :8] < DBL_MAX).all() and (r["gap"][0, 9:] == DBL_MAX).all()  # t_8 = 1.0: interval 8 starts at T_0 and touches it
+    r = ref(oracle, states=st, t=t, agents=on_path(AFTER, 1.0))
+    assert (r["gap"][0, :7] == DBL_MAX).all() and (r["gap"][0, 7:39] < DBL_MAX).all()
+    # an agent with a NaN, an infinite time, a negative or NaN radius, n_pts of 0 or 9: as if it were not there
+    ag, first = binding.pack_agents([[disc(5.0, 0.0, 0.3), (0.3, 3, [(0.0, 5.0, 0.0), (1.0, 5.0, 0.1)])]])
+    assert ref(oracle, states=st, t=t, agents=(ag, first))["status"][0] >= 2
+    for field, idx, val in (("x", 0, np.nan), ("y", 0, np.inf), ("t", 0, -np.inf), ("radius", None, -0.1), ("radius", None, np.nan), ("n_pts", None, 0), ("n_pts", None, 9)):
+        bad = ag.copy()
+        for a in range(2):
+            if idx is None:
+                bad[a][field] = val
+            else:
+                bad[a][field][idx] = val
+        r = ref(oracle, states=st, t=t, agents=(bad, first))
+        assert r["status"][0] == 1 and r["gap_min"][0] == DBL_MAX, (field, val)
+    bad = ag.copy(); bad[1]["x"][1] = np.nan  # one bad agent does not hide the other
+    assert ref(oracle, states=st, t=t, agents=(bad, first))["status"][0] >= 2
+    bad = ag.copy(); bad[0]["x"][3] = np.nan  # a NaN beyond n_pts is not read
+    assert same(ref(oracle, states=st, t=t, agents=(bad, first))["gap"], ref(oracle, states=st, t=t, agents=(ag, first))["gap"])
+
+
+def no_map(**kw):
+    sp = binding.default_speed_params()
+    for k, v in kw.items():
+        setattr(sp, k, v)
+    return sp
+
+
+def yield_case():
+    """Four straight paths of 120 states 0.25 m apart, offset sideways by 0, 0.5, 9 and 0 m, and a held disc on the x axis 20 m ahead (the last path: ok = 0)."""
+    st = np.concatenate([straight(120, 0.25, y=y)[0] for y in (0.0, 0.5, 9.0, 0.0)])
+    return dict(states=st, v0=np.array([3.0, 5.0, 4.0, 3.0]), ok=np.array([1, 1, 1, 0], dtype=np.int32)), [[disc(20.0, 0.0, 0.4)]]
+
+
+def test_yield_closure_on_the_references(oracle):
+    params = oracle.default_params()
+    c, agents = yield_case()
+    sp, dp = no_map(), params_of(0.3, 2.0)
+    p1 = speed_ref.profile(params, c["states"], c["v0"], sp, ok=c["ok"])
+    d1 = ref(oracle, dp, states=c["states"], t=p1["t"], ok=c["ok"], agents=agents)
+    assert d1["status"].tolist() == [2, 2, 1, 0]
+    p2 = speed_ref.profile(params, c["states"], c["v0"], sp, ok=c["ok"], v_limit=d1["v_limit"])
+    d2 = ref(oracle, dp, states=c["states"], t=p2["t"], ok=c["ok"], agents=agents)
+    assert d2["status"].tolist() == [1, 1, 1, 0]
+    for b in (0, 1):
+        j = d1["stop_state"][b]
+        assert p2["v"][b, j] == 0 and not p2["v"][b, j:].any() and (p2["v"][b, :j] > 0).all() and j < d1["first_state"][b]
+        assert (np.diff(p2["t"][b, j:]) == 0).all() and d2["gap_min"][b] >= dp.margin
+    assert same(p2["v"][2], p1["v"][2])  # the free path keeps its profile
+
+
+def test_new_symbols_and_abi_mirror():
+    L = binding.lib()
+    for name in NEW_ENTRIES:
+        assert hasattr(L, name), name
+        assert name in binding.EXPORTS
+    fields = {"po_agent": ["n_pts", "flags", "radius", "t", "x", "y"], "po_agent_lists": ["agents", "first", "n_agents", "S"],
+              "po_dynamic_params": ["margin", "stop_distance"],
+              "po_dynamic_in": ["B", "N", "states", "n_states", "ok", "t", "set_of", "agents", "v_limit_in"],
+              "po_dynamic_out": ["status", "ok_out", "gap_min", "first_state", "first_agent", "stop_state", "first_time", "gap", "v_limit"]}
+    mirror = {"po_agent": abi.PoAgent, "po_agent_lists": abi.PoAgentLists, "po_dynamic_params": abi.PoDynamicParams, "po_dynamic_in": abi.PoDynamicIn,
+              "po_dynamic_out": abi.PoDynamicOut}
+    body = "".join(f'printf("%zu ", sizeof({s}));' + "".join(f'printf("%zu ", offsetof({s}, {f}));' for f in fs) for s, fs in fields.items())
+    body += 'printf("%d %d %d %d", PO_ABI_VERSION, PO_AGENT_MAX_PTS, PO_AGENT_HOLD_BEFORE, PO_AGENT_HOLD_AFTER);'
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "po_hip.h"\nint main(){' + body + "return 0;}\n"
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        got = [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).split()]
+    want = []
+    for s, fs in fields.items():
+        want.append(ctypes.sizeof(mirror[s]))
+        want += [getattr(mirror[s], f).offset for f in fs]
+    want += [abi.PO_ABI_VERSION, abi.PO_AGENT_MAX_PTS, abi.PO_AGENT_HOLD_BEFORE, abi.PO_AGENT_HOLD_AFTER]
+    assert got == want and abi.PO_ABI_VERSION == 7
+    assert ctypes.sizeof(abi.PoAgent) == 208 == binding.AGENT_DTYPE.itemsize
+    assert [binding.AGENT_DTYPE.fields[f][1] for f in fields["po_agent"]] == [getattr(abi.PoAgent, f).offset for f in fields["po_agent"]]
+    dp = binding.default_dynamic_params()
+    assert [dp.margin, dp.stop_distance] == [0.3, 5.0]
+    ag, first = binding.pack_agents([[disc(1.0, 2.0, 0.5)], [], [(0.25, AFTER, [(0.0, 1.0, 2.0), (1.5, 3.0, 4.0)])]])
+    assert first.tolist() == [0, 1, 1, 2] and ag["n_pts"].tolist() == [1, 2] and ag["flags"].tolist() == [3, 2] and ag[1]["t"][:2].tolist() == [0.0, 1.5]
+    assert ag[1]["x"][1] == 3.0 and ag[1]["y"][1] == 4.0 and ag[0]["radius"] == 0.5
+
+
+def test_null_arguments_are_refused_without_a_device():
+    L = binding.lib()
+    dp, di, do = binding.default_dynamic_params(), abi.PoDynamicIn(), abi.PoDynamicOut()
+    for entry in (L.po_dynamic_batch, L.po_dynamic_batch_device):
+        assert entry(None, ctypes.byref(dp), ctypes.byref(di), ctypes.byref(do)) == abi.PO_ERR_INVALID
+        assert entry(None, None, None, None) == abi.PO_ERR_INVALID
+    L.po_default_dynamic_params(None)  # a NULL struct is ignored
+
+
+def test_host_mirror_header_compiles():
+    inc = os.path.join(ROOT, "path_optimizer_amd", "host", "include")
+    with tempfile.TemporaryDirectory() as d:
+        src = os.path.join(d, "t.cpp")
+        open(src, "w").write('#include "path_optimizer_amd/dynamic_check.hpp"\nint main() { PathOptimizationNS::DynamicChecker c; (void)c; return 0; }\n')
+        subprocess.check_call(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, "-I", os.path.join(ROOT, "include"), src])
+
+
+def test_host_mirror_dynamic_test_compiles_and_links():
+    host = os.path.join(ROOT, "path_optimizer_amd", "host")
+    subprocess.check_call(["make", "-C", host, "dynamic_test"], stdout=subprocess.DEVNULL)
+    assert os.path.exists(os.path.join(host, "dynamic_test"))
+    assert "DynamicChecker" in open(os.path.join(host, "test", "dynamic_test.cpp")).read()
+
+
+def mirror_case():
+    """The seeded case of host/test/dynamic_test.cpp, rebuilt with the same integer generator and the same dyadic arithmetic: bit for bit its inputs."""
+    state = [13579]
+
+    def u():
+        state[0] = (state[0] * 1103515245 + 12345) & 0x7fffffff
+        return (((state[0] >> 8) % 257) - 128) / 64.0
+
+    B = 7
+    n = np.array([2 + (b * 11) % 41 for b in range(B)], dtype=np.int32)
+    N = int(n.max())
+    states, t = np.zeros((B, N, 5)), np.zeros((B, N))
+    for b in range(B):
+        for k in range(n[b]):
+            x = -12.0 + 0.5 * k + u() / 8; y = u(); z = u() / 4; kk = u() / 8
+            states[b, k] = (x, y, z, kk, 0.5 * k)
+            t[b, k] = 0.25 * k
+    sets = []
+    for s in range(3):
+        agents = []
+        for a in range(0 if s == 1 else 5):
+            npts = 1 + (a * 3 + s) % 8
+            t0, x0, y0 = u(), 4 * u(), u()
+            pts = [(t0 + 0.75 * j, x0 + 0.5 * j, y0 + (j % 2) * 0.25) for j in range(npts)]
+            agents.append((0.25 + 0.125 * a, (a + s) % 4, pts))
+        sets.append(agents)
+    set_of = np.array([b % 3 for b in range(B)], dtype=np.int32)
+    ok = np.ones(B, dtype=np.int32); ok[5] = 0
+    lim = np.full((B, N), -1.0)
+    for b in range(0, B, 2):
+        lim[b, :n[b]] = 6.0
+    return dict(states=states, t=t, n_states=n, ok=ok, set_of=set_of, agents=sets, v_limit_in=lim)
+
+
+# ---------------------------------------------------------------- GPU ----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def eng():
+    e = binding.Engine(0)  # no map: the stage reads none
+    yield e
+    e.close()
+
+
+def _dev(a):
+    import torch
+
+    return None if a is None else torch.from_numpy(np.array(a)).cuda()
+
+
+def _host(t):
+    import torch
+
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+OUT_SHAPES = {"status": np.int32, "ok_out": np.int32, "gap_min": np.float64, "first_state": np.int32, "first_agent": np.int32, "stop_state": np.int32,
+              "first_time": np.float64, "gap": np.float64, "v_limit": np.float64}
+
+
+def device_inputs(c):
+    agents, first = binding.pack_agents(c["agents"])
+    t = {"states": _dev(np.asarray(c["states"], dtype=np.float64)), "t": _dev(np.asarray(c["t"], dtype=np.float64)), "first": _dev(first),
+         "agents": _dev(agents.view(np.uint8)) if len(agents) else None}
+    for k in ("n_states", "ok", "set_of"):
+        t[k] = None if c.get(k) is None else _dev(np.asarray(c[k], dtype=np.int32))
+    t["v_limit_in"] = None if c.get("v_limit_in") is None else _dev(np.asarray(c["v_limit_in"], dtype=np.float64))
+    return t
+
+
+def device_outputs(B, N, want=KEYS):
+    """Outputs that start as 7 / 77."""
+    return {k: _dev(np.full((B, N) if k in ("gap", "v_limit") else (B,), 77 if OUT_SHAPES[k] == np.int32 else 7.0, dtype=OUT_SHAPES[k])) for k in want}
+
+
+def run_device(e, c, dp=None, want=KEYS):
+    B, N = c["states"].shape[0], c["states"].shape[1]
+    out = device_outputs(B, N, want)
+    e.dynamic_batch_device(device_inputs(c), out, dp)
+    return {k: _host(v) for k, v in out.items()}
+
+
+def both(e, oracle, dp=None, tag="", **c):
+    """Host entry, device entry and the reference: all three bitwise equal.  Returns the reference's dict."""
+    want = ref(oracle, dp, **c)
+    assert_same(e.dynamic_batch(params=dp, **c), want, tag=tag + " host")
+    assert_same(run_device(e, c, dp), want, tag=tag + " device")
+    return want
+
+
+@pytest.mark.gpu
+def test_path_lengths_around_one_and_two_waves(eng, oracle):
+    lengths = [0, 1, 2, 3, 63, 64, 65, 66, 129]
+    c = random_case(60, len(lengths), 130, per_set=(6, 3, 0))
+    c["n_states"] = np.array(lengths, dtype=np.int32)
+    r = both(eng, oracle, tag="lengths", **c)
+    assert r["status"][:2].tolist() == [0, 0] and (r["status"][2:] > 0).all() and (r["status"] >= 2).any()
+    c = random_case(61, 3, 130, per_set=(8,), ragged=False, limits=False)  # N itself, no n_states, no set_of, no v_limit_in
+    c.pop("n_states"); c.pop("set_of")
+    r = both(eng, oracle, tag="N", **c)
+    assert (r["v_limit"][r["status"] == 1] == -1).all()
+
+
+@pytest.mark.gpu
+def test_agent_counts_around_the_chunk(eng, oracle):
+    counts = [0, 1, DYN_CHUNK - 1, DYN_CHUNK, DYN_CHUNK + 1, 2 * DYN_CHUNK + 1]
+    c = random_case(62, 2 * len(counts), 70, per_set=counts, limits=False)  # 69 intervals: two tiles, so a set longer than a chunk is loaded twice
+    c["set_of"] = np.arange(2 * len(counts), dtype=np.int32) % len(counts)
+    c["n_states"][:len(counts)] = 70
+    r = both(eng, oracle, params_of(0.1, 1.0), tag="counts", **c)
+    assert (r["gap_min"][c["set_of"] == 0] == DBL_MAX).all() and (r["status"] == 1).any() and (r["status"] >= 2).any()
+    first = c["agents"][1]
+    hit = r["first_agent"][r["status"] >= 2]
+    assert (hit - first[c["set_of"][r["status"] >= 2]]).max() >= DYN_CHUNK  # a conflict found in a later chunk
+
+
+@pytest.mark.gpu
+def test_batch_sizes_and_position_in_the_batch(eng, oracle):
+    for B in (1, 2, 65):
+        c = random_case(70 + B, B, 40)
+        ok = np.ones(B, dtype=np.int32); ok[B // 3] = 0
+        both(eng, oracle, ok=ok, tag=f"B {B}", **c)
+    c = random_case(80, 70, 50, per_set=(9, 4, 0))
+    c["n_states"][41] = 50; c["set_of"][41] = 0
+    big = eng.dynamic_batch(**c)
+    one = eng.dynamic_batch(**{k: (v if k == "agents" else v[41:42]) for k, v in c.items()})
+    assert big["status"][41] > 0
+    for k in KEYS:
+        assert same(big[k][41:42], one[k]), k
+
+
+@pytest.mark.gpu
+def test_sets(eng, oracle):
+    c = random_case(90, 12, 40, per_set=(6, 0, 11))
+    c["set_of"] = np.array([0, 1, 2, 2, 1, 0, 0, 2, 1, 1, 2, 0], dtype=np.int32)
+    c["n_states"] = np.maximum(c["n_states"], 10)
+    r = both(eng, oracle, params_of(0.5, 1.0), tag="sets", **c)
+    assert (r["status"][c["set_of"] == 1] == 1).all() and (r["gap_min"][c["set_of"] == 1] == DBL_MAX).all()
+    first = c["agents"][1]
+    conf = r["status"] >= 2
+    assert conf.any() and ((r["first_agent"][conf] >= first[c["set_of"][conf]]) & (r["first_agent"][conf] < first[c["set_of"][conf] + 1])).all()
+    c.pop("set_of")  # NULL: every path meets set 0
+    r0 = both(eng, oracle, params_of(0.5, 1.0), tag="no set_of", **c)
+    assert (r0["first_agent"] < first[1]).all()
+
+
+def piece_case():
+    """Dyadic times: states 0.25 s apart, agents whose point times are multiples of 0.25 (so piece boundaries fall exactly on state times), 1 .. 8 points and every
+    flag combination, a zero and a negative duration, and a disc at the start of path 2 (a conflict on interval 0)."""
+    B, N = 4, 40
+    st = np.concatenate([straight(N, 0.25, y=y)[0] for y in (0.0, 0.25, -0.5, 6.0)])
+    st[:, :, 0] -= 8.0
+    t = np.tile(0.25 * np.arange(N), (B, 1))
+    t[1, 7] = t[1, 6]; t[1, 15] = t[1, 14] - 0.25; t[1, 16] = t[1, 14]
+    agents = []
+    for npts in range(1, 9):
+        for flags in range(4):
+            T0 = 0.25 * ((npts * 5 + flags * 3) % 11)
+            pts = [(T0 + 0.5 * j, 1.0 + npts + 0.75 * j, (2.0 - 0.5 * flags) * (-1) ** j) for j in range(npts)]
+            agents.append((0.125 + 0.0625 * flags, flags, pts))
+    sets = [agents, agents + [disc(-7.5, -0.5, 0.25)]]
+    return dict(states=st, t=t, agents=sets, set_of=np.array([0, 0, 1, 0], dtype=np.int32))
+
+
+@pytest.mark.gpu
+def test_agent_pieces_durations_and_a_conflict_on_interval_zero(eng, oracle):
+    c = piece_case()
+    r = both(eng, oracle, params_of(0.3, 1.0), tag="pieces", **c)
+    assert r["status"][2] == 3 and r["first_state"][2] == 0 and r["stop_state"][2] == 0 and r["first_agent"][2] == 64 and not r["v_limit"][2].any()
+    assert r["gap"][1, 6] == DBL_MAX and r["gap"][1, 14] == DBL_MAX and r["gap"][1, 15] < DBL_MAX  # zero, negative, and the positive one after it
+    assert (r["status"][:2] >= 2).all() and r["status"][3] == 1 and r["gap_min"][3] < DBL_MAX
+    got = eng.dynamic_batch(params=params_of(0.3, 0.0), **c)  # stop_distance 0: stop at the conflict's own state
+    assert got["status"][2] == 2 and (got["stop_state"][got["status"] == 2] == got["first_state"][got["status"] == 2]).all()
+    assert_same(got, ref(oracle, params_of(0.3, 0.0), **c), tag="stop 0")
+
+
+@pytest.mark.gpu
+def test_margin_one_ulp_either_side_and_index_ties(eng, oracle):
+    st, t = straight(50, 0.25)
+    # two agents with the same data: the same gap on every interval, the smaller index wins; a third one far away does not matter
+    agents = [[disc(30.0, 9.0, 0.1), disc(6.0, 2.0, 0.5), disc(6.0, 2.0, 0.5)]]
+    c = dict(states=st, t=t, agents=agents)
+    base = ref(oracle, params_of(-5.0, 1.0), **c)
+    assert base["status"][0] == 1
+    g = base["gap_min"][0]
+    i = int(np.argmin(base["gap"][0]))
+    assert 0 < g < 2 and base["gap"][0, i] == g  # (the first of the intervals that reach the minimum)
+    for margin, hit in ((np.nextafter(g, -np.inf), False), (g, False), (np.nextafter(g, np.inf), True)):
+        r = both(eng, oracle, params_of(margin, 1.0), tag=f"margin {margin!r}", **c)
+        assert (r["status"][0] == 2) == hit
+        if hit:
+            assert r["first_state"][0] == i and r["first_agent"][0] == 1
+    # many intervals below the margin: the first one, and the stop state stop_distance before it
+    r = both(eng, oracle, params_of(1.5 * g, 1.0), tag="first of many", **c)
+    below = np.flatnonzero(base["gap"][0] < 1.5 * g)
+    assert len(below) > 2 and r["first_state"][0] == below[0] and r["first_agent"][0] == 1 and r["stop_state"][0] == below[0] - 4  # 1 m = 4 states
+    swapped = dict(c, agents=[[disc(6.0, 2.0, 0.5), disc(30.0, 9.0, 0.1), disc(6.0, 2.0, 0.5)]])
+    assert both(eng, oracle, params_of(1.5 * g, 1.0), tag="swapped", **swapped)["first_agent"][0] == 0
+
+
+@pytest.mark.gpu
+def test_status_zero_triggers(eng, oracle):
+    for tag, change, still in status0_cases():
+        c = status0_inputs()
+        change(c)
+        r = both(eng, oracle, tag=tag, **c)
+        assert (r["status"][1] > 0) == bool(still), tag
+
+
+@pytest.mark.gpu
+def test_optional_outputs_and_empty_calls(eng, oracle):
+    c = random_case(100, 70, 30)
+    want = ref(oracle, **c)
+    for drop in KEYS[1:]:  # every optional output NULL in turn
+        keys = tuple(k for k in KEYS if k != drop)
+        assert_same(run_device(eng, c, want=keys), want, keys=keys, tag="without " + drop)
+    assert_same(run_device(eng, c, want=("status",)), want, keys=("status",), tag="status alone")
+    r = eng.dynamic_batch(want_rows=False, **c)
+    assert r["gap"] is None and r["v_limit"] is None
+    assert_same(r, want, keys=KEYS[:7], tag="host, no rows")
+    # B = 0: PO_OK from both entries on this handle, which has no map; nothing is looked at, not even the agents
+    L = binding.lib()
+    dp = binding.default_dynamic_params()
+    for entry in (L.po_dynamic_batch, L.po_dynamic_batch_device):
+        di = abi.PoDynamicIn(); di.N = 5
+        assert entry(eng._h, ctypes.byref(dp), ctypes.byref(di), ctypes.byref(abi.PoDynamicOut())) == abi.PO_OK
+    # no agents at all: every checked path is free
+    none = dict(c, agents=[[], []], set_of=np.zeros(70, dtype=np.int32))
+    r = both(eng, oracle, tag="no agents", **none)
+    assert set(r["status"].tolist()) <= {0, 1} and (r["gap"] == DBL_MAX).all()
+
+
+@pytest.mark.gpu
+def test_device_lists_are_read_clamped(eng, oracle):
+    """What the host entry refuses, the device entry reads as the definition says: set_of and first clamped, an agent with a bad n_pts covers nothing."""
+    c = random_case(105, 6, 30, per_set=(5, 5), ragged=False)
+    agents, first = c["agents"]
+    agents = agents.copy(); agents["n_pts"][2] = 9; agents["n_pts"][7] = -1
+    first = np.array([-3, 5, 99], dtype=np.int32)
+    c["agents"] = (agents, first)
+    c["set_of"] = np.array([0, 1, -2, 7, 1, 0], dtype=np.int32)
+    assert_same(run_device(eng, c, params_of(0.6, 1.0)), ref(oracle, params_of(0.6, 1.0), **c), tag="clamped")
+    with pytest.raises(binding.PoError):
+        eng.dynamic_batch(**c)
+
+
+@pytest.mark.gpu
+def test_yield_chain_on_one_stream(oracle):
+    """speed -> dynamic -> speed(v_limit) -> dynamic, device entries only, no synchronisation and no host copy between the four calls."""
+    import torch
+
+    params = oracle.default_params()
+    c, agents = yield_case()
+    B, N = c["states"].shape[0], c["states"].shape[1]
+    sp, dp = no_map(), params_of(0.3, 2.0)
+    e = binding.Engine(0)
+    f64 = lambda: _dev(np.full((B, N), 7.0))
+    spd = [{"v": f64(), "a": f64(), "t": f64(), "total_time": _dev(np.full(B, 7.0)), "status": _dev(np.full(B, 77, dtype=np.int32))} for _ in range(2)]
+    dyn = [device_outputs(B, N) for _ in range(2)]
+    d_in = device_inputs(dict(states=c["states"], t=np.zeros((B, N)), ok=c["ok"], agents=agents))
+    s_in = {"states": d_in["states"], "ok": d_in["ok"], "v0": _dev(c["v0"])}
+    torch.cuda.synchronize()
+    e.speed_batch_device(s_in, spd[0], sp)
+    e.dynamic_batch_device(dict(d_in, t=spd[0]["t"]), dyn[0], dp)
+    e.speed_batch_device(dict(s_in, v_limit=dyn[0]["v_limit"]), spd[1], sp)
+    e.dynamic_batch_device(dict(d_in, t=spd[1]["t"]), dyn[1], dp)
+    got_s = [{k: _host(v) for k, v in o.items()} for o in spd]
+    got_d = [{k: _host(v) for k, v in o.items()} for o in dyn]
+    e.close()
+    p1 = speed_ref.profile(params, c["states"], c["v0"], sp, ok=c["ok"])
+    d1 = ref(oracle, dp, states=c["states"], t=p1["t"], ok=c["ok"], agents=agents)
+    p2 = speed_ref.profile(params, c["states"], c["v0"], sp, ok=c["ok"], v_limit=d1["v_limit"])
+    d2 = ref(oracle, dp, states=c["states"], t=p2["t"], ok=c["ok"], agents=agents)
+    skeys = ("v", "a", "t", "total_time", "status")
+    assert_same(got_s[0], p1, keys=skeys, tag="speed 1"); assert_same(got_d[0], d1, tag="dynamic 1")
+    assert_same(got_s[1], p2, keys=skeys, tag="speed 2"); assert_same(got_d[1], d2, tag="dynamic 2")
+    assert got_d[0]["status"].tolist() == [2, 2, 1, 0] and got_d[1]["status"].tolist() == [1, 1, 1, 0]
+    for b in (0, 1):
+        assert got_s[1]["v"][b, got_d[0]["stop_state"][b]] == 0
+
+
+@pytest.mark.gpu
+def test_select_chain_prefers_the_conflict_free_candidate(oracle):
+    """ok_out as po_select_in.ok on a flat free map: three straight candidates whose cost is their length, the shortest one runs into a held disc."""
+    N = 60
+    st = np.zeros((3, N, 5)); t = np.zeros((3, N))
+    n = np.array([40, 50, 60], dtype=np.int32)
+    for b in range(3):
+        st[b, :n[b]], t[b, :n[b]] = straight(n[b], 0.25, y=-3.0 + 3.0 * b)[0][0], straight(n[b], 0.25)[1][0]
+    agents = [[disc(5.0, -3.0, 0.4)]]
+    e = binding.Engine(0)
+    e.set_map(np.full((200, 120), 10.0, dtype=np.float32), 0.2, 5.0, 0.0)  # 40 m x 24 m around (5, 0), 10 m of clearance everywhere
+    dyn = device_outputs(3, N)
+    e.dynamic_batch_device(device_inputs(dict(states=st, t=t, n_states=n, agents=agents)), dyn)
+    t_sel = {"states": _dev(st), "n_states": _dev(n), "group_start": _dev(np.array([0, 3], dtype=np.int32))}
+    out = [{"best": _dev(np.full(1, 77, dtype=np.int32)), "cost": _dev(np.full(3, 7.0))} for _ in range(2)]
+    e.select_batch_device(dict(t_sel, ok=dyn["ok_out"]), out[0])
+    e.select_batch_device(t_sel, out[1])
+    ok_out, cost = _host(dyn["ok_out"]), _host(out[1]["cost"])
+    best = [int(_host(o["best"])[0]) for o in out]
+    e.close()
+    assert ok_out.tolist() == [0, 1, 1] and cost[0] < cost[1] < cost[2] and best == [1, 0]
+    assert_same({k: _host(v) for k, v in dyn.items()}, ref(oracle, states=st, t=t, n_states=n, agents=agents), tag="select chain")
+
+
+@pytest.mark.gpu
+def test_host_mirror_dynamic_program(eng, oracle):
+    """DynamicChecker::check end to end in its own process: its statuses and its checksum of gap equal the Python call's and the reference's."""
+    host = os.path.join(ROOT, "path_optimizer_amd", "host")
+    subprocess.check_call(["make", "-C", host, "dynamic_test"], stdout=subprocess.DEVNULL)
+    r = subprocess.run([os.path.join(host, "dynamic_test")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "dynamic_test passed" in r.stdout, r.stdout[-2000:] + r.stderr[-1000:]
+    printed = {ln.split()[0]: [int(v) for v in ln.split()[1:]] for ln in r.stdout.splitlines() if ln.split() and ln.split()[0] in ("status", "checksum")}
+    c = mirror_case()
+    got = both(eng, oracle, params_of(0.3, 1.0), tag="mirror case", **c)
+    assert printed["status"] == got["status"].tolist() and got["status"][5] == 0 and {1, 2, 3} <= set(got["status"].tolist())
+    rows = np.concatenate([got["gap"][b, :c["n_states"][b]] for b in range(len(c["n_states"]))])
+    assert printed["checksum"] == [int(rows.view(np.uint64).sum(dtype=np.uint64))]
+
+
+@pytest.mark.gpu
+def test_host_validation(eng):
+    st, t = make_paths(120, 4, 8, box=1.0)
+    good = [[disc(0.0, 0.0, 0.3), (0.2, 3, [(0.0, 1.0, 1.0), (1.0, 2.0, 1.0), (2.5, 2.0, 3.0)])], []]
+    assert (eng.dynamic_batch(st, t, good)["status"] > 0).all()
+    for field, val in (("margin", np.nan), ("margin", np.inf), ("margin", -np.inf), ("stop_distance", -0.5), ("stop_distance", np.nan), ("stop_distance", np.inf)):
+        with pytest.raises(binding.PoError):
+            eng.dynamic_batch(st, t, good, params=params_of(**{field: val}))
+    assert (eng.dynamic_batch(st, t, good, params=params_of(-10.0, 0.0))["status"] == 1).all()  # a negative margin (below every gap here) and a zero stop distance are inside the ranges
+
+    def bad_agent(field, val, idx=None):
+        ag, first = binding.pack_agents(good)
+        if idx is None:
+            ag[1][field] = val
+        else:
+            ag[1][field][idx] = val
+        return ag, first
+
+    lists = [bad_agent("n_pts", 0), bad_agent("n_pts", 9), bad_agent("radius", -0.1), bad_agent("radius", np.nan), bad_agent("radius", np.inf),
+             bad_agent("t", np.nan, 1), bad_agent("t", 0.0, 1), bad_agent("t", 0.5, 2), bad_agent("t", np.inf, 2), bad_agent("x", np.nan, 0), bad_agent("y", -np.inf, 2),
+             bad_agent("flags", 4), bad_agent("flags", -1)]
+    ag, first = binding.pack_agents(good)
+    lists += [(ag, np.array(f, dtype=np.int32)) for f in ([1, 2, 2], [0, 2, 1], [0, 2, 3], [0, -1, 2])]
+    for k, bad in enumerate(lists):
+        with pytest.raises(binding.PoError):
+            eng.dynamic_batch(st, t, bad)
+            raise AssertionError(f"list {k} was accepted")
+    assert (eng.dynamic_batch(st, t, bad_agent("x", np.nan, 5))["status"] > 0).all()  # beyond n_pts: not read
+    for so in ([0, 1, 2, 0], [0, -1, 0, 0]):
+        with pytest.raises(binding.PoError):
+            eng.dynamic_batch(st, t, good, set_of=np.array(so, dtype=np.int32))
+    L = binding.lib()
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    dp = binding.default_dynamic_params()
+    status = np.zeros(4, dtype=np.int32)
+
+    def call(entry, lists_args, in_edit=None, out_status=True, no_lists=False):
+        lists_ = abi.PoAgentLists(*lists_args)
+        args = [4, 8, p(st), None, None, p(t), None, None if no_lists else ctypes.pointer(lists_), None]
+        for k, v in (in_edit or {}).items():
+            args[k] = v
+        do = abi.PoDynamicOut(p(status) if out_status else None, *([None] * 8))
+        return entry(eng._h, ctypes.byref(dp), ctypes.byref(abi.PoDynamicIn(*args)), ctypes.byref(do))
+
+    full = [p(ag), p(first), len(ag), 2]
+    assert call(L.po_dynamic_batch, full) == abi.PO_OK
+    for entry in (L.po_dynamic_batch, L.po_dynamic_batch_device):
+        for edit in ({2: None}, {5: None}, {0: -1}, {1: -1}):  # states, t, B, N
+            assert call(entry, full, edit) == abi.PO_ERR_INVALID, edit
+        assert call(entry, full, out_status=False) == abi.PO_ERR_INVALID
+        assert call(entry, full, no_lists=True) == abi.PO_ERR_INVALID
+        for bad in ([None, p(first), len(ag), 2], [p(ag), None, len(ag), 2], [p(ag), p(first), -1, 2], [p(ag), p(first), len(ag), -1], [p(ag), p(first), len(ag), 0]):
+            assert call(entry, bad) == abi.PO_ERR_INVALID
+        lists_ = abi.PoAgentLists(*full)
+        di = abi.PoDynamicIn(4, 8, p(st), None, None, p(t), None, ctypes.pointer(lists_), None)
+        do = abi.PoDynamicOut(p(status), *([None] * 8))
+        assert entry(eng._h, None, ctypes.byref(di), ctypes.byref(do)) == abi.PO_ERR_INVALID
+        assert entry(eng._h, ctypes.byref(dp), None, ctypes.byref(do)) == abi.PO_ERR_INVALID
+        assert entry(eng._h, ctypes.byref(dp), ctypes.byref(di), None) == abi.PO_ERR_INVALID
+    assert call(L.po_dynamic_batch, [None, p(np.zeros(3, dtype=np.int32)), 0, 2]) == abi.PO_OK and (status == 1).all()  # n_agents = 0 needs no agents pointer
