@@ -888,6 +888,88 @@ typedef struct po_dynamic_out {
 int po_dynamic_batch(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out);         /* host pointers, synchronous */
 int po_dynamic_batch_device(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out);  /* device pointers, on the stream, no synchronisation */
 
+/* ---- station-time speed planning: pass or yield around predicted agents (csrc/po_stplan.hip) ----
+ * po_dynamic_batch* knows one remedy: stop short of the first conflict.  This stage decides between easing off, yielding and passing ahead.  Per path it lays
+ * stations along the path, marks every (time window, station) cell an agent of the path's set blocks, and searches the station-time graph for the cheapest
+ * speed plan through the free cells.  out->v_limit has the layout of po_speed_in.v_limit, so stplan -> speed -> dynamic stays on one stream.  The stage reads no
+ * map and works on a handle without one.  The reference has no such stage.
+ *
+ * Definition (the bar is BIT equality).  The conventions are po_dynamic_batch's: every operation is one rounded IEEE double operation in the order written,
+ * nothing contracted; sqrt and / are the correctly rounded ones; a comparison with a NaN is false; min(a, b) = b < a ? b : a; max(a, b) = b > a ? b : a.
+ * n = n_states[b] clamped into [0, N] (N when NULL); row i = (x_i, y_i, z_i, k_i, s_i).  L(i) = v_limit_in[b][i], -1 when v_limit_in is NULL.  Integer divisions
+ * truncate.  K, stride, U, dt, margin, a_max, b_max, v_max, w_acc, w_slow are the fields of po_stplan_params.
+ *   Not planned: status = 0, ok_out = 0, n_layers = 0, cost = DBL_MAX, every entry of the station row and of the cells row -1 and v_limit[i] = L(i) for every
+ *       i < N, when ok[b] == 0, or n < 2, or v0[b] is not a finite value >= 0, or any x, y, z or s of rows < n is non-finite, or M < 2.
+ *   Stations.  M = min((n - 1) / stride + 1, PO_ST_MAX_STATIONS).  Station m < M is state m * stride; S_m = its s.  Vc_m = v_max; when v_cap is given and
+ *       e = v_cap[b][m * stride] satisfies e >= 0: Vc_m = min(Vc_m, e).  The circle centres gx_mq, gy_mq, q = 0 .. 5, are po_dynamic_batch's at that state.
+ *   Blocked cells.  One cell (k, m) for every k < K, m < M: the window [tk, tk1], tk = (double)k * dt, tk1 = (double)(k + 1) * dt, with the ego standing still
+ *       at station m.  The agents of path b are po_dynamic_batch's (set_of clamped, first clamped, agents that cover nothing by the same rule), ascending; each
+ *       agent's pieces come in po_dynamic_batch's order with its window formulas, t_i := tk and t_{i+1} := tk1; a piece is skipped unless ta <= tb.  For
+ *       q = 0 .. 5:  rax = gx_mq - ax_a, ray = gy_mq - ay_a, rbx = gx_mq - ax_b, rby = gy_mq - ay_b;  then po_dynamic_batch's dx, dy, px, py, L2, dot, u (clamped),
+ *       qx, qy, dist and gap = (dist - cr_q) - R.  cell(k, m) = the smallest agent index (into agents[]) with some gap < margin, -1 when there is none.
+ *       Known and not fixed: an edge of the search counts the vehicle as present at every station it sweeps, for the whole window — conservative; between two
+ *       stations only the margin covers the vehicle.
+ *   Step table, for 0 <= u <= min(U, j), j < M:  v(j, u) = (S_j - S_{j-u}) / dt;  c(j, u): c = Vc_{j-u}, then c = min(c, Vc_m) for m = j - u + 1 .. j, ascending.
+ *       (j, u) is DRIVABLE iff u == 0, or v(j, u) > 0 and v(j, u) <= c(j, u).  It is CLEAR in window k iff no cell (k, m), m = j - u .. j, is blocked.
+ *   Search.  Every state holds DBL_MAX until a feasible edge reaches it; a state is REACHABLE iff its value is < DBL_MAX.  Layer 0 has one state: station 0 with
+ *       the previous speed v0 and the value 0.  For k = 1 .. K, state (j, u) of layer k looks at its predecessors (j - u, u') of layer k - 1, u' = 0 .. min(U, j - u)
+ *       ascending (for k = 1: the one state of layer 0, which needs j - u == 0; its back pointer is 0), and takes  cand = C_{k-1}(j - u, u') + e  when the edge is
+ *       feasible and cand < the value held (strict: the smallest u' among equals); the back pointer is the winning u'.
+ *       vp = v0 for k = 1, else v(j - u, u');  acc = (v(j, u) - vp) / dt;  dv = c(j, u) - v(j, u);  e = (w_acc * acc) * acc + (w_slow * dv) * dv.
+ *       The edge is feasible iff the predecessor is reachable and has not ARRIVED (j - u != M - 1), (j, u) is drivable and clear in window k - 1,
+ *       acc <= a_max and acc >= -b_max, and, for k > 1, u' == 0 implies u == 0: a speed profile over arc length cannot express stop, wait, go — po_dynamic_batch's
+ *       own statement about stops — so a vehicle that has stopped stays stopped to the horizon.
+ *   Choice.  The candidates are the states (k, M - 1, u), k = 1 .. K (arrived), and every state of layer K.  Scan k ascending, then j, then u, and take a
+ *       candidate when its value < the best so far (starting at DBL_MAX).  None: status = 3 and the outputs of "not planned" except that the cells row is the map.
+ *       Otherwise n_layers = the chosen k, cost = its value, station[0 .. n_layers] = the stations along the back pointers (station[0] = 0) and -1 behind them,
+ *       u_k = station[k] - station[k-1];  status = 1 when no cell of the map is blocked, else 2;  ok_out = 1.
+ *   v_limit.  i >= n: L(i).  i < n: m = i / stride.  m >= station[n_layers]: 0 when u_{n_layers} == 0, else L(i).  Otherwise, with the one k such that
+ *       station[k] <= m < station[k+1]:  V = v(station[k+1], u_{k+1});  the value is L(i) >= 0 ? min(L(i), V) : V.
+ *   cells [B][K][PO_ST_MAX_STATIONS]: cell(k, m) for m < M, -1 in the columns >= M — there so that the geometry half and the search half can be checked apart.
+ * Return codes, both entries.  PO_ERR_INVALID: a NULL handle, struct or required pointer (B > 0: states, v0, status, agents; inside agents: first, and agents
+ *   when n_agents > 0); a negative B, N, S or n_agents; S = 0 with B > 0; dt, a_max, b_max or v_max not finite or not > 0; K outside 1 .. PO_ST_MAX_LAYERS;
+ *   stride < 1; U outside 1 .. PO_ST_MAX_STEP; margin not finite; w_acc or w_slow negative or not finite.  The HOST entry refuses the lists po_dynamic_batch
+ *   refuses; the DEVICE entry reads them clamped, as the definition says, and never reads outside the buffers.  B = 0: PO_OK after those checks, nothing launched.
+ * `p`, `in->agents` (the struct) are host pointers in both entries; the arrays inside are device pointers for the device entry.  Deterministic: no atomics, no
+ * scratch, and a path's results depend neither on the batch size nor on its position in the batch.
+ * po_default_stplan_params: {1.0, 8, 3, 20, 0.5, 2, 3, 15, 1, 1} — a starting point nobody has tuned. */
+#define PO_ST_MAX_LAYERS 16
+#define PO_ST_MAX_STEP 31
+#define PO_ST_MAX_STATIONS 128
+typedef struct po_stplan_params {
+    double dt;                   /* > 0, finite: time step */
+    int K;                       /* 1 .. PO_ST_MAX_LAYERS steps; the horizon is K * dt */
+    int stride;                  /* >= 1: path states per station */
+    int U;                       /* 1 .. PO_ST_MAX_STEP: most stations advanced in one step */
+    double margin;               /* finite: a cell is blocked <=> gap < margin */
+    double a_max, b_max;         /* > 0, finite: acceleration and braking limits */
+    double v_max;                /* > 0, finite: speed cap */
+    double w_acc, w_slow;        /* >= 0, finite: cost weights */
+} po_stplan_params;
+void po_default_stplan_params(po_stplan_params *p);
+typedef struct po_stplan_in {
+    int B, N;                    /* paths, rows per path (stride of the arrays) */
+    const double *states;        /* [B][N][5] x, y, heading, k, s */
+    const int    *n_states;      /* optional [B] (NULL: N) */
+    const int    *ok;            /* optional [B] (NULL: all 1) */
+    const double *v0;            /* [B] */
+    const double *v_cap;         /* optional [B][N]: a per-state speed cap (po_speed_out.v of a profile without agents); negative or NaN: none */
+    const int    *set_of;        /* optional [B] (NULL: set 0) */
+    const po_agent_lists *agents;
+    const double *v_limit_in;    /* optional [B][N], merged into v_limit */
+} po_stplan_in;
+typedef struct po_stplan_out {
+    int    *status;              /* [B] 0 not planned, 1 planned and no cell blocked, 2 planned around blocked cells, 3 no plan */
+    int    *ok_out;              /* optional [B]: status 1 or 2 */
+    int    *n_layers;            /* optional [B] */
+    double *cost;                /* optional [B] */
+    int    *station;             /* optional [B][PO_ST_MAX_LAYERS + 1] */
+    int    *cells;               /* optional [B][K][PO_ST_MAX_STATIONS] */
+    double *v_limit;             /* optional [B][N]: the layout of po_speed_in.v_limit */
+} po_stplan_out;
+int po_stplan_batch(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out);         /* host pointers, synchronous */
+int po_stplan_batch_device(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -920,7 +1002,8 @@ const char *po_last_hip_error(void);
  * obstacle-list entries (po_obstacle, po_obstacle_lists, po_rasterize_batch*, po_set_map_stack_obstacles*) and the static-world entries (po_rings, po_scene, po_set_world_occupancy*, po_rasterize_scene_batch*, po_set_map_stack_scene*,
  * po_debug_get "world_cells") and the score-and-select entries (po_select_params, po_select_in, po_select_out, po_default_select_params, po_select_batch*) and
  * the speed-profile entries (po_speed_params, po_speed_in, po_speed_out, po_default_speed_params, po_speed_batch*) and the moving-obstacle entries (po_agent, po_agent_lists, po_dynamic_params, po_dynamic_in, po_dynamic_out,
- * po_default_dynamic_params, po_dynamic_batch*) were added under 7 by the same rule.  A binding should compare
+ * po_default_dynamic_params, po_dynamic_batch*) and the station-time entries (po_stplan_params, po_stplan_in, po_stplan_out, po_default_stplan_params,
+ * po_stplan_batch*) were added under 7 by the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7
 const char *po_version(void);

@@ -182,3 +182,22 @@ class PoDynamicIn(C.Structure):
 class PoDynamicOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("ok_out", C.c_void_p), ("gap_min", C.c_void_p), ("first_state", C.c_void_p), ("first_agent", C.c_void_p),
                 ("stop_state", C.c_void_p), ("first_time", C.c_void_p), ("gap", C.c_void_p), ("v_limit", C.c_void_p)]
+
+
+# ---- station-time speed planning (po_stplan_batch*) ----
+PO_ST_MAX_LAYERS, PO_ST_MAX_STEP, PO_ST_MAX_STATIONS = 16, 31, 128
+
+
+class PoStplanParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("K", C.c_int), ("stride", C.c_int), ("U", C.c_int), ("margin", C.c_double), ("a_max", C.c_double), ("b_max", C.c_double),
+                ("v_max", C.c_double), ("w_acc", C.c_double), ("w_slow", C.c_double)]
+
+
+class PoStplanIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("v0", C.c_void_p), ("v_cap", C.c_void_p),
+                ("set_of", C.c_void_p), ("agents", C.POINTER(PoAgentLists)), ("v_limit_in", C.c_void_p)]
+
+
+class PoStplanOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("ok_out", C.c_void_p), ("n_layers", C.c_void_p), ("cost", C.c_void_p), ("station", C.c_void_p), ("cells", C.c_void_p),
+                ("v_limit", C.c_void_p)]

@@ -33,7 +33,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_set_map_stack_scene", "po_set_map_stack_scene_device",
            "po_default_select_params", "po_select_batch", "po_select_batch_device",
            "po_default_speed_params", "po_speed_batch", "po_speed_batch_device",
-           "po_default_dynamic_params", "po_dynamic_batch", "po_dynamic_batch_device"]
+           "po_default_dynamic_params", "po_dynamic_batch", "po_dynamic_batch_device",
+           "po_default_stplan_params", "po_stplan_batch", "po_stplan_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -108,6 +109,10 @@ def lib():
         L.po_default_dynamic_params.restype = None
         L.po_dynamic_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_dynamic_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_default_stplan_params.argtypes = [C.c_void_p]
+        L.po_default_stplan_params.restype = None
+        L.po_stplan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_stplan_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -151,6 +156,15 @@ def default_dynamic_params():
 
     p = PoDynamicParams()
     lib().po_default_dynamic_params(C.byref(p))
+    return p
+
+
+def default_stplan_params():
+    """po_default_stplan_params: the knobs of po_stplan_batch* (a starting point nobody has tuned)."""
+    from .abi import PoStplanParams
+
+    p = PoStplanParams()
+    lib().po_default_stplan_params(C.byref(p))
     return p
 
 
@@ -953,6 +967,47 @@ class Engine:
         do = PoDynamicOut(*[p(out, k) for k in self.DYNAMIC_KEYS])
         dp = params if params is not None else default_dynamic_params()
         _check(lib().po_dynamic_batch_device(self._h, C.byref(dp), C.byref(di), C.byref(do)))
+
+    # ---- station-time speed planning: pass or yield around predicted agents ----
+    STPLAN_KEYS = ("status", "ok_out", "n_layers", "cost", "station", "cells", "v_limit")
+
+    def stplan_batch(self, states, v0, agents, n_states=None, ok=None, v_cap=None, set_of=None, v_limit_in=None, params=None, want_rows=True):
+        """Host-pointer entry of po_stplan_batch.  states [B,N,5], v0 [B], agents: what pack_agents takes; optional n_states [B], ok [B], v_cap [B,N], set_of [B]
+        (None: set 0), v_limit_in [B,N].  Returns a dict: status, ok_out, n_layers [B] i32, cost [B], station [B,17] i32, cells [B,K,128] i32 and v_limit [B,N]
+        (the last two None without want_rows)."""
+        from .abi import PO_ST_MAX_LAYERS, PO_ST_MAX_STATIONS, PoAgentLists, PoStplanIn, PoStplanOut
+
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        B, N = states.shape[0], states.shape[1]
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        vv, cap, vin = f(v0), f(v_cap), f(v_limit_in)
+        ns, okk, so = _i32(n_states), _i32(ok), _i32(set_of)
+        ag, first = pack_agents(agents)
+        lists = PoAgentLists(_np(ag) if len(ag) else None, _np(first), len(ag), len(first) - 1)
+        si = PoStplanIn(B, N, _np(states), _np(ns), _np(okk), _np(vv), _np(cap), _np(so), C.pointer(lists), _np(vin))
+        sp = params if params is not None else default_stplan_params()
+        i32 = lambda *shape: np.zeros(shape, dtype=np.int32)
+        r = {"status": i32(B), "ok_out": i32(B), "n_layers": i32(B), "cost": np.zeros(B), "station": i32(B, PO_ST_MAX_LAYERS + 1),
+             "cells": i32(B, max(int(sp.K), 0), PO_ST_MAX_STATIONS) if want_rows else None, "v_limit": np.zeros((B, N)) if want_rows else None}
+        so_ = PoStplanOut(*[_np(r[k]) for k in self.STPLAN_KEYS])
+        _check(lib().po_stplan_batch(self._h, C.byref(sp), C.byref(si), C.byref(so_)))
+        return r
+
+    def stplan_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: states [B,N,5] f64, v0 [B] f64, agents (a uint8 tensor over AGENT_DTYPE records, or None when there are none), first [S+1] i32
+        (+ n_states, ok, set_of i32 [B], v_cap, v_limit_in [B,N]); out: status [B] i32 (+ any of STPLAN_KEYS: station [B,17] i32, cells [B,K,128] i32).  Enqueued on
+        the handle's stream, no synchronisation."""
+        from .abi import PoAgentLists, PoStplanIn, PoStplanOut
+
+        B, N = t["states"].shape[0], t["states"].shape[1]
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        ag = t.get("agents")
+        n_agents = 0 if ag is None else ag.numel() * ag.element_size() // AGENT_DTYPE.itemsize
+        lists = PoAgentLists(p(t, "agents") if n_agents else None, p(t, "first"), n_agents, t["first"].shape[0] - 1)
+        si = PoStplanIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "v0"), p(t, "v_cap"), p(t, "set_of"), C.pointer(lists), p(t, "v_limit_in"))
+        so = PoStplanOut(*[p(out, k) for k in self.STPLAN_KEYS])
+        sp = params if params is not None else default_stplan_params()
+        _check(lib().po_stplan_batch_device(self._h, C.byref(sp), C.byref(si), C.byref(so)))
 
     def map_sample(self, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)

@@ -1443,6 +1443,78 @@ int po_dynamic_batch(po_handle h, const po_dynamic_params *p, const po_dynamic_i
     return S.copy_out(h);
 }
 
+// ---- station-time speed planning (po_stplan.hip) ------------------------------------------------
+void po_default_stplan_params(po_stplan_params *p) {
+    if (!p) return;
+    *p = po_stplan_params{1.0, 8, 3, 20, 0.5, 2.0, 3.0, 15.0, 1.0, 1.0};  // a starting point nobody has tuned
+}
+
+// What both entries can check without reading through a pointer of the structs (testable without a GPU)
+static bool stplan_args_ok(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0) return false;
+    auto pos = [](double v) { return std::isfinite(v) && v > 0; };
+    auto wgt = [](double v) { return std::isfinite(v) && v >= 0; };
+    if (!pos(p->dt) || !pos(p->a_max) || !pos(p->b_max) || !pos(p->v_max) || !wgt(p->w_acc) || !wgt(p->w_slow) || !std::isfinite(p->margin)) return false;
+    if (p->K < 1 || p->K > PO_ST_MAX_LAYERS || p->stride < 1 || p->U < 1 || p->U > PO_ST_MAX_STEP) return false;
+    const po_agent_lists *L = in->agents;
+    if (L && (L->S < 0 || L->n_agents < 0)) return false;
+    if (in->B == 0) return true;
+    if (!in->states || !in->v0 || !out->status || !L) return false;
+    return L->S >= 1 && L->first && (L->n_agents == 0 || L->agents);
+}
+
+int po_stplan_batch_device(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out) {
+    if (!stplan_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing to plan: no launch, whatever the handle holds
+    std::lock_guard<std::mutex> g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    po::DevStplan D{};
+    D.B = in->B; D.N = in->N; D.S = in->agents->S; D.n_agents = in->agents->n_agents;
+    D.states = in->states; D.n_states = in->n_states; D.ok = in->ok; D.v0 = in->v0; D.v_cap = in->v_cap; D.set_of = in->set_of;
+    D.agents = in->agents->agents; D.first = in->agents->first; D.v_limit_in = in->v_limit_in;
+    D.dt = p->dt; D.K = p->K; D.stride = p->stride; D.U = p->U; D.margin = p->margin; D.a_max = p->a_max; D.b_max = p->b_max; D.v_max = p->v_max;
+    D.w_acc = p->w_acc; D.w_slow = p->w_slow;
+    const int mb = in->N > 0 ? (in->N - 1) / p->stride + 1 : 1;  // no path of the call has more stations: the LDS is sized from it
+    D.Mb = mb > PO_ST_MAX_STATIONS ? PO_ST_MAX_STATIONS : mb;
+    D.status = out->status; D.ok_out = out->ok_out; D.n_layers = out->n_layers; D.cost = out->cost; D.station = out->station; D.cells = out->cells;
+    D.v_limit = out->v_limit;
+    const po::DevCar car = make_car(h->params);
+    HIP_TRY(po_launch_stplan(&car, &D, h->stream));
+    return PO_OK;
+}
+
+int po_stplan_batch(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out) {
+    if (!stplan_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
+    po_dynamic_in as_dynamic{};    // the lists are po_dynamic_batch's and so is what the host entry refuses in them
+    as_dynamic.B = in->B; as_dynamic.set_of = in->set_of; as_dynamic.agents = in->agents;
+    if (!dynamic_lists_ok(&as_dynamic)) return PO_ERR_INVALID;
+    const po_agent_lists *L = in->agents;
+    const size_t B = in->B, bn = B * (size_t)in->N;
+    Stage S;
+    const Slot<double> states = S.in(in->states, 5 * bn), v0 = S.in(in->v0, B), cap = S.in(in->v_cap, bn), vin = S.in(in->v_limit_in, bn);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B), first = S.in(L->first, (size_t)L->S + 1);
+    const Slot<po_agent> agents = S.in(L->n_agents > 0 ? L->agents : nullptr, (size_t)L->n_agents);
+    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernel skips it
+    auto opt_i = [&](int *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<int>{}; };
+    auto opt_d = [&](double *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<double>{}; };
+    const Slot<int> status = S.out(out->status, B), ok_out = opt_i(out->ok_out, B), nl = opt_i(out->n_layers, B);
+    const Slot<int> station = opt_i(out->station, B * (PO_ST_MAX_LAYERS + 1)), cells = opt_i(out->cells, B * (size_t)p->K * PO_ST_MAX_STATIONS);
+    const Slot<double> cost = opt_d(out->cost, B), vl = opt_d(out->v_limit, bn);
+    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        HIP_TRY(hipSetDevice(h->device));
+        PO_TRY(S.upload(h, h->post_buf));
+    }
+    const po_agent_lists dl{agents, first, L->n_agents, L->S};
+    const po_stplan_in d{in->B, in->N, states, ns, ok, v0, cap, set_of, &dl, vin};
+    const po_stplan_out o{status, ok_out, nl, cost, station, cells, vl};
+    PO_TRY(po_stplan_batch_device(h, p, &d, &o));
+    std::lock_guard<std::mutex> g(h->mu);
+    return S.copy_out(h);
+}
+
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------
 static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bounds, const int *n_valid) {
     if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return false;

@@ -17,7 +17,7 @@ enum { kLaunchSolve, kLaunchNewton, kLaunchFallback, kLaunchPolish };  // what a
 // the groups the shapes are dealt to the objects in (KP's two-level shapes: one lane per chunk / role-split / multi-group / the wide role-split shapes by SPL; the single-level mapping)
 enum { kGrpLane = 1, kGrpSplit = 2, kGrpMulti = 4, kGrpW56 = 8, kGrpW7 = 16, kGrpW8 = 32, kGrpOne = 64 };
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
-struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic;
+struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic; struct DevStplan;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
 
@@ -121,4 +121,8 @@ hipError_t po_launch_speed(const po::DevMaps *m, const po::DevCar *c, const po::
 
 // ---- po_dynamic.hip: timed paths against moving agents (one wave per path, lanes over intervals, the path's agent set through LDS in chunks; device pointers) ----
 hipError_t po_launch_dynamic(const po::DevCar *c, const po::DevDynamic *a, hipStream_t st);
+
+// ---- po_stplan.hip: station-time speed planning (one workgroup per path: blocked cells over the lanes with the agent set through LDS in chunks, then the layered
+// search in LDS; dynamic LDS sized from K, a->Mb and U; device pointers) ----
+hipError_t po_launch_stplan(const po::DevCar *c, const po::DevStplan *a, hipStream_t st);
 }  // extern "C"

@@ -129,6 +129,18 @@ struct DevDynamic {
     int *status, *ok_out; double *gap_min; int *first_state, *first_agent, *stop_state; double *first_time, *gap, *v_limit;
 };
 
+// station-time planning launch arguments (po_stplan.hip): po_stplan_in / po_stplan_out with the lists of po_agent_lists flattened, the fields
+// of po_stplan_params, and Mb = min((N - 1) / stride + 1, PO_ST_MAX_STATIONS), the bound on the stations of a path that sizes the LDS.  Every output but status
+// may be null.
+struct DevStplan {
+    int B, N, S, n_agents;
+    const double *states; const int *n_states, *ok; const double *v0, *v_cap; const int *set_of;
+    const po_agent *agents; const int *first;
+    const double *v_limit_in;
+    double dt; int K, stride, U, Mb; double margin, a_max, b_max, v_max, w_acc, w_slow;
+    int *status, *ok_out, *n_layers; double *cost; int *station, *cells; double *v_limit;
+};
+
 #ifdef PO_MAP_DEVICE_CODE  // kernels and device functions: po_kernels.hip only (po_capi.cpp needs just the structs)
 // Layer k of the stack as a DevMap.  k is clamped into [0, M - 1] HERE, where it is read: a table that arrived through a device pointer was never validated, and a
 // bad entry must select a wrong layer, never an address outside the stack.
