@@ -298,7 +298,9 @@ int po_debug_set(po_handle h, const char *key, int value);
  * an unchanged size and layer count must leave it where it is); "map_layers" = M, the number of layers the handle holds (0: no map; does not synchronise); "fixed_length_used" = 1 when the last solve ran the
  * length-specialised kernels, 0 when it ran the generic ones (does not synchronise); "dp_waves_used" = 8 or 1, the waves per instance of the handle's last DP lattice
  * search — po_dp_search_batch* or the search inside po_plan_batch* (0: none yet; does not synchronise): one wave above 512 instances, under "dp_one_wave", and when
- * the eight-wave reduction scratch does not fit in LDS beside the spline; "world_cells" = size_x * size_y of the handle's world grid (po_set_world_occupancy*; 0: none;
+ * the eight-wave reduction scratch does not fit in LDS beside the spline; "smooth_variant_used" = 100 * kind + 10 * waves + WPE, the instantiation of the smoothing kernel
+ * that the handle's last po_smooth_batch* call launched: kind 0 .. 2, 1 / 4 / 8 waves per QP, WPE the occupancy bound it was compiled for (11, 42, 43 or 82; 0: no call
+ * yet, and unchanged by a call that was refused before its launch; does not synchronise); "world_cells" = size_x * size_y of the handle's world grid (po_set_world_occupancy*; 0: none;
  * does not synchronise). */
 int po_debug_get(po_handle h, const char *key, long long *value);
 
@@ -535,7 +537,11 @@ int po_bounds_batch_device(po_handle h, const po_bounds_in *in, double *bounds, 
  * info[b].status == PO_STATUS_SOLVED <=> the reference's `solver.solve()` returned true; raw (optional) = the whole QP solution in
  * the REFERENCE variable order, [B][n_max] with n_max = po_smooth_dims(kind, P).  OSQP settings come from the handle's po_params
  * (the reference runs the smoothers at OSQP's default eps_abs = eps_rel = 1e-3; create the handle accordingly to mirror that).
- * Fewer points than the reference accepts (TENSION*: 3, POST: 4, reference_path_smoother.cpp:536) -> PO_ERR_INVALID. */
+ * Fewer points than the reference accepts (TENSION*: 3, POST: 4, reference_path_smoother.cpp:536) -> PO_ERR_INVALID.  That is judged on P; n_points is
+ * not screened by either entry (the device entry cannot read it): an instance whose n_points[b] is below that minimum or above P comes back with
+ * info[b].status == PO_STATUS_UNSOLVED and zero rows of out_x / out_y / out_s (raw[b] is not written: do not read it for such an instance), the other instances are unaffected.
+ * A P whose QP does not fit the on-chip tile -> PO_ERR_UNSUPPORTED, nothing written (the admissible P are not one interval: the footprint steps with the
+ * layout of the substitution; the largest are 344 / 349 / 473 for TENSION2 / TENSION / POST). */
 enum { PO_SMOOTH_TENSION2 = 0, PO_SMOOTH_TENSION = 1, PO_SMOOTH_POST = 2 };
 typedef struct po_smooth_in {
     int kind, B, P;

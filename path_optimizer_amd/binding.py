@@ -318,7 +318,7 @@ class Engine:
 
     def debug_set(self, key: str, value: int):
         """po_debug_set: developer A/B switches (identity_order, debug_cycles, host_threads, smooth_seq, smooth_waves, smooth_nopad, smooth_debug, dp_one_wave, newton_slice, fixed_length).
-        Read-only keys go through debug_get: fixed_length_used, dp_waves_used (8 or 1: the variant of the last DP lattice search; dp_one_wave = 1 forces 1), fallback_paths,
+        Read-only keys go through debug_get: fixed_length_used, dp_waves_used (8 or 1: the variant of the last DP lattice search; dp_one_wave = 1 forces 1), smooth_variant_used (100 * kind + 10 * waves + WPE of the last smoothing launch), fallback_paths,
         newton_parked, map_ptr, map_layers."""
         _check(lib().po_debug_set(self._h, key.encode(), int(value)))
 

@@ -216,6 +216,10 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
         *value = h->dp_waves_used;
         return PO_OK;
     }
+    if (k == "smooth_variant_used") {  // which instantiation the launcher picked for the handle's last smoothing call: 100 * kind + 10 * waves per QP + WPE (0: no call yet); no device call
+        *value = h->smooth_variant_used;
+        return PO_OK;
+    }
     if (k == "fallback_paths") {  // split scheduling of refine = 2: how many paths the last solve's Newton launch handed to the fallback launch
         *value = 0;
         if (!h->fb_buf.p) return PO_OK;
@@ -1617,7 +1621,7 @@ int po_smooth_batch_device(po_handle h, const po_smooth_in *in, const po_smooth_
         D.dbg_cycles = static_cast<long long *>(h->dbg_buf.p);
     }
     if (h->timed) HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    HIP_TRY(po_launch_smooth(&D, h->stream));
+    HIP_TRY(po_launch_smooth(&D, &h->smooth_variant_used, h->stream));
     if (dbg) {
         std::vector<long long> hc(8 * (size_t)in->B);
         HIP_TRY(hipMemcpyAsync(hc.data(), D.dbg_cycles, sizeof(long long) * hc.size(), hipMemcpyDeviceToHost, h->stream));

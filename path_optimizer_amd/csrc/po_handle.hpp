@@ -97,6 +97,7 @@ struct po_handle_s {
     bool fixed_length = true;  // take the length-specialised kernels where the batch has one (po_debug_set "fixed_length"; 0: always the generic kernels).  Same results.
     int fixed_used = 0;        // ... and whether the last solve ran them (po_debug_get "fixed_length_used")
     int dp_waves_used = 0;     // waves per instance of the last DP lattice search: 8 or 1 (0: none yet; po_debug_get "dp_waves_used")
+    int smooth_variant_used = 0;  // instantiation of the last smoothing launch: 100 * kind + 10 * waves per QP + WPE, e.g. 143 = <TENSION, 4, 3> (0: none yet; po_debug_get "smooth_variant_used")
     int nw_slice = 8;  // steps of the first of the two Newton launches (po_debug_set "newton_slice"; 0: one launch).  Scheduling only.
     HostBuf fb_host; // ... and the pinned word its count is read back into (refine_chain = 2)
     // developer switches (po_debug_set; the library reads no environment variable): identity_order (block i solves path i), debug_cycles (per-phase shader

@@ -96,7 +96,7 @@ hipError_t po_launch_plan_scatter(const po::PlanRows *r, hipStream_t st);
 hipError_t po_launch_plan_clear(int B, int N, const int *stage, double *states, po_info *info, hipStream_t st);
 
 // ---- po_smooth.hip: the reference-smoothing QPs ----
-hipError_t po_launch_smooth(const po::DevSmooth *a, hipStream_t st);
+hipError_t po_launch_smooth(const po::DevSmooth *a, int *variant_used, hipStream_t st);  // *variant_used: 100 * kind + 10 * waves per QP + WPE of the instantiation launched
 size_t po_smooth_lds_bytes(int kind, int P);
 size_t po_smooth_scratch_doubles(int kind, int P);
 int po_smooth_blocked(int kind, int P);

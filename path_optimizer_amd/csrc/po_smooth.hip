@@ -1446,14 +1446,15 @@ template <int KIND, int NWV, int WPE> __global__ __launch_bounds__(64 * NWV, WPE
     }
 }
 
-template <int KIND, int NWV, int WPE> static hipError_t launch_kind_w(const DevSmooth &a, hipStream_t st, size_t lds) {
+template <int KIND, int NWV, int WPE> static hipError_t launch_kind_w(const DevSmooth &a, hipStream_t st, size_t lds, int *variant_used) {
+    if (variant_used) *variant_used = 100 * KIND + 10 * NWV + WPE;
     const size_t dyn = lds - 64;  // lds = dynamic part + the kernel's 64 static bytes (Lds::bytes)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&smooth_kernel<KIND, NWV, WPE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((smooth_kernel<KIND, NWV, WPE>), dim3(a.B), dim3(64 * NWV), dyn, st, a);
     return hipGetLastError();
 }
-template <int KIND> static hipError_t launch_kind(const DevSmooth &a, hipStream_t st, size_t lds) {
+template <int KIND> static hipError_t launch_kind(const DevSmooth &a, hipStream_t st, size_t lds, int *variant_used) {
     {
         constexpr int kCUs = 256, kLdsPerCU = 160 * 1024;
         const int by_lds = (int)(kLdsPerCU / (lds ? lds : 1));  // QPs a CU holds
@@ -1465,20 +1466,20 @@ template <int KIND> static hipError_t launch_kind(const DevSmooth &a, hipStream_
             const bool alone = by_lds == 1 || a.B <= kCUs;
             waves = (alone && ST<KIND>::n(a.P) >= 256) ? 8 : ((by_lds <= 4 || a.B <= 3 * kCUs) ? 4 : 1);
         }
-        if (waves == 8) return launch_kind_w<KIND, 8, 2>(a, st, lds);
+        if (waves == 8) return launch_kind_w<KIND, 8, 2>(a, st, lds, variant_used);
         if (waves == 4) {
             // three QPs per CU need the 168-register allocation (a handful of spilled values); up to two per CU keep the full one
-            if (by_lds >= 3 && a.B > 2 * kCUs) return launch_kind_w<KIND, 4, 3>(a, st, lds);
-            return launch_kind_w<KIND, 4, 2>(a, st, lds);
+            if (by_lds >= 3 && a.B > 2 * kCUs) return launch_kind_w<KIND, 4, 3>(a, st, lds, variant_used);
+            return launch_kind_w<KIND, 4, 2>(a, st, lds, variant_used);
         }
     }
-    return launch_kind_w<KIND, 1, 1>(a, st, lds);
+    return launch_kind_w<KIND, 1, 1>(a, st, lds, variant_used);
 }
 
 }  // namespace po
 
 // TENSION (W = 9): the block layout of the factor (band_solve_blocks) while two QPs of it fit a CU, the natural layout with the column-by-column
-// substitution beyond (P > 111: one QP per CU up to the 160 KB capacity).
+// substitution beyond (P > 117: still two QPs per CU up to P = 171, one from there to the 160 KB capacity at P = 349).
 extern "C" int po_smooth_blocked(int kind, int P) {
     return kind == PO_SMOOTH_TENSION && po::Lds<PO_SMOOTH_TENSION>::bytes(P, true) <= 80 * 1024 ? 1 : 0;
 }
@@ -1498,15 +1499,15 @@ extern "C" size_t po_smooth_scratch_doubles(int kind, int P) {
     }
     return 0;
 }
-extern "C" hipError_t po_launch_smooth(const po::DevSmooth *a0, hipStream_t st) {  // (po_smooth_lds_bytes counts the 64 static bytes too: the dynamic part is that minus 64)
+extern "C" hipError_t po_launch_smooth(const po::DevSmooth *a0, int *variant_used, hipStream_t st) {  // (po_smooth_lds_bytes counts the 64 static bytes too: the dynamic part is that minus 64)
     po::DevSmooth a1 = *a0;
     a1.blocked = (po_smooth_blocked(a1.kind, a1.P) && !a1.seq_band) ? 1 : 0;
     const po::DevSmooth *a = &a1;
     const size_t lds = a1.kind == PO_SMOOTH_TENSION ? po::Lds<PO_SMOOTH_TENSION>::bytes(a1.P, a1.blocked != 0) : po_smooth_lds_bytes(a1.kind, a1.P);
     switch (a->kind) {
-        case PO_SMOOTH_TENSION2: return po::launch_kind<PO_SMOOTH_TENSION2>(*a, st, lds);
-        case PO_SMOOTH_TENSION: return po::launch_kind<PO_SMOOTH_TENSION>(*a, st, lds);
-        case PO_SMOOTH_POST: return po::launch_kind<PO_SMOOTH_POST>(*a, st, lds);
+        case PO_SMOOTH_TENSION2: return po::launch_kind<PO_SMOOTH_TENSION2>(*a, st, lds, variant_used);
+        case PO_SMOOTH_TENSION: return po::launch_kind<PO_SMOOTH_TENSION>(*a, st, lds, variant_used);
+        case PO_SMOOTH_POST: return po::launch_kind<PO_SMOOTH_POST>(*a, st, lds, variant_used);
     }
     return hipErrorInvalidValue;
 }

@@ -395,8 +395,10 @@ def test_device_tension_full_batch_blocked_against_column_by_column(engine):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", [0, 2])
 def test_device_chunk_layout_transitions(engine, oracle, omap, kind):
-    """Sizes either side of every change in the partitioned substitution: single-lane window (tiny QPs), natural layout (fewer than 6 rows per lane),
-    chunk-padded layout with even and odd chunk lengths (W = 3), and the steps of the rows-per-lane count."""
+    """Sizes either side of every change in the partitioned substitution up to 230 points: the smallest QPs (3, 4, 5 points, POST 4, 5, 6: scan_chunk = W, one chunk
+    of W rows per lane on the natural layout, most lanes owning padding only — NOT the single-lane window, which scan_chunk selects from 261 / 325 points on only:
+    tests/test_smooth_edges.py), natural layout (fewer than 6 rows per lane), chunk-padded layout with even and odd chunk lengths (W = 3), and the steps of the
+    rows-per-lane count."""
     sizes = [3, 4, 5, 16, 17, 33, 64, 65, 97, 128, 129, 161, 192, 193, 225] if kind == 0 else [4, 5, 6, 21, 22, 43, 64, 65, 100, 128, 129, 150, 192, 193, 230]
     for P in sizes:
         inp = synth.make_smooth_inputs(40 + P, 3, P=P, kind=kind, jitter_ds=True)
