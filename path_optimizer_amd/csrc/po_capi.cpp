@@ -161,7 +161,10 @@ int po_create(int device, const po_params *params, po_handle *out) {
     }
     for (Event &e : h->evh) if (!hip_ok(hipEventCreate(&e.e), "hipEventCreate")) { delete h; return PO_ERR_HIP; }
     for (Event &e : h->evp) if (!hip_ok(hipEventCreate(&e.e), "hipEventCreate")) { delete h; return PO_ERR_HIP; }
-    h->stream = h->own_stream.s;
+    {
+        Lock g(h->mu);
+        h->stream = h->own_stream.s;
+    }
     *out = h;
     return PO_OK;
 }
@@ -169,14 +172,17 @@ int po_create(int device, const po_params *params, po_handle *out) {
 int po_destroy(po_handle h) {
     if (!h) return PO_ERR_INVALID;
     (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
+    {
+        Lock g(h->mu);
+        (void)hipStreamSynchronize(h->stream);
+    }
     delete h;  // buffers, then events, then the stream (po_handle_s, po_handle.hpp)
     return PO_OK;
 }
 
 int po_debug_set(po_handle h, const char *key, int value) {
     if (!h || !key) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     const std::string k(key);
     if (k == "identity_order") h->env_identity = value != 0;
     else if (k == "host_threads") h->host_threads = value < 0 ? 0 : value;
@@ -195,7 +201,7 @@ int po_debug_set(po_handle h, const char *key, int value) {
 int po_debug_get(po_handle h, const char *key, long long *value) {
     if (!h || !key || !value) return PO_ERR_INVALID;
     const std::string k(key);
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (k == "map_ptr") {  // where the handle's map layer lives (0: none); no device call
         *value = (long long)reinterpret_cast<uintptr_t>(h->maps.d);
         return PO_OK;
@@ -269,7 +275,7 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
 
 int po_set_stream(po_handle h, void *hip_stream) {
     if (!h) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream.s;
     return PO_OK;
 }
@@ -318,7 +324,7 @@ static int validate(const po_batch_in *in, int *n, int *m, int *C) {
     return PO_OK;
 }
 
-static void fill_dev_batch(const po_handle_s *h, po::DevBatch *D, const po_batch_in *in, const po_batch_out *out, int n, int m, int C) {
+static void fill_dev_batch(const po_handle_s *h, po::DevBatch *D, const po_batch_in *in, const po_batch_out *out, int n, int m, int C) PO_REQUIRES(h->mu) {
     D->B = in->B; D->N = in->N; D->keep = in->keep; D->C = C;
     D->ref_x = in->ref_x; D->ref_y = in->ref_y; D->ref_z = in->ref_z; D->ref_k = in->ref_k; D->ref_s = in->ref_s;
     D->bounds = in->bounds; D->x0 = in->x0; D->goal_z = in->goal_z; D->max_k = in->max_k; D->max_kp = in->max_kp;
@@ -348,7 +354,7 @@ int po_solve_batch_device(po_handle h, const po_batch_in *in, const po_batch_out
     int rc = validate(in, &n, &m, &C);
     if (rc) return rc;
     if (in->B == 0) return PO_OK;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     h->timed_host = false;  // (set again by po_solve_batch when this call is its inner solve: po_last_phase_ms never mixes this solve's events with an older call's)
     po::DevParams P;
@@ -508,10 +514,14 @@ int po_solve_batch(po_handle h, const po_batch_in *in, const po_batch_out *out) 
     }
     const size_t in_bytes = sizeof(double) * (B * N * per_pt + B * 4 + 2 * ((B + 1) / 2 + 1));
     const size_t out_bytes = sizeof(double) * (B * N * 5 + (out->x ? B * (size_t)n : 0)) + sizeof(po_info) * B;
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
+    Lock call(h->call_mu);  // the call lock, as in staged_call (po_handle.hpp); mu is NOT held while the host threads pack and unpack
+    hipStream_t st;
+    int nthr;
     {
-        std::lock_guard<std::mutex> g(h->mu);
+        Lock g(h->mu);
         if ((rc = h->in_buf.ensure(in_bytes)) || (rc = h->out_buf.ensure(out_bytes)) || (rc = h->pin_in.ensure(in_bytes)) || (rc = h->pin_out.ensure(out_bytes))) return rc;
+        st = h->stream;
+        nthr = h->host_threads > 0 ? h->host_threads : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
     }
     // ---- pack: caller's (pageable) arrays -> the pinned block, on several host threads; the block goes to the device in slices as they fill ----
     double *d = static_cast<double *>(h->in_buf.p);
@@ -539,8 +549,8 @@ int po_solve_batch(po_handle h, const po_batch_in *in, const po_batch_out *out) 
         din.order = reinterpret_cast<const int *>(reinterpret_cast<char *>(d) + oo);
         used = oo + sizeof(int) * B;
     }
-    const int nthr = h->host_threads > 0 ? h->host_threads : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-    HIP_TRY(hipEventRecord(h->evh[0], h->stream));
+    double pack_ms, unpack_ms;
+    HIP_TRY(hipEventRecord(h->evh[0], st));
     {
         const auto t0 = std::chrono::steady_clock::now();
         // the block in slices of 32 MB: slice k is on its way over PCIe while slice k + 1 is being packed (gaps between the int arrays travel as they are)
@@ -554,11 +564,11 @@ int po_solve_batch(po_handle h, const po_batch_in *in, const po_batch_out *out) 
                 if (a0 < a1) cur.push_back({pin + a0, sg.src + (a0 - s0), a1 - a0});
             }
             parallel_copy(cur, nthr);
-            HIP_TRY(hipMemcpyAsync(reinterpret_cast<char *>(d) + lo, pin + lo, hi - lo, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(reinterpret_cast<char *>(d) + lo, pin + lo, hi - lo, hipMemcpyHostToDevice, st));
         }
-        h->host_pack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    HIP_TRY(hipEventRecord(h->evh[1], h->stream));
+    HIP_TRY(hipEventRecord(h->evh[1], st));
     po_batch_out dout;
     char *ob = static_cast<char *>(h->out_buf.p);
     dout.states = reinterpret_cast<double *>(ob);
@@ -568,9 +578,9 @@ int po_solve_batch(po_handle h, const po_batch_in *in, const po_batch_out *out) 
     if (rc) return rc;
     // ---- D2H into the pinned block (one copy), then unpack on the host threads ----
     char *pout = static_cast<char *>(h->pin_out.p);
-    HIP_TRY(hipMemcpyAsync(pout, ob, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipEventRecord(h->evh[2], h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(pout, ob, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(h->evh[2], st));
+    HIP_TRY(hipStreamSynchronize(st));
     {
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<CopySeg> us;
@@ -578,8 +588,10 @@ int po_solve_batch(po_handle h, const po_batch_in *in, const po_batch_out *out) 
         if (out->x) us.push_back({reinterpret_cast<char *>(out->x), pout + sizeof(double) * B * N * 5, sizeof(double) * B * (size_t)n});
         us.push_back({reinterpret_cast<char *>(out->info), pout + sizeof(double) * (B * N * 5 + (out->x ? B * (size_t)n : 0)), sizeof(po_info) * B});
         parallel_copy(us, nthr);
-        h->host_unpack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        unpack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
+    Lock g(h->mu);
+    h->host_pack_ms = pack_ms; h->host_unpack_ms = unpack_ms;
     h->timed_host = true;
     return PO_OK;
 }
@@ -588,7 +600,9 @@ int po_solve_batch(po_handle h, const po_batch_in *in, const po_batch_out *out) 
 // under the copies), [1] the solve (= po_last_kernel_ms), [2] D2H, [3] host pack alone (wall), [4] host unpack (wall).  And, for the split scheduling of
 // refine = 2, the solve's own phases: [5] equilibration + warm-start launches, [6] the Newton launch, [7] the per-round fallback launches + status sweep (0 otherwise).
 int po_last_phase_ms(po_handle h, float *ms8) {
-    if (!h || !ms8 || !h->timed) return PO_ERR_INVALID;
+    if (!h || !ms8) return PO_ERR_INVALID;
+    Lock g(h->mu);
+    if (!h->timed) return PO_ERR_INVALID;
     for (int i = 0; i < 8; ++i) ms8[i] = 0.0f;
     HIP_TRY(hipEventSynchronize(h->ev1));
     HIP_TRY(hipEventElapsedTime(&ms8[1], h->ev0, h->ev1));
@@ -613,30 +627,27 @@ int po_assemble_batch(po_handle h, const po_batch_in *in, double *l, double *u, 
     int rc = validate(in, &n, &m, &C);
     if (rc) return rc;
     if (in->B == 0) return PO_OK;
-    HIP_TRY(hipSetDevice(h->device));
     const size_t B = in->B, N = in->N;
     const bool kpc = in->formulation == PO_KPC;
-    Stage I, O;  // the inputs in in_buf, the three outputs in asm_buf
-    const Slot<double> rx = I.in(in->ref_x, B * N), ry = I.in(in->ref_y, B * N), rz = I.in(in->ref_z, B * N), rk = I.in(in->ref_k, B * N), rs = I.in(in->ref_s, B * N);
-    const Slot<double> bd = I.in(in->bounds, B * N * 8), x0 = I.in(in->x0, B * 3), gz = I.in(in->goal_z, B);
-    const Slot<double> mk = I.in(kpc ? in->max_k : nullptr, B * N), mkp = I.in(kpc ? in->max_kp : nullptr, B * N);
-    const Slot<double> dl = O.out(l, B * (size_t)m), du = O.out(u, B * (size_t)m), dd = O.out(dyn, B * (N - 1) * 3);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        if ((rc = I.reserve(h, h->in_buf)) || (rc = O.reserve(h, h->asm_buf))) return rc;
-    }
-    PO_TRY(I.copy_in(h));
-    po_batch_in din = *in;
-    din.ref_x = rx; din.ref_y = ry; din.ref_z = rz; din.ref_k = rk; din.ref_s = rs; din.bounds = bd; din.x0 = x0; din.goal_z = gz;
-    if (kpc) { din.max_k = mk; din.max_kp = mkp; }
-    HIP_TRY(hipMemsetAsync(dl, 0, O.bytes(), h->stream));
-    po::DevParams P;
-    make_dev_params(h, in->formulation, in->keep, &P);
-    po::DevBatch D;
-    fill_dev_batch(h, &D, &din, nullptr, n, m, C);
-    HIP_TRY(po_launch_assemble(in->formulation, &D, &P, dl, du, dd, h->stream));
-    return O.copy_out(h);
+    Stage S;  // the inputs, then the three outputs side by side
+    const Slot<double> rx = S.in(in->ref_x, B * N), ry = S.in(in->ref_y, B * N), rz = S.in(in->ref_z, B * N), rk = S.in(in->ref_k, B * N), rs = S.in(in->ref_s, B * N);
+    const Slot<double> bd = S.in(in->bounds, B * N * 8), x0 = S.in(in->x0, B * 3), gz = S.in(in->goal_z, B);
+    const Slot<double> mk = S.in(kpc ? in->max_k : nullptr, B * N), mkp = S.in(kpc ? in->max_kp : nullptr, B * N);
+    const size_t out_from = (S.bytes() + 15) & ~(size_t)15;  // where dl will start
+    const Slot<double> dl = S.out(l, B * (size_t)m), du = S.out(u, B * (size_t)m), dd = S.out(dyn, B * (N - 1) * 3);
+    return staged_call(h, S, &po_handle_s::asm_buf, false, [&]() -> int {  // (no device twin: the launch itself, under mu like one)
+        Lock g(h->mu);
+        po_batch_in din = *in;
+        din.ref_x = rx; din.ref_y = ry; din.ref_z = rz; din.ref_k = rk; din.ref_s = rs; din.bounds = bd; din.x0 = x0; din.goal_z = gz;
+        if (kpc) { din.max_k = mk; din.max_kp = mkp; }
+        HIP_TRY(hipMemsetAsync(dl, 0, S.bytes() - out_from, h->stream));
+        po::DevParams P;
+        make_dev_params(h, in->formulation, in->keep, &P);
+        po::DevBatch D;
+        fill_dev_batch(h, &D, &din, nullptr, n, m, C);
+        HIP_TRY(po_launch_assemble(in->formulation, &D, &P, dl, du, dd, h->stream));
+        return PO_OK;
+    });
 }
 
 int po_scaling_batch(po_handle h, const po_batch_in *in, double *out) {
@@ -646,28 +657,26 @@ int po_scaling_batch(po_handle h, const po_batch_in *in, double *out) {
     int rc = validate(in, &n, &m, &C);
     if (rc) return rc;
     if (in->B == 0) return PO_OK;
-    HIP_TRY(hipSetDevice(h->device));
     const size_t B = in->B, N = in->N;
-    Stage I, O;  // ref_s in in_buf, the factors in scale_buf
-    const Slot<double> rs = I.in(in->ref_s, B * N), sc = O.out(out, 64 * B);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        if ((rc = I.reserve(h, h->in_buf)) || (rc = O.reserve(h, h->scale_buf))) return rc;
-    }
-    PO_TRY(I.copy_in(h));
-    po_batch_in din = *in;
-    din.ref_s = rs;
-    po::DevParams P;
-    make_dev_params(h, in->formulation, in->keep, &P);
-    po::DevBatch D;
-    fill_dev_batch(h, &D, &din, nullptr, n, m, C);
-    HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, sc, nullptr, nullptr, h->stream));  // (diagnostic: no solve follows, nothing to reset)
-    return O.copy_out(h);
+    Stage S;
+    const Slot<double> rs = S.in(in->ref_s, B * N), sc = S.out(out, 64 * B);
+    return staged_call(h, S, &po_handle_s::asm_buf, false, [&]() -> int {  // (no device twin: the launch itself, under mu like one)
+        Lock g(h->mu);
+        po_batch_in din = *in;
+        din.ref_s = rs;
+        po::DevParams P;
+        make_dev_params(h, in->formulation, in->keep, &P);
+        po::DevBatch D;
+        fill_dev_batch(h, &D, &din, nullptr, n, m, C);
+        HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, sc, nullptr, nullptr, h->stream));  // (diagnostic: no solve follows, nothing to reset)
+        return PO_OK;
+    });
 }
 
 int po_last_kernel_ms(po_handle h, float *ms) {
-    if (!h || !ms || !h->timed) return PO_ERR_INVALID;
+    if (!h || !ms) return PO_ERR_INVALID;
+    Lock g(h->mu);
+    if (!h->timed) return PO_ERR_INVALID;
     HIP_TRY(hipEventSynchronize(h->ev1));
     HIP_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
     return PO_OK;
@@ -693,8 +702,8 @@ static po::DevCar make_car(const po_params &p) {
 }
 
 // ---- the map stack.  Every install goes through publish_stack; the single-map entries are the stack entries with M = 1. ----
-// The view the kernels get, after the layers are in place (h->mu held).  An install that changes M drops the assignment, one with the same M keeps it.
-static void publish_stack(po_handle h, int M, int sx, int sy, double res, double px, double py, bool layer_pos) {
+// The view the kernels get, after the layers are in place.  An install that changes M drops the assignment, one with the same M keeps it.
+static void publish_stack(po_handle h, int M, int sx, int sy, double res, double px, double py, bool layer_pos) PO_REQUIRES(h->mu) {
     const bool keep = h->maps.M == M && h->maps.layer_of;
     po::DevMaps s{};
     s.d = static_cast<const float *>(h->map_buf.p); s.sx = sx; s.sy = sy; s.res = res; s.px = px; s.py = py;
@@ -704,8 +713,8 @@ static void publish_stack(po_handle h, int M, int sx, int sy, double res, double
     s.n_assign = keep ? h->maps.n_assign : 0;
     h->maps = s;
 }
-// M float layers from host memory (h->mu held): upload, synchronise, publish
-static int install_layers(po_handle h, int M, const po_map *map, const double *pos_xy) {
+// M float layers from host memory: upload, synchronise, publish
+static int install_layers(po_handle h, int M, const po_map *map, const double *pos_xy) PO_REQUIRES(h->mu) {
     HIP_TRY(hipSetDevice(h->device));
     const size_t bytes = sizeof(float) * (size_t)M * (size_t)map->size_x * (size_t)map->size_y;
     if (bytes > h->map_buf.cap) h->maps.d = nullptr;  // the old layers are about to be released: no map until the new ones are in place
@@ -722,21 +731,21 @@ static int install_layers(po_handle h, int M, const po_map *map, const double *p
 
 int po_set_map(po_handle h, const po_map *map) {
     if (!h || !map || !map->distance || map->size_x < 1 || map->size_y < 1 || !(map->resolution > 0)) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     return install_layers(h, 1, map, nullptr);
 }
 
 int po_set_map_stack(po_handle h, int M, const po_map *layers, const double *pos_xy) {
     if (!h || M < 1 || !layers || !layers->distance || layers->size_x < 1 || layers->size_y < 1 || !(layers->resolution > 0)) return PO_ERR_INVALID;
     if (layers->size_x > po_edt_max_side() || layers->size_y > po_edt_max_side() || M > po_edt_max_images()) return PO_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> call(h->call_mu);
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock call(h->call_mu);
+    Lock g(h->mu);
     return install_layers(h, M, layers, pos_xy);
 }
 
 int po_set_map_assignment_device(po_handle h, int n, const int *layer_of) {
     if (!h || n < 0) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (n == 0 || !layer_of) {  // clear: every instance reads layer 0 again (launches already enqueued got the table by value of its address: the block stays)
         h->maps.layer_of = nullptr; h->maps.n_assign = 0;
         return PO_OK;
@@ -751,8 +760,8 @@ int po_set_map_assignment_device(po_handle h, int n, const int *layer_of) {
 
 int po_set_map_assignment(po_handle h, int n, const int *layer_of) {
     if (!h || n < 0) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> call(h->call_mu);
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock call(h->call_mu);
+    Lock g(h->mu);
     if (n == 0 || !layer_of) {
         h->maps.layer_of = nullptr; h->maps.n_assign = 0;
         return PO_OK;
@@ -783,7 +792,7 @@ static int check_occupancy(po_handle h, int M, const po_occupancy *occ) {
 int po_distance_map_batch_device(po_handle h, int M, const po_occupancy *occ, float *distance) {
     if (int rc = check_occupancy(h, M, occ)) return rc;
     if (!distance) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = grow_after_sync(h, h->edt_buf, po_edt_scratch_bytes(M, occ->size_x, occ->size_y))) return rc;
     HIP_TRY(po_launch_edt(occ->cells, M, occ->size_x, occ->size_y, (float)occ->resolution, h->edt_buf.p, distance, h->stream));
@@ -797,21 +806,16 @@ int po_distance_map_batch(po_handle h, int M, const po_occupancy *occ, float *di
     Stage S;
     const Slot<float> d_dist = S.out(distance, cells);
     const Slot<unsigned char> d_cells = S.in(occ->cells, cells);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->edt_io, true));
-    }
-    po_occupancy dev = *occ;
-    dev.cells = d_cells;
-    PO_TRY(po_distance_map_batch_device(h, M, &dev, d_dist));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::edt_io, true, [&] {
+        po_occupancy dev = *occ;
+        dev.cells = d_cells;
+        return po_distance_map_batch_device(h, M, &dev, d_dist);
+    });
 }
 
-// M images on the device -> the handle's stack (h->mu held, device set): grow what has to grow, transform, publish
-static int stack_from_images(po_handle h, int M, const unsigned char *cells, int sx, int sy, double res, double px, double py, const double *pos_xy) {
+// M images on the device -> the handle's stack (device set): grow what has to grow, transform, publish
+static int stack_from_images(po_handle h, int M, const unsigned char *cells, int sx, int sy, double res, double px, double py, const double *pos_xy)
+    PO_REQUIRES(h->mu) {
     // same M and size as before: every block is large enough already — nothing is allocated, nothing waits; the transform overwrites the layers in stream order
     const size_t stack_bytes = sizeof(float) * (size_t)M * (size_t)sx * (size_t)sy;
     if (stack_bytes > h->map_buf.cap) h->maps.d = nullptr;  // the old layers are about to be released: no map until the new ones are in place
@@ -828,7 +832,7 @@ static int stack_from_images(po_handle h, int M, const unsigned char *cells, int
 
 int po_set_map_stack_occupancy_device(po_handle h, int M, const po_occupancy *occ, const double *pos_xy) {
     if (int rc = check_occupancy(h, M, occ)) return rc;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     return stack_from_images(h, M, occ->cells, occ->size_x, occ->size_y, occ->resolution, occ->pos_x, occ->pos_y, pos_xy);
 }
@@ -840,17 +844,12 @@ int po_set_map_stack_occupancy(po_handle h, int M, const po_occupancy *occ, cons
     Stage S;
     const Slot<unsigned char> d_cells = S.in(occ->cells, (size_t)M * (size_t)occ->size_x * (size_t)occ->size_y);
     const Slot<double> d_pos = S.in(pos_xy, 2 * (size_t)M);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and the final synchronisation are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->edt_io, true));
-    }
-    po_occupancy dev = *occ;
-    dev.cells = d_cells;
-    PO_TRY(po_set_map_stack_occupancy_device(h, M, &dev, d_pos));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);  // (no output: the synchronise alone) like po_set_map: the caller's images may be reused, the stack is in place
+    // (no output: the synchronise alone) like po_set_map: the caller's images may be reused, the stack is in place
+    return staged_call(h, S, &po_handle_s::edt_io, true, [&] {
+        po_occupancy dev = *occ;
+        dev.cells = d_cells;
+        return po_set_map_stack_occupancy_device(h, M, &dev, d_pos);
+    });
 }
 
 int po_set_map_occupancy(po_handle h, const po_occupancy *occ) { return po_set_map_stack_occupancy(h, 1, occ, nullptr); }
@@ -908,7 +907,7 @@ struct StagedLists {
 int po_rasterize_batch_device(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy, unsigned char *cells_out) {
     if (int rc = check_lists(h, M, lists)) return rc;
     if (!cells_out) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(po_launch_raster(lists, M, pos_xy, cells_out, h->stream));
     return PO_OK;
@@ -922,21 +921,15 @@ int po_rasterize_batch(po_handle h, int M, const po_obstacle_lists *lists, const
     StagedLists d;
     d.declare(S, M, lists, pos_xy);
     const Slot<unsigned char> d_cells = S.out(cells_out, (size_t)M * (size_t)lists->size_x * (size_t)lists->size_y);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->edt_io, true));
-    }
-    const po_obstacle_lists dev = d.device(lists);
-    PO_TRY(po_rasterize_batch_device(h, M, &dev, d.pos, d_cells));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::edt_io, true, [&] {
+        const po_obstacle_lists dev = d.device(lists);
+        return po_rasterize_batch_device(h, M, &dev, d.pos, d_cells);
+    });
 }
 
 int po_set_map_stack_obstacles_device(po_handle h, int M, const po_obstacle_lists *lists, const double *pos_xy) {
     if (int rc = check_lists(h, M, lists)) return rc;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     // the images live in a grow-only block of the handle: with the M and size it already holds nothing is allocated and nothing waits
     if (int rc = grow_after_sync(h, h->raster_buf, (size_t)M * (size_t)lists->size_x * (size_t)lists->size_y)) return rc;
@@ -951,16 +944,11 @@ int po_set_map_stack_obstacles(po_handle h, int M, const po_obstacle_lists *list
     Stage S;  // obs, first, pos_xy and the base: the images never exist on the host
     StagedLists d;
     d.declare(S, M, lists, pos_xy);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and the final synchronisation are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->edt_io, true));
-    }
-    const po_obstacle_lists dev = d.device(lists);
-    PO_TRY(po_set_map_stack_obstacles_device(h, M, &dev, d.pos));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);  // (no output: the synchronise alone) the caller's lists may be reused, the stack is in place
+    // (no output: the synchronise alone) the caller's lists may be reused, the stack is in place
+    return staged_call(h, S, &po_handle_s::edt_io, true, [&] {
+        const po_obstacle_lists dev = d.device(lists);
+        return po_set_map_stack_obstacles_device(h, M, &dev, d.pos);
+    });
 }
 
 // ---- the static world: a world grid on the handle, polygon rings (po_scene.hip) --------------------------------
@@ -972,8 +960,8 @@ static int check_world(po_handle h, const po_occupancy *w, int outside_occupied)
     if (w->size_x > PO_WORLD_MAX_SIDE || w->size_y > PO_WORLD_MAX_SIDE) return PO_ERR_UNSUPPORTED;
     return PO_OK;
 }
-// The image into the handle's block, on the stream (h->mu held): launches already enqueued that read the old world run before the copy
-static int install_world(po_handle h, const po_occupancy *w, int outside_occupied, hipMemcpyKind kind) {
+// The image into the handle's block, on the stream: launches already enqueued that read the old world run before the copy
+static int install_world(po_handle h, const po_occupancy *w, int outside_occupied, hipMemcpyKind kind) PO_REQUIRES(h->mu) {
     if (!w) {  // (the block stays: launches already enqueued got its address by value)
         h->world = po_occupancy{};
         return PO_OK;
@@ -991,14 +979,14 @@ static int install_world(po_handle h, const po_occupancy *w, int outside_occupie
 
 int po_set_world_occupancy_device(po_handle h, const po_occupancy *world, int outside_occupied) {
     if (int rc = check_world(h, world, outside_occupied)) return rc;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     return install_world(h, world, outside_occupied, hipMemcpyDeviceToDevice);
 }
 
 int po_set_world_occupancy(po_handle h, const po_occupancy *world, int outside_occupied) {
     if (int rc = check_world(h, world, outside_occupied)) return rc;
-    std::lock_guard<std::mutex> call(h->call_mu);
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock call(h->call_mu);
+    Lock g(h->mu);
     PO_TRY(install_world(h, world, outside_occupied, hipMemcpyHostToDevice));
     if (world) HIP_TRY(hipStreamSynchronize(h->stream));  // the caller's image may be reused
     return PO_OK;
@@ -1056,8 +1044,8 @@ struct StagedScene {
         return d;
     }
 };
-// scene -> M images at `cells` on the device (h->mu held, device set): po_raster.hip's image of the lists, then the world and the rings ORed into it
-static int scene_images(po_handle h, int M, const po_scene *S, const double *pos_xy, unsigned char *cells) {
+// scene -> M images at `cells` on the device (device set): po_raster.hip's image of the lists, then the world and the rings ORed into it
+static int scene_images(po_handle h, int M, const po_scene *S, const double *pos_xy, unsigned char *cells) PO_REQUIRES(h->mu) {
     HIP_TRY(po_launch_raster(&S->lists, M, pos_xy, cells, h->stream));
     if (S->rings.n_rings == 0 && !S->use_world) return PO_OK;  // nothing to add: the bytes of po_rasterize_batch
     po_scene sc = *S;
@@ -1065,12 +1053,16 @@ static int scene_images(po_handle h, int M, const po_scene *S, const double *pos
     HIP_TRY(po_launch_scene(&sc, M, pos_xy, S->use_world ? &h->world : nullptr, h->world_outside, cells, h->stream));
     return PO_OK;
 }
-static bool world_missing(po_handle h, const po_scene *S) { return S->use_world && !h->world.cells; }  // (h->mu held)
+static bool world_missing(po_handle h, const po_scene *S) PO_REQUIRES(h->mu) { return S->use_world && !h->world.cells; }
+// ... as the pre-check of staged_call: a scene entry that lacks its world refuses before anything is staged
+static auto needs_world(const po_scene *S) {
+    return [S](po_handle h) PO_REQUIRES(h->mu) { return world_missing(h, S) ? PO_ERR_INVALID : PO_OK; };
+}
 
 int po_rasterize_scene_batch_device(po_handle h, int M, const po_scene *scene, const double *pos_xy, unsigned char *cells_out) {
     if (int rc = check_scene(h, M, scene)) return rc;
     if (!cells_out) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (world_missing(h, scene)) return PO_ERR_INVALID;
     HIP_TRY(hipSetDevice(h->device));
     return scene_images(h, M, scene, pos_xy, cells_out);
@@ -1084,22 +1076,15 @@ int po_rasterize_scene_batch(po_handle h, int M, const po_scene *scene, const do
     StagedScene d;
     d.declare(S, M, scene, pos_xy);
     const Slot<unsigned char> d_cells = S.out(cells_out, (size_t)M * (size_t)scene->lists.size_x * (size_t)scene->lists.size_y);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        if (world_missing(h, scene)) return PO_ERR_INVALID;  // (nothing has been touched)
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->edt_io, true));
-    }
-    const po_scene dev = d.device(scene);
-    PO_TRY(po_rasterize_scene_batch_device(h, M, &dev, d.lists.pos, d_cells));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::edt_io, true, [&] {
+        const po_scene dev = d.device(scene);
+        return po_rasterize_scene_batch_device(h, M, &dev, d.lists.pos, d_cells);
+    }, needs_world(scene));
 }
 
 int po_set_map_stack_scene_device(po_handle h, int M, const po_scene *scene, const double *pos_xy) {
     if (int rc = check_scene(h, M, scene)) return rc;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (world_missing(h, scene)) return PO_ERR_INVALID;
     HIP_TRY(hipSetDevice(h->device));
     const po_obstacle_lists &L = scene->lists;
@@ -1116,23 +1101,17 @@ int po_set_map_stack_scene(po_handle h, int M, const po_scene *scene, const doub
     Stage S;  // the lists, the ring tables, pos_xy and the base: the images never exist on the host
     StagedScene d;
     d.declare(S, M, scene, pos_xy);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and the final synchronisation are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        if (world_missing(h, scene)) return PO_ERR_INVALID;  // (nothing has been touched)
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->edt_io, true));
-    }
-    const po_scene dev = d.device(scene);
-    PO_TRY(po_set_map_stack_scene_device(h, M, &dev, d.lists.pos));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);  // (no output: the synchronise alone) the caller's tables may be reused, the stack is in place
+    // (no output: the synchronise alone) the caller's tables may be reused, the stack is in place
+    return staged_call(h, S, &po_handle_s::edt_io, true, [&] {
+        const po_scene dev = d.device(scene);
+        return po_set_map_stack_scene_device(h, M, &dev, d.lists.pos);
+    }, needs_world(scene));
 }
 
 int po_get_map_layer(po_handle h, int k, po_map *geometry_out, float *distance_or_null) {
     if (!h || !geometry_out) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> call(h->call_mu);
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock call(h->call_mu);
+    Lock g(h->mu);
     const po::DevMaps &s = h->maps;
     if (!s.d || k < 0 || k >= s.M) return PO_ERR_INVALID;
     double pos[2] = {s.px, s.py};
@@ -1161,7 +1140,7 @@ static bool densify_args_ok(po_handle h, int B, int N, const double *states, con
 
 int po_postcheck_batch_device(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid, int *ok) {
     if (!postcheck_args_ok(h, B, N, states, info, n_valid, ok)) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (!h->maps.d && h->params.enable_collision_check) return PO_ERR_INVALID;  // no map set
     if (!assignment_covers(h, B)) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
@@ -1173,7 +1152,7 @@ int po_postcheck_batch_device(po_handle h, int B, int N, const int *n_points, co
 
 int po_densify_batch_device(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int M, double *out_states, int *n_out, int *ok) {
     if (!densify_args_ok(h, B, N, states, info, M, out_states, n_out, ok)) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (!h->maps.d && h->params.enable_collision_check) return PO_ERR_INVALID;  // no map set
     if (!assignment_covers(h, B)) return PO_ERR_INVALID;
     if (!(h->params.output_spacing > 0)) return PO_ERR_INVALID;
@@ -1192,15 +1171,7 @@ int po_densify_batch(po_handle h, int B, int N, const int *n_points, const doubl
     const Slot<double> d_states = S.in(states, 5 * (size_t)B * N), d_out = S.out(out_states, 5 * (size_t)B * M);
     const Slot<po_info> d_info = S.in(info, B);
     const Slot<int> d_np = S.in(n_points, B), d_nout = S.out(n_out, B), d_ok = S.out(ok, B);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->post_buf));
-    }
-    PO_TRY(po_densify_batch_device(h, B, N, d_np, d_states, d_info, M, d_out, d_nout, d_ok));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] { return po_densify_batch_device(h, B, N, d_np, d_states, d_info, M, d_out, d_nout, d_ok); });
 }
 
 int po_postcheck_batch(po_handle h, int B, int N, const int *n_points, const double *states, const po_info *info, int *n_valid, int *ok) {
@@ -1210,15 +1181,7 @@ int po_postcheck_batch(po_handle h, int B, int N, const int *n_points, const dou
     const Slot<double> d_states = S.in(states, 5 * (size_t)B * N);
     const Slot<po_info> d_info = S.in(info, B);
     const Slot<int> d_np = S.in(n_points, B), d_nvalid = S.out(n_valid, B), d_ok = S.out(ok, B);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->post_buf));
-    }
-    PO_TRY(po_postcheck_batch_device(h, B, N, d_np, d_states, d_info, d_nvalid, d_ok));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] { return po_postcheck_batch_device(h, B, N, d_np, d_states, d_info, d_nvalid, d_ok); });
 }
 
 // ---- score and select --------------------------------------------------------------------------
@@ -1247,7 +1210,7 @@ static bool select_args_ok(po_handle h, const po_select_params *p, const po_sele
 int po_select_batch_device(po_handle h, const po_select_params *p, const po_select_in *in, const po_select_out *out) {
     if (!select_args_ok(h, p, in, out)) return PO_ERR_INVALID;
     if (in->B == 0 || in->G == 0) return PO_OK;  // nothing to score or nothing to select: no launch, whatever the handle holds
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (!h->maps.d || !assignment_covers(h, in->B)) return PO_ERR_INVALID;  // po_set_map first; an assignment covers every candidate
     HIP_TRY(hipSetDevice(h->device));
     const size_t gs_bytes = (sizeof(int) * ((size_t)in->G + 1) + 15) & ~(size_t)15;
@@ -1289,18 +1252,12 @@ int po_select_batch(po_handle h, const po_select_params *p, const po_select_in *
         const Slot<double> feat = out->feat ? S.out(out->feat, PO_N_FEAT * B) : Slot<double>{}, cost = out->cost ? S.out(out->cost, B) : Slot<double>{};
         const Slot<double> bc = out->best_cost ? S.out(out->best_cost, G) : Slot<double>{}, ss = out->sel_states ? S.out(out->sel_states, 5 * G * N) : Slot<double>{};
         const Slot<int> best = S.out(out->best, G), nf = out->n_feasible ? S.out(out->n_feasible, G) : Slot<int>{}, sn = out->sel_n ? S.out(out->sel_n, G) : Slot<int>{};
-        std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-        {
-            std::lock_guard<std::mutex> g(h->mu);
-            HIP_TRY(hipSetDevice(h->device));
-            PO_TRY(S.upload(h, h->post_buf));
-        }
-        d.states = states; d.goal = goal; d.prev_states = prev; d.n_states = ns; d.ok = ok; d.group_start = gs; d.prev_n = pn;
-        d.Np = (int)Np;
-        o = po_select_out{feat, cost, best, bc, nf, ss, sn};
-        PO_TRY(po_select_batch_device(h, p, &d, &o));
-        std::lock_guard<std::mutex> g(h->mu);
-        return S.copy_out(h);
+        return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+            d.states = states; d.goal = goal; d.prev_states = prev; d.n_states = ns; d.ok = ok; d.group_start = gs; d.prev_n = pn;
+            d.Np = (int)Np;
+            o = po_select_out{feat, cost, best, bc, nf, ss, sn};
+            return po_select_batch_device(h, p, &d, &o);
+        });
     }
     return PO_OK;  // B = 0 or G = 0: nothing is staged, launched or written
 }
@@ -1323,7 +1280,7 @@ static bool speed_args_ok(po_handle h, const po_speed_params *p, const po_speed_
 int po_speed_batch_device(po_handle h, const po_speed_params *p, const po_speed_in *in, const po_speed_out *out) {
     if (!speed_args_ok(h, p, in, out)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;  // nothing to profile: no launch, whatever the handle holds
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (p->use_map && (!h->maps.d || !assignment_covers(h, in->B))) return PO_ERR_INVALID;  // po_set_map first; an assignment covers every path
     HIP_TRY(hipSetDevice(h->device));
     po::DevSpeed D{};
@@ -1350,17 +1307,11 @@ int po_speed_batch(po_handle h, const po_speed_params *p, const po_speed_in *in,
     const Slot<double> v = S.out(out->v, bn), a = S.out(out->a, bn), t = out->t ? S.out(out->t, bn) : Slot<double>{};
     const Slot<double> tt = out->total_time ? S.out(out->total_time, B) : Slot<double>{};
     const Slot<int> status = S.out(out->status, B);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->post_buf));
-    }
-    const po_speed_in d{in->B, in->N, states, ns, ok, v0, ve, vl};
-    const po_speed_out o{v, a, t, tt, status};
-    PO_TRY(po_speed_batch_device(h, p, &d, &o));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+        const po_speed_in d{in->B, in->N, states, ns, ok, v0, ve, vl};
+        const po_speed_out o{v, a, t, tt, status};
+        return po_speed_batch_device(h, p, &d, &o);
+    });
 }
 
 // ---- moving obstacles (po_dynamic.hip) ----------------------------------------------------------
@@ -1404,7 +1355,7 @@ static bool dynamic_lists_ok(const po_dynamic_in *in) {
 int po_dynamic_batch_device(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out) {
     if (!dynamic_args_ok(h, p, in, out)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;  // nothing to check: no launch, whatever the handle holds
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     po::DevDynamic D{};
     D.B = in->B; D.N = in->N; D.S = in->agents->S; D.n_agents = in->agents->n_agents;
@@ -1433,18 +1384,12 @@ int po_dynamic_batch(po_handle h, const po_dynamic_params *p, const po_dynamic_i
     auto opt_d = [&](double *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<double>{}; };
     const Slot<int> status = S.out(out->status, B), ok_out = opt_i(out->ok_out), fs = opt_i(out->first_state), fa = opt_i(out->first_agent), ss = opt_i(out->stop_state);
     const Slot<double> gmin = opt_d(out->gap_min, B), ft = opt_d(out->first_time, B), gap = opt_d(out->gap, bn), vl = opt_d(out->v_limit, bn);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->post_buf));
-    }
-    const po_agent_lists dl{agents, first, L->n_agents, L->S};
-    const po_dynamic_in d{in->B, in->N, states, ns, ok, t, set_of, &dl, vin};
-    const po_dynamic_out o{status, ok_out, gmin, fs, fa, ss, ft, gap, vl};
-    PO_TRY(po_dynamic_batch_device(h, p, &d, &o));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+        const po_agent_lists dl{agents, first, L->n_agents, L->S};
+        const po_dynamic_in d{in->B, in->N, states, ns, ok, t, set_of, &dl, vin};
+        const po_dynamic_out o{status, ok_out, gmin, fs, fa, ss, ft, gap, vl};
+        return po_dynamic_batch_device(h, p, &d, &o);
+    });
 }
 
 // ---- station-time speed planning (po_stplan.hip) ------------------------------------------------
@@ -1470,7 +1415,7 @@ static bool stplan_args_ok(po_handle h, const po_stplan_params *p, const po_stpl
 int po_stplan_batch_device(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out) {
     if (!stplan_args_ok(h, p, in, out)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;  // nothing to plan: no launch, whatever the handle holds
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     po::DevStplan D{};
     D.B = in->B; D.N = in->N; D.S = in->agents->S; D.n_agents = in->agents->n_agents;
@@ -1505,18 +1450,12 @@ int po_stplan_batch(po_handle h, const po_stplan_params *p, const po_stplan_in *
     const Slot<int> status = S.out(out->status, B), ok_out = opt_i(out->ok_out, B), nl = opt_i(out->n_layers, B);
     const Slot<int> station = opt_i(out->station, B * (PO_ST_MAX_LAYERS + 1)), cells = opt_i(out->cells, B * (size_t)p->K * PO_ST_MAX_STATIONS);
     const Slot<double> cost = opt_d(out->cost, B), vl = opt_d(out->v_limit, bn);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->post_buf));
-    }
-    const po_agent_lists dl{agents, first, L->n_agents, L->S};
-    const po_stplan_in d{in->B, in->N, states, ns, ok, v0, cap, set_of, &dl, vin};
-    const po_stplan_out o{status, ok_out, nl, cost, station, cells, vl};
-    PO_TRY(po_stplan_batch_device(h, p, &d, &o));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+        const po_agent_lists dl{agents, first, L->n_agents, L->S};
+        const po_stplan_in d{in->B, in->N, states, ns, ok, v0, cap, set_of, &dl, vin};
+        const po_stplan_out o{status, ok_out, nl, cost, station, cells, vl};
+        return po_stplan_batch_device(h, p, &d, &o);
+    });
 }
 
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------
@@ -1527,7 +1466,7 @@ static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bo
 
 int po_bounds_batch_device(po_handle h, const po_bounds_in *in, double *bounds, int *n_valid) {
     if (!bounds_args_ok(h, in, bounds, n_valid)) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (!h->maps.d || !assignment_covers(h, in->B)) return PO_ERR_INVALID;  // po_set_map first; an assignment covers every instance
     if (in->B == 0) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));
@@ -1554,16 +1493,10 @@ int po_bounds_batch(po_handle h, const po_bounds_in *in, double *bounds, int *n_
     const Slot<int> np = S.in(in->n_points, B), nk = S.in(in->n_knots, B);
     const Slot<double> d_bounds = S.out(bounds, 8 * bn);
     const Slot<int> d_nvalid = S.out(n_valid, B);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->bnd_buf));
-    }
-    const po_bounds_in d{in->B, in->N, in->K, rx, ry, rz, rs, np, ks, kx, ky, nk};
-    PO_TRY(po_bounds_batch_device(h, &d, d_bounds, d_nvalid));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::bnd_buf, false, [&] {
+        const po_bounds_in d{in->B, in->N, in->K, rx, ry, rz, rs, np, ks, kx, ky, nk};
+        return po_bounds_batch_device(h, &d, d_bounds, d_nvalid);
+    });
 }
 
 // ---- reference-smoothing QPs -----------------------------------------------------------------------
@@ -1589,7 +1522,7 @@ static int smooth_args_ok(const po_smooth_in *in, const po_smooth_out *out) {
 
 int po_smooth_batch_device(po_handle h, const po_smooth_in *in, const po_smooth_out *out) {
     if (!h || !smooth_args_ok(in, out)) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (in->kind == PO_SMOOTH_TENSION && (!h->maps.d || !assignment_covers(h, in->B))) return PO_ERR_INVALID;  // po_set_map first (clearance of every point)
     if (in->B == 0) return PO_OK;
     if (po_smooth_lds_bytes(in->kind, in->P) > 160 * 1024) return PO_ERR_UNSUPPORTED;
@@ -1649,17 +1582,11 @@ int po_smooth_batch(po_handle h, const po_smooth_in *in, const po_smooth_out *ou
     const Slot<double> ox = S.out(out->x, np), oy = S.out(out->y, np), os = S.out(out->s, np);
     const Slot<po_info> oinfo = S.out(out->info, B);
     const Slot<double> oraw = out->raw ? S.out(out->raw, B * (size_t)nmax) : Slot<double>{};
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->smooth_io));
-    }
-    const po_smooth_in d{in->kind, in->B, in->P, n_points, x, y, angle, k, s, lb, ub, l0};
-    const po_smooth_out dout{ox, oy, os, oinfo, oraw};
-    PO_TRY(po_smooth_batch_device(h, &d, &dout));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::smooth_io, false, [&] {
+        const po_smooth_in d{in->kind, in->B, in->P, n_points, x, y, angle, k, s, lb, ub, l0};
+        const po_smooth_out dout{ox, oy, os, oinfo, oraw};
+        return po_smooth_batch_device(h, &d, &dout);
+    });
 }
 
 // ---- reference re-sampling, limits, DP lattice search -----------------------------------------------
@@ -1681,7 +1608,7 @@ int po_resample_batch_device(po_handle h, const po_spline_in *in, double ds_smal
     if (!(ds_smaller <= ds_larger) || !(ds_smaller > 0)) return PO_ERR_INVALID;  // CHECK_LE(delta_s_smaller, delta_s_larger)
     if (in->B == 0) return PO_OK;
     if (po_spline_lds_bytes(in->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     const po::DevSpline D = make_dev_spline(in);
     po::DevResample R{ds_smaller, ds_larger, h->params.enable_dynamic_segmentation, N, ref_x, ref_y, ref_z, ref_k, ref_s, n_points};
@@ -1692,7 +1619,7 @@ int po_resample_batch_device(po_handle h, const po_spline_in *in, double ds_smal
 int po_limits_batch_device(po_handle h, int B, int N, const int *n_points, const double *v, const double *a, double *max_k, double *max_kp) {
     if (!limits_args_ok(h, B, N, v, a, max_k, max_kp)) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(po_launch_limits(B, N, n_points, v, a, max_k, max_kp, h->params.mu, h->params.max_curvature_rate, h->stream));
     return PO_OK;
@@ -1704,7 +1631,7 @@ int po_dp_search_batch_device(po_handle h, const po_spline_in *in, const double 
     const po_params &p = h->params;
     if (!(p.search_lat_spacing > 0) || !(p.search_long_spacing > 0) || !(p.search_lateral_range > 0) ||
         2 * p.search_lateral_range / p.search_lat_spacing + 1 > 64) return PO_ERR_UNSUPPORTED;  // one wave per path: <= 64 lateral samples
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock g(h->mu);
     if (!h->maps.d || !assignment_covers(h, in->B)) return PO_ERR_INVALID;  // po_set_map first; an assignment covers every instance
     if (in->B == 0) return PO_OK;
     if (po_dp_lds_bytes(in->K, L) > 160 * 1024) return PO_ERR_UNSUPPORTED;
@@ -1738,16 +1665,10 @@ int po_resample_batch(po_handle h, const po_spline_in *in, double ds_smaller, do
     stage_spline_batch(S, in, &sp);
     const Slot<double> x = S.out(ref_x, bn), y = S.out(ref_y, bn), z = S.out(ref_z, bn), k = S.out(ref_k, bn), s = S.out(ref_s, bn);
     const Slot<int> np = S.out(n_points, B);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->plan_io));
-    }
-    const po_spline_in d = sp.dev(in);
-    PO_TRY(po_resample_batch_device(h, &d, ds_smaller, ds_larger, N, x, y, z, k, s, np));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::plan_io, false, [&] {
+        const po_spline_in d = sp.dev(in);
+        return po_resample_batch_device(h, &d, ds_smaller, ds_larger, N, x, y, z, k, s, np);
+    });
 }
 
 int po_limits_batch(po_handle h, int B, int N, const int *n_points, const double *v, const double *a, double *max_k, double *max_kp) {
@@ -1757,15 +1678,7 @@ int po_limits_batch(po_handle h, int B, int N, const int *n_points, const double
     Stage S;
     const Slot<double> d_v = S.in(v, bn), d_a = S.in(a, bn), d_k = S.out(max_k, bn), d_kp = S.out(max_kp, bn);
     const Slot<int> d_np = S.in(n_points, B);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->plan_io));
-    }
-    PO_TRY(po_limits_batch_device(h, B, N, d_np, d_v, d_a, d_k, d_kp));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::plan_io, false, [&] { return po_limits_batch_device(h, B, N, d_np, d_v, d_a, d_k, d_kp); });
 }
 
 int po_dp_search_batch(po_handle h, const po_spline_in *in, const double *start, int L, double *layer_s, double *lb, double *ub, double *l0, int *n_layers) {
@@ -1778,22 +1691,16 @@ int po_dp_search_batch(po_handle h, const po_spline_in *in, const double *start,
     const Slot<double> d_start = S.in(start, 3 * B);
     const Slot<double> d_s = S.out(layer_s, bl), d_lb = S.out(lb, bl), d_ub = S.out(ub, bl), d_l0 = S.out(l0, B);
     const Slot<int> d_n = S.out(n_layers, B);
-    std::lock_guard<std::mutex> call(h->call_mu);  // the call lock: staging, launch and read-back are one atomic unit (po_handle_s)
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        HIP_TRY(hipSetDevice(h->device));
-        PO_TRY(S.upload(h, h->plan_io));
-    }
-    const po_spline_in d = sp.dev(in);
-    PO_TRY(po_dp_search_batch_device(h, &d, d_start, L, d_s, d_lb, d_ub, d_l0, d_n));
-    std::lock_guard<std::mutex> g(h->mu);
-    return S.copy_out(h);
+    return staged_call(h, S, &po_handle_s::plan_io, false, [&] {
+        const po_spline_in d = sp.dev(in);
+        return po_dp_search_batch_device(h, &d, d_start, L, d_s, d_lb, d_ub, d_l0, d_n);
+    });
 }
 
 int po_map_sample_layer(po_handle h, int k, int n, const double *xy, double *dist, int *inside) {
     if (!h || n < 0 || (n > 0 && (!xy || !dist || !inside))) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> call(h->call_mu);  // (post_buf is the staging block of po_postcheck_batch / po_densify_batch too)
-    std::lock_guard<std::mutex> g(h->mu);
+    Lock call(h->call_mu);  // (post_buf is the staging block of po_postcheck_batch / po_densify_batch too)
+    Lock g(h->mu);
     if (!h->maps.d || k < 0 || k >= h->maps.M) return PO_ERR_INVALID;
     if (n == 0) return PO_OK;
     HIP_TRY(hipSetDevice(h->device));

@@ -1,5 +1,6 @@
-// po_handle.hpp — what the two host files of libpo_hip.so (po_capi.cpp, po_plan.cpp) share: error plumbing, the owning buffers, the handle, the staging helper of
-// the host-pointer entries (Stage) and the spline argument check.  Private: not part of include/po_hip.h, and nothing here is exported (hidden visibility).
+// po_handle.hpp — what the two host files of libpo_hip.so (po_capi.cpp, po_plan.cpp) share: error plumbing, the owning buffers, the annotated locks, the handle, the
+// staging helper of the host-pointer entries (Stage), the one staged call they all make and the spline argument check.  Private: not part of include/po_hip.h, and
+// nothing here is exported (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,66 +75,89 @@ struct HostBuf : NoCopy {  // grow-only PINNED host buffer (hipHostMalloc): the 
     ~HostBuf() { release(); }
 };
 
+// The locks, annotated for clang's thread-safety analysis (-Wthread-safety is an error for the host files: an unlocked access to a guarded member does not build).
+#define PO_GUARDED_BY(m) __attribute__((guarded_by(m)))
+#define PO_REQUIRES(m) __attribute__((requires_capability(m)))
+#define PO_ACQUIRED_AFTER(m) __attribute__((acquired_after(m)))
+class __attribute__((capability("mutex"))) Mutex : NoCopy {
+    std::mutex m_;
+
+public:
+    void lock() __attribute__((acquire_capability())) { m_.lock(); }
+    void unlock() __attribute__((release_capability())) { m_.unlock(); }
+};
+class __attribute__((scoped_lockable)) Lock : NoCopy {
+    Mutex &m_;
+
+public:
+    explicit Lock(Mutex &m) __attribute__((acquire_capability(m))) : m_(m) { m_.lock(); }
+    ~Lock() __attribute__((release_capability())) { m_.unlock(); }
+};
+
 struct po_handle_s {
+    // Two locks, always taken in the order call_mu -> mu, and every member says which one guards it:
+    // mu       guards whatever a device-pointer entry reads, writes or grows while it enqueues its launches: the stream, the map stack and the world, the developer
+    //          switches, the read-backs and the timing record, and the scratch blocks of the device entries;
+    // call_mu  is the CALL lock: every host-pointer entry (and po_plan_batch*, whose stages share the plan arena) holds it from before its first ensure() until its
+    //          last read-back has been synchronised, so staging, launch and read-back of one call are atomic with respect to every other call on the handle.  It
+    //          guards the blocks only those entries touch: the staging blocks and the plan arena.
+    // No guard: what po_create sets and nothing changes afterwards (device, params, wave_slots, own_stream, the event handles).
+    Mutex call_mu;
+    Mutex mu PO_ACQUIRED_AFTER(call_mu);
     int device = 0;
     po_params params{};
     // Declared AHEAD of every buffer: members are destroyed in reverse order, so the buffers are freed first, then the events, the stream last
     // (po_destroy has set the device and synchronised the stream before).
     Stream own_stream;
-    hipStream_t stream = nullptr;
+    PO_GUARDED_BY(mu) hipStream_t stream = nullptr;
     Event ev0, ev1;
     Event evh[4];  // host-pointer entry: start, H2D done, (ev0 .. ev1 = the solve), D2H done; evh[3]: solve phase mark (po_last_phase_ms)
     Event evp[2];  // split scheduling (refine = 2): end of the warm-start launches, end of the Newton launch
-    bool timed = false, timed_host = false, timed_phases = false;
-    double host_pack_ms = 0.0, host_unpack_ms = 0.0;
-    HostBuf pin_in, pin_out;   // pinned staging of the host-pointer entry
-    int host_threads = 0;      // pack / unpack threads (0: min(8, hardware threads); po_debug_set "host_threads")
-    DevBuf pol_buf;  // per-lane ADMM state handed from the solve kernels to newton_kernel / polish_kernel (po_params.refine / polish)
-    DevBuf fb_buf;   // refine = 2: the work list of newton_fallback_kernel
-    DevBuf nw_state_buf, nw_idx_buf;  // sliced Newton launches: the parked paths' blocks; keys [B] + list [B + 1]
-    bool nw_slice_forced = false;
-    int nw_last_B = 0;  // ... and the batch size of the last sliced solve (po_debug_get "newton_parked")
+    PO_GUARDED_BY(mu) bool timed = false, timed_host = false, timed_phases = false;
+    PO_GUARDED_BY(mu) double host_pack_ms = 0.0, host_unpack_ms = 0.0;
+    PO_GUARDED_BY(call_mu) HostBuf pin_in, pin_out;   // pinned staging of the host-pointer entry
+    PO_GUARDED_BY(mu) int host_threads = 0;      // pack / unpack threads (0: min(8, hardware threads); po_debug_set "host_threads")
+    PO_GUARDED_BY(mu) DevBuf pol_buf;  // per-lane ADMM state handed from the solve kernels to newton_kernel / polish_kernel (po_params.refine / polish)
+    PO_GUARDED_BY(mu) DevBuf fb_buf;   // refine = 2: the work list of newton_fallback_kernel
+    PO_GUARDED_BY(mu) DevBuf nw_state_buf, nw_idx_buf;  // sliced Newton launches: the parked paths' blocks; keys [B] + list [B + 1]
+    PO_GUARDED_BY(mu) bool nw_slice_forced = false;
+    PO_GUARDED_BY(mu) int nw_last_B = 0;  // ... and the batch size of the last sliced solve (po_debug_get "newton_parked")
     int wave_slots = 1024;  // paths the device runs at a time (one wave per SIMD: 4 per CU); batches below two rounds of that are not sliced (no queueing tail to remove)
-    bool fixed_length = true;  // take the length-specialised kernels where the batch has one (po_debug_set "fixed_length"; 0: always the generic kernels).  Same results.
-    int fixed_used = 0;        // ... and whether the last solve ran them (po_debug_get "fixed_length_used")
-    int dp_waves_used = 0;     // waves per instance of the last DP lattice search: 8 or 1 (0: none yet; po_debug_get "dp_waves_used")
-    int smooth_variant_used = 0;  // instantiation of the last smoothing launch: 100 * kind + 10 * waves per QP + WPE, e.g. 143 = <TENSION, 4, 3> (0: none yet; po_debug_get "smooth_variant_used")
-    int nw_slice = 8;  // steps of the first of the two Newton launches (po_debug_set "newton_slice"; 0: one launch).  Scheduling only.
-    HostBuf fb_host; // ... and the pinned word its count is read back into (refine_chain = 2)
+    PO_GUARDED_BY(mu) bool fixed_length = true;  // take the length-specialised kernels where the batch has one (po_debug_set "fixed_length"; 0: always the generic kernels).  Same results.
+    PO_GUARDED_BY(mu) int fixed_used = 0;        // ... and whether the last solve ran them (po_debug_get "fixed_length_used")
+    PO_GUARDED_BY(mu) int dp_waves_used = 0;     // waves per instance of the last DP lattice search: 8 or 1 (0: none yet; po_debug_get "dp_waves_used")
+    PO_GUARDED_BY(mu) int smooth_variant_used = 0;  // instantiation of the last smoothing launch: 100 * kind + 10 * waves per QP + WPE, e.g. 143 = <TENSION, 4, 3> (0: none yet; po_debug_get "smooth_variant_used")
+    PO_GUARDED_BY(mu) int nw_slice = 8;  // steps of the first of the two Newton launches (po_debug_set "newton_slice"; 0: one launch).  Scheduling only.
+    PO_GUARDED_BY(mu) HostBuf fb_host; // ... and the pinned word its count is read back into (refine_chain = 2)
     // developer switches (po_debug_set; the library reads no environment variable): identity_order (block i solves path i), debug_cycles (per-phase shader
     // clocks of path 0 on stderr; synchronises), smoothing / DP-search A/B switches
-    bool env_identity = false, env_cycles = false, env_smooth_seq = false, env_smooth_nopad = false, env_smooth_debug = false, env_dp_one_wave = false;
-    int env_smooth_waves = 0;
-    DevBuf in_buf, out_buf, asm_buf, scale_buf, dbg_buf, map_buf, post_buf, coef_buf, bnd_buf, smooth_buf, smooth_io, plan_io, plan_arena, plan_host;
-    DevBuf edt_buf, edt_io;  // occupancy -> distance transform: the 16-bit intermediate (2 bytes per cell); staging of the host-pointer entries (image + layers)
-    DevBuf raster_buf;  // obstacle lists -> map stack: the M occupancy images between the rasteriser and the transform (1 byte per cell)
+    PO_GUARDED_BY(mu) bool env_identity = false, env_cycles = false, env_smooth_seq = false, env_smooth_nopad = false, env_smooth_debug = false, env_dp_one_wave = false;
+    PO_GUARDED_BY(mu) int env_smooth_waves = 0;
+    // the staging blocks of the host-pointer entries, the arena of po_plan_batch*; edt_io: staging of the occupancy, obstacle-list and scene entries
+    PO_GUARDED_BY(call_mu) DevBuf in_buf, out_buf, asm_buf, post_buf, bnd_buf, smooth_io, plan_io, plan_arena, plan_host, edt_io;
+    // scratch of the device-pointer entries; edt_buf: occupancy -> distance transform, the 16-bit intermediate (2 bytes per cell)
+    PO_GUARDED_BY(mu) DevBuf scale_buf, dbg_buf, map_buf, coef_buf, smooth_buf, edt_buf;
+    PO_GUARDED_BY(mu) DevBuf raster_buf;  // obstacle lists -> map stack: the M occupancy images between the rasteriser and the transform (1 byte per cell)
     // The map stack: M layers in map_buf, their centres in map_pos_buf when they differ, the instance -> layer table in map_assign_buf.
     // maps is the view the kernels get; maps.d == nullptr until a map is set (maps.M survives a failed re-install: "same M keeps the assignment" is judged against it).
-    DevBuf map_pos_buf, map_assign_buf;
-    po::DevMaps maps{};
-    // Two locks, always taken in the order call_mu -> mu:
-    // mu       guards the handle's fields and grow-only blocks while a device-pointer entry reads them and enqueues its launches;
-    // call_mu  is the CALL lock: every host-pointer entry (and po_plan_batch*, whose stages share the plan arena) holds it from before its first ensure() until its
-    //          last read-back has been synchronised, so staging, launch and read-back of one call are atomic with respect to every other call on the handle.
-    std::mutex mu;
-    std::mutex call_mu;
+    PO_GUARDED_BY(mu) DevBuf map_pos_buf, map_assign_buf;
+    PO_GUARDED_BY(mu) po::DevMaps maps{};
     // The world grid: one static occupancy image of the site in world_buf; world.cells == nullptr until one is set.  The scene entries read it.
-    // (Declared last: no member the solve or the map stages read has moved.)
-    DevBuf world_buf;
-    po_occupancy world{};
-    int world_outside = 0;
-    DevBuf select_buf;  // score and select: the clamped group table [G + 1] and, when the caller wants no cost array, cost [B]
+    PO_GUARDED_BY(mu) DevBuf world_buf;
+    PO_GUARDED_BY(mu) po_occupancy world{};
+    PO_GUARDED_BY(mu) int world_outside = 0;
+    PO_GUARDED_BY(mu) DevBuf select_buf;  // score and select: the clamped group table [G + 1] and, when the caller wants no cost array, cost [B]
 };
 
-// A grow-only block that launches already enqueued on the handle's stream may still read: they are finished before the old block is released.  (h->mu held.)
-inline int grow_after_sync(po_handle h, DevBuf &buf, size_t bytes) {
+// A grow-only block that launches already enqueued on the handle's stream may still read: they are finished before the old block is released.
+inline int grow_after_sync(po_handle h, DevBuf &buf, size_t bytes) PO_REQUIRES(h->mu) {
     if (bytes <= buf.cap) return PO_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return buf.ensure(bytes);
 }
 
-// A batch of B instances on the handle's map stack: with an assignment installed, every instance needs an entry of the table.  (h->mu held.)
-inline bool assignment_covers(const po_handle_s *h, int B) { return !h->maps.layer_of || B <= h->maps.n_assign; }
+// A batch of B instances on the handle's map stack: with an assignment installed, every instance needs an entry of the table.
+inline bool assignment_covers(const po_handle_s *h, int B) PO_REQUIRES(h->mu) { return !h->maps.layer_of || B <= h->maps.n_assign; }
 
 // ---- Stage: the format of one staging block of a host-pointer entry.  The entry DECLARES its arrays, in any order, and gets a slot for each; reserve() sizes the
 // block from those declarations and grows the DevBuf it lives in, copy_in() enqueues one H2D copy per declared input, copy_out() one D2H copy per wanted output and
@@ -142,7 +166,7 @@ inline bool assignment_covers(const po_handle_s *h, int B) { return !h->maps.lay
 //   out(host, n)     n elements the kernel writes, copied to host by copy_out(); host == nullptr: the device array exists all the same, only the copy is skipped
 //                    (an output the kernel must not write at all is simply not declared: a default-constructed Slot is a null pointer)
 //   scratch(n)       n elements that travel in neither direction
-// Copies go from / to the caller's own memory on the handle's stream.  The caller holds the locks the entry's contract asks for.
+// Copies go from / to the caller's own memory on the handle's stream, under mu; the block itself is under the lock its member names.
 class Stage;
 template <typename T> struct Slot {
     const Stage *stage = nullptr;
@@ -168,21 +192,21 @@ public:
     template <typename T> Slot<T> out(T *host, size_t n) { return add<T>(n, nullptr, host); }
     template <typename T> Slot<T> scratch(size_t n) { return add<T>(n, nullptr, nullptr); }
     size_t bytes() const { return bytes_; }
-    int reserve(po_handle h, DevBuf &buf, bool after_sync = false) {
+    int reserve(po_handle h, DevBuf &buf, bool after_sync = false) PO_REQUIRES(h->mu) {
         PO_TRY(after_sync ? grow_after_sync(h, buf, bytes_) : buf.ensure(bytes_));
         base_ = static_cast<char *>(buf.p);
         return PO_OK;
     }
-    int copy_in(po_handle h) const {
+    int copy_in(po_handle h) const PO_REQUIRES(h->mu) {
         for (const Item &it : items_)
             if (it.src) HIP_TRY(hipMemcpyAsync(base_ + it.off, it.src, it.bytes, hipMemcpyHostToDevice, h->stream));
         return PO_OK;
     }
-    int upload(po_handle h, DevBuf &buf, bool after_sync = false) {  // reserve + copy_in: what an entry does under h->mu before it calls its device twin
+    int upload(po_handle h, DevBuf &buf, bool after_sync = false) PO_REQUIRES(h->mu) {  // reserve + copy_in
         PO_TRY(reserve(h, buf, after_sync));
         return copy_in(h);
     }
-    int copy_out(po_handle h) const {
+    int copy_out(po_handle h) const PO_REQUIRES(h->mu) {
         for (const Item &it : items_)
             if (it.dst) HIP_TRY(hipMemcpyAsync(it.dst, base_ + it.off, it.bytes, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -190,6 +214,27 @@ public:
     }
 };
 template <typename T> T *Slot<T>::ptr() const { return stage ? reinterpret_cast<T *>(stage->base_ + stage->items_[item].off) : nullptr; }
+
+// ---- The staged call: what every host-pointer entry does once its arguments are checked and its arrays are declared on S.  The call lock makes staging, launch
+// and read-back one atomic unit; mu is held while the handle's fields are read and the copies are enqueued, and released around the device twin, which takes it
+// itself.  `block` names the staging block S lives in (a member pointer: the block is only touched here, under both locks).  `precheck` runs under mu before
+// anything is staged, for an entry that must refuse on the handle's state with nothing touched.
+struct NoPrecheck {
+    int operator()(po_handle) const { return PO_OK; }
+};
+template <typename Twin, typename Precheck = NoPrecheck>
+int staged_call(po_handle h, Stage &S, DevBuf po_handle_s::*block, bool after_sync, Twin twin, Precheck precheck = Precheck{}) {
+    Lock call(h->call_mu);
+    {
+        Lock g(h->mu);
+        PO_TRY(precheck(h));
+        HIP_TRY(hipSetDevice(h->device));
+        PO_TRY(S.upload(h, h->*block, after_sync));
+    }
+    PO_TRY(twin());
+    Lock g(h->mu);
+    return S.copy_out(h);
+}
 
 // ---- a batch of splines (po_spline_in): one argument check, one DevSpline.  `length` is what ReferencePath attaches to the spline; segmentRawReference and the
 // post-smoothing projection do not read it (need_length = false).

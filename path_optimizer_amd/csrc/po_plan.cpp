@@ -21,6 +21,7 @@ int po_bspline_batch_device(po_handle h, int B, int W, const int *n_way, const d
     if (!h || B < 0 || W < 1 || M < 2 || (B > 0 && (!way_x || !way_y || !x || !y || !s || !n_samples))) return PO_ERR_INVALID;
     if (B == 0) return PO_OK;
     if (sizeof(double) * 2 * (size_t)W > 64 * 1024) return PO_ERR_UNSUPPORTED;
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(po_launch_bspline(B, W, n_way, way_x, way_y, M, x, y, s, n_samples, h->stream));
     return PO_OK;
@@ -31,6 +32,7 @@ int po_segment_raw_batch_device(po_handle h, const po_spline_in *raw, int P, dou
     if (po_spline_lds_bytes(raw->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
     if (raw->B == 0) return PO_OK;
     const po::DevSpline D = make_dev_spline(raw);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(po_launch_segment_raw(&D, P, x, y, s, angle, k, n_points, h->stream));
     return PO_OK;
@@ -42,6 +44,7 @@ int po_post_project_batch_device(po_handle h, const po_spline_in *spline, int L,
     if (po_spline_lds_bytes(spline->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
     if (spline->B == 0) return PO_OK;
     const po::DevSpline D = make_dev_spline(spline);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(po_launch_post_project(&D, L, n_layers, layer_s, offsets, x, y, s, length, h->stream));
     return PO_OK;
@@ -52,6 +55,7 @@ int po_segment_init_batch_device(po_handle h, const po_spline_in *spline, const 
     if (po_spline_lds_bytes(spline->K) > 64 * 1024) return PO_ERR_UNSUPPORTED;
     if (spline->B == 0) return PO_OK;
     const po::DevSpline D = make_dev_spline(spline);
+    Lock g(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(po_launch_segment_init(&D, start, start_stride, goal, goal_stride, h->params.enable_exact_position, init, ok, h->stream));
     return PO_OK;
@@ -75,15 +79,21 @@ static int plan_layer_capacity(int want) {
     return want;
 }
 
-static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_out *out) {
+// The orchestration, under the call lock (the arena).  It cannot hold mu across the stage entries it calls (they take it themselves): what it needs of the handle's
+// guarded state is read in one short section at the top, and its own launches go to that copy of the stream.
+static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_out *out) PO_REQUIRES(h->call_mu) {
     if (!plan_args_ok(h, in, out)) return PO_ERR_INVALID;
     if (!(in->max_length > 0)) return PO_ERR_INVALID;  // the device entry cannot look at the waypoints
-    if (!h->maps.d) return PO_ERR_INVALID;
     const int B = in->B;
-    if (!assignment_covers(h, B)) return PO_ERR_INVALID;  // every instance needs its entry of the map assignment: refused before any stage is enqueued
+    hipStream_t st;
+    {
+        Lock g(h->mu);
+        if (!h->maps.d) return PO_ERR_INVALID;
+        if (!assignment_covers(h, B)) return PO_ERR_INVALID;  // every instance needs its entry of the map assignment: refused before any stage is enqueued
+        st = h->stream;
+    }
     if (B == 0) return PO_OK;
     const po_params *prm = &h->params;
-    hipStream_t st = h->stream;
     HIP_TRY(hipSetDevice(h->device));
     // capacities from the waypoint polyline length: a B-spline is never longer than its control polygon
     const double Lmax = in->max_length;
@@ -117,7 +127,10 @@ static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_o
     Slot<po_info> g_info = Q(nB);
     Slot<double> lim_k = D(bN), lim_kp = D(bN);
     Slot<double> own_states = raw_out ? Slot<double>{} : D(5 * bN);  // QP states before the densifying output branch
-    PO_TRY(A.reserve(h, h->plan_arena));
+    {
+        Lock g(h->mu);
+        PO_TRY(A.reserve(h, h->plan_arena));
+    }
     po_info *info3 = out->info ? out->info : own_info3.ptr();
     int *stage = out->stage ? out->stage : own_stage.ptr();
     double *qp_states = raw_out ? out->states : own_states.ptr();  // optimizePath's two output branches (path_optimizer.cpp:191 / :201)
@@ -223,7 +236,7 @@ static int plan_device_locked(po_handle h, const po_plan_in *in, const po_plan_o
 
 int po_plan_batch_device(po_handle h, const po_plan_in *in, const po_plan_out *out) {
     if (!h) return PO_ERR_INVALID;
-    std::lock_guard<std::mutex> g(h->call_mu);
+    Lock call(h->call_mu);
     return plan_device_locked(h, in, out);
 }
 
@@ -250,12 +263,17 @@ int po_plan_batch(po_handle h, const po_plan_in *in, const po_plan_out *out) {
     const Slot<double> d_states = S.out(out->states, nB * in->N * 5);
     const Slot<int> d_n = S.out(out->n_states, nB), d_ok = S.out(out->ok, nB), d_stage = S.out(out->stage, nB);
     const Slot<po_info> d_info = S.out(out->info, nB);
-    std::lock_guard<std::mutex> g(h->call_mu);
-    PO_TRY(S.upload(h, h->plan_host));
+    // the sequence of staged_call (po_handle.hpp), written out: the twin needs the call lock this function holds, and a callable cannot state that
+    Lock call(h->call_mu);
+    {
+        Lock g(h->mu);
+        PO_TRY(S.upload(h, h->plan_host));
+    }
     po_plan_in din = *in;
     din.way_x = wx; din.way_y = wy; din.start = d_start; din.goal = d_goal; din.n_way = d_nway; din.max_length = Lmax;
     const po_plan_out dout{d_states, d_n, d_ok, d_stage, d_info};
     PO_TRY(plan_device_locked(h, &din, &dout));
+    Lock g(h->mu);
     return S.copy_out(h);
 }
 
