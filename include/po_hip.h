@@ -976,6 +976,93 @@ typedef struct po_stplan_out {
 int po_stplan_batch(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out);         /* host pointers, synchronous */
 int po_stplan_batch_device(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out);  /* device pointers, on the stream, no synchronisation */
 
+/* ---- corridor nudge: carve predicted agents out of the corridor bounds, pass left or right (csrc/po_nudge.hip) ----
+ * po_dynamic_batch* and po_stplan_batch* answer an agent with speed.  This stage answers with steering: per path it takes the corridor po_bounds_batch* wrote
+ * (lb, ub per state and covering circle), finds for every agent of the path's set the lateral interval it occupies at the states the vehicle reaches while the
+ * agent is there, decides per agent whether the vehicle passes LEFT or RIGHT of it, and moves the lower or the upper bound of the touched pairs to the
+ * interval's edge.  out->bounds has the layout of po_batch_in.bounds, so bounds -> nudge -> QP -> speed -> dynamic / stplan stays on one stream.  An agent that
+ * leaves no side to pass on is reported (status 3) and the caller hands it to the speed stages.  The stage reads no map and works on a handle without one.  The
+ * reference has no such stage.
+ *
+ * Definition (the bar is BIT equality).  The conventions are po_dynamic_batch's: every operation is one rounded IEEE double operation in the order written,
+ * nothing contracted; sqrt and / are the correctly rounded ones; a comparison with a NaN is false; min(a, b) = b < a ? b : a; max(a, b) = b > a ? b : a.
+ * margin, t_before, t_after, min_width, skip_states are the fields of po_nudge_params.  n = n_points[b] clamped into [0, N] (N when NULL); x_i, y_i, z_i =
+ * ref_x, ref_y, ref_z[b][i]; t_i = t[b][i]; lb_ij = bounds[b][i][j][0], ub_ij = bounds[b][i][j][1], j = 0 .. 3.  rad = sqrt((car_length / 8) * (car_length / 8) +
+ * (car_width / 2) * (car_width / 2)) + safety_margin of the handle's parameters (the radius po_bounds_batch* derives); d_j = po_params.d[j].
+ *   Not processed: status = 0, ok_out = 0, out->bounds equal to in->bounds in all N rows, side[b][e] = 0 for every e < W, first_blocked_state =
+ *       first_blocked_agent = -1, width_min = DBL_MAX, when ok[b] == 0, or n < 1, or any x, y, z, t or bound of rows < n is non-finite.
+ *   Working corridor: Wl_ij = lb_ij, Wu_ij = ub_ij.
+ *   Frame of pair (i, j), i < n:  cz = pcos(z_i), sz = psin(z_i);  cx = x_i + d_j * cz, cy = y_i + d_j * sz.  A world point (X, Y) has, with dx = X - cx and
+ *       dy = Y - cy, the longitudinal coordinate u = dx * cz + dy * sz and the lateral coordinate l = (-dx) * sz + dy * cz, left positive (bounds_kernel's off).
+ *   Window of state i:  w0_i = t_i - t_before,  w1_i = t_i + t_after.
+ *   The agents of path b are po_dynamic_batch's: k = set_of[b] clamped into [0, S - 1] (0 when NULL), first[k] and first[k + 1] clamped into [0, n_agents],
+ *       ascending; e = a - first[k] (clamped) is the agent's index within the set.  An agent that covers nothing by po_dynamic_batch's rule has side 0 and
+ *       changes nothing.  Otherwise rho = (rad + R) + margin.
+ *   Hull of one agent on one pair: lo = DBL_MAX, hi = -DBL_MAX.  The agent's pieces come in po_dynamic_batch's order with its window formulas, t_i := w0_i and
+ *       t_{i+1} := w1_i (the substitution po_stplan_batch makes): the same ta, tb, wa, wb and positions (ax_a, ay_a), (ax_b, ay_b); a piece is skipped unless
+ *       ta <= tb.  (ua, la) and (ub, lb) are the two positions in the pair's frame.  Every candidate c below is folded in as lo = min(lo, c), hi = max(hi, c),
+ *       in this order:
+ *       end a:  q = rho * rho - ua * ua;  if q >= 0:  w = sqrt(q);  candidates la - w, then la + w.
+ *       end b:  the same with (ub, lb).
+ *       sides:  du = ub - ua, dl = lb - la, L2 = du * du + dl * dl;  only if L2 > 0 and du != 0:  len = sqrt(L2), ox = (rho * dl) / len, oy = (rho * du) / len;
+ *               tp = (ox - ua) / du;  if 0 <= tp and tp <= 1: candidate (la + oy) + tp * dl;   tm = (0 - (ox + ua)) / du;  if 0 <= tm and tm <= 1: candidate
+ *               (la - oy) + tm * dl.
+ *       Per piece this is exactly the lateral interval in which a circle centre of this pair comes within rho of the agent's swept segment; over several
+ *       pieces it is their hull, which is conservative (an agent that turns around a corner also takes the room inside the corner).
+ *   Pair (i, j) is TOUCHED by the agent iff i >= skip_states and lo <= hi and hi > Wl_ij and lo < Wu_ij.
+ *   Decision per agent, over its touched pairs: rl = the minimum of Wu_ij - hi, rr = the minimum of lo - Wl_ij (minima of doubles that are never NaN: see the
+ *       decision below; any order gives the same comparisons), f = the smallest touched i.  Then, in this order:
+ *       no touched pair: side = 0.  Left is passable iff rl >= min_width, right iff rr >= min_width.  sp = side_prev[b][e] when side_prev is given and e < W,
+ *       else 0.  sp == 1 and left passable: side = +1.  Else sp == -1 and right passable: side = -1.  Else both passable: side = +1 if rl >= rr, else -1.
+ *       Else one side passable: that side.  Else side = 2: the corridor stays as it was, and if this is the first blocking agent of the path,
+ *       first_blocked_agent = a (the index into agents[]) and first_blocked_state = f.
+ *       side +1 (the vehicle passes LEFT of the agent): Wl_ij = hi on the touched pairs.  side -1: Wu_ij = lo on the touched pairs.  The next agent sees the
+ *       corridor this one left, so the order of the agents in a set matters.
+ *       Decided while building: a touched pair has a finite Wl and Wu and lo <= hi, but lo or hi may be infinite when the inputs are near DBL_MAX; rl and rr
+ *       are then -inf, never NaN (a NaN candidate never enters lo or hi: its comparison is false), and the comparisons above hold as written.
+ *   side[b][e] is written for e < W, 0 for e at or beyond the size of the set; agents with e >= W are processed and not recorded.
+ *   Results.  out->bounds = the working corridor in rows < n and in->bounds in rows >= n.  width_min = the minimum over rows < n and j of Wu_ij - Wl_ij, folded
+ *       with min from DBL_MAX; a term that is zero counts as +0.0 (decided while building: -0.0 - 0.0 is -0.0, and the minimum must not depend on the order
+ *       of the fold).  status = 3 if any agent blocks, else 2 if some agent carved, else 1.  ok_out = status is 1 or 2.
+ *       Carved rows may have lb > 0 or ub < 0 — the point of the stage; the QP entries take any bounds, and a corridor the QP cannot satisfy comes back from the
+ *       solve as PO_STATUS_PRIMAL_INFEASIBLE.
+ * Return codes, both entries.  PO_ERR_INVALID: a NULL handle, params, struct or required pointer (B > 0: ref_x, ref_y, ref_z, t, both bounds, status, agents;
+ *   inside agents: first, and agents when n_agents > 0); out->bounds == in->bounds; a negative B, N, W, S, n_agents or skip_states; S = 0 with B > 0; side or
+ *   side_prev given with W = 0; a margin that is not finite; a t_before, t_after or min_width that is negative or not finite.  The HOST entry refuses the lists
+ *   po_dynamic_batch refuses; the DEVICE entry reads them clamped, as the definition says, and never reads outside the buffers.  A side_prev value other than
+ *   +1 / -1 is no hint.  B = 0: PO_OK after those checks, nothing launched, nothing written.
+ * `p`, `in->agents` (the struct) are host pointers in both entries; the arrays inside are device pointers for the device entry.  Deterministic: no atomics, no
+ * scratch, and a path's results depend neither on the batch size nor on its position in the batch.
+ * po_default_nudge_params: {0.3, 1.0, 1.0, 0.2, 0} — a starting point nobody has tuned. */
+typedef struct po_nudge_params {
+    double margin;               /* finite: extra clearance around an agent */
+    double t_before, t_after;    /* >= 0, finite: the agent is considered over [t_i - t_before, t_i + t_after] */
+    double min_width;            /* >= 0, finite: a side is passable iff every touched pair keeps this much room */
+    int    skip_states;          /* >= 0: rows i < skip_states are never carved (a QP that pins its start) */
+} po_nudge_params;
+void po_default_nudge_params(po_nudge_params *p);
+typedef struct po_nudge_in {
+    int B, N, W;                 /* paths, rows per path (stride), stride of side / side_prev */
+    const double *ref_x, *ref_y, *ref_z;   /* [B][N] reference states (po_batch_in's) */
+    const int    *n_points;      /* optional [B] (NULL: N); po_bounds_batch's n_valid fits */
+    const int    *ok;            /* optional [B] (NULL: all 1) */
+    const double *t;             /* [B][N]: when the vehicle is expected at reference state i */
+    const double *bounds;        /* [B][N][4][2] (lb, ub) per covering circle: po_bounds_batch's output */
+    const int    *set_of;        /* optional [B], as po_dynamic_in */
+    const po_agent_lists *agents;
+    const int    *side_prev;     /* optional [B][W]: last cycle's side per agent of the set */
+} po_nudge_in;
+typedef struct po_nudge_out {
+    int    *status;              /* [B] 0 not processed, 1 no agent touches the corridor, 2 carved, 3 at least one agent blocks */
+    int    *ok_out;              /* optional [B]: status is 1 or 2 */
+    double *bounds;              /* [B][N][4][2]: the layout of po_batch_in.bounds; must not alias in->bounds */
+    int    *side;                /* optional [B][W]: per agent e of the set 0 untouched, +1 vehicle passes LEFT of it, -1 RIGHT, 2 blocks */
+    int    *first_blocked_state, *first_blocked_agent;  /* optional [B]; -1 when none */
+    double *width_min;           /* optional [B] */
+} po_nudge_out;
+int po_nudge_batch(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out);         /* host pointers, synchronous */
+int po_nudge_batch_device(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -1009,7 +1096,8 @@ const char *po_last_hip_error(void);
  * po_debug_get "world_cells") and the score-and-select entries (po_select_params, po_select_in, po_select_out, po_default_select_params, po_select_batch*) and
  * the speed-profile entries (po_speed_params, po_speed_in, po_speed_out, po_default_speed_params, po_speed_batch*) and the moving-obstacle entries (po_agent, po_agent_lists, po_dynamic_params, po_dynamic_in, po_dynamic_out,
  * po_default_dynamic_params, po_dynamic_batch*) and the station-time entries (po_stplan_params, po_stplan_in, po_stplan_out, po_default_stplan_params,
- * po_stplan_batch*) were added under 7 by the same rule.  A binding should compare
+ * po_stplan_batch*) and the corridor-nudge entries (po_nudge_params, po_nudge_in, po_nudge_out, po_default_nudge_params, po_nudge_batch*) were added under 7 by
+ * the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7
 const char *po_version(void);

@@ -201,3 +201,19 @@ class PoStplanIn(C.Structure):
 class PoStplanOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("ok_out", C.c_void_p), ("n_layers", C.c_void_p), ("cost", C.c_void_p), ("station", C.c_void_p), ("cells", C.c_void_p),
                 ("v_limit", C.c_void_p)]
+
+
+# ---- corridor nudge (po_nudge_batch*) ----
+class PoNudgeParams(C.Structure):
+    _fields_ = [("margin", C.c_double), ("t_before", C.c_double), ("t_after", C.c_double), ("min_width", C.c_double), ("skip_states", C.c_int)]
+
+
+class PoNudgeIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("W", C.c_int), ("ref_x", C.c_void_p), ("ref_y", C.c_void_p), ("ref_z", C.c_void_p), ("n_points", C.c_void_p),
+                ("ok", C.c_void_p), ("t", C.c_void_p), ("bounds", C.c_void_p), ("set_of", C.c_void_p), ("agents", C.POINTER(PoAgentLists)),
+                ("side_prev", C.c_void_p)]
+
+
+class PoNudgeOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("ok_out", C.c_void_p), ("bounds", C.c_void_p), ("side", C.c_void_p), ("first_blocked_state", C.c_void_p),
+                ("first_blocked_agent", C.c_void_p), ("width_min", C.c_void_p)]

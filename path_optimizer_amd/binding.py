@@ -34,7 +34,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_default_select_params", "po_select_batch", "po_select_batch_device",
            "po_default_speed_params", "po_speed_batch", "po_speed_batch_device",
            "po_default_dynamic_params", "po_dynamic_batch", "po_dynamic_batch_device",
-           "po_default_stplan_params", "po_stplan_batch", "po_stplan_batch_device"]
+           "po_default_stplan_params", "po_stplan_batch", "po_stplan_batch_device",
+           "po_default_nudge_params", "po_nudge_batch", "po_nudge_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -113,6 +114,10 @@ def lib():
         L.po_default_stplan_params.restype = None
         L.po_stplan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_stplan_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_default_nudge_params.argtypes = [C.c_void_p]
+        L.po_default_nudge_params.restype = None
+        L.po_nudge_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_nudge_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -165,6 +170,15 @@ def default_stplan_params():
 
     p = PoStplanParams()
     lib().po_default_stplan_params(C.byref(p))
+    return p
+
+
+def default_nudge_params():
+    """po_default_nudge_params: the knobs of po_nudge_batch* (a starting point nobody has tuned)."""
+    from .abi import PoNudgeParams
+
+    p = PoNudgeParams()
+    lib().po_default_nudge_params(C.byref(p))
     return p
 
 
@@ -1008,6 +1022,52 @@ class Engine:
         so = PoStplanOut(*[p(out, k) for k in self.STPLAN_KEYS])
         sp = params if params is not None else default_stplan_params()
         _check(lib().po_stplan_batch_device(self._h, C.byref(sp), C.byref(si), C.byref(so)))
+
+    # ---- corridor nudge: carve predicted agents out of the corridor bounds, pass left or right ----
+    NUDGE_KEYS = ("status", "ok_out", "bounds", "side", "first_blocked_state", "first_blocked_agent", "width_min")
+
+    def nudge_batch(self, ref_x, ref_y, ref_z, t, bounds, agents, n_points=None, ok=None, set_of=None, side_prev=None, W=None, params=None):
+        """Host-pointer entry of po_nudge_batch.  ref_x, ref_y, ref_z, t [B,N], bounds [B,N,4,2] (bounds_batch's), agents: what pack_agents takes; optional
+        n_points [B], ok [B], set_of [B] (None: set 0), side_prev [B,W] (the side of the last call).  W: columns of side (None: side_prev's, else the largest
+        set, at least 1).  Returns a dict: status, ok_out, first_blocked_state, first_blocked_agent [B] i32, bounds [B,N,4,2] (solve_batch's), side [B,W] i32,
+        width_min [B]."""
+        from .abi import PoAgentLists, PoNudgeIn, PoNudgeOut
+
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        rx, ry, rz, tt, bnd = f(ref_x), f(ref_y), f(ref_z), f(t), f(bounds)
+        B, N = rx.shape[0], rx.shape[1]
+        ns, okk, so, sp_ = _i32(n_points), _i32(ok), _i32(set_of), _i32(side_prev)
+        ag, first = pack_agents(agents)
+        if W is None:
+            W = sp_.shape[1] if sp_ is not None else max(1, int(np.diff(first).max()) if len(first) > 1 else 1)
+        lists = PoAgentLists(_np(ag) if len(ag) else None, _np(first), len(ag), len(first) - 1)
+        ni = PoNudgeIn(B, N, W, _np(rx), _np(ry), _np(rz), _np(ns), _np(okk), _np(tt), _np(bnd), _np(so), C.pointer(lists), _np(sp_))
+        i32 = lambda *shape: np.zeros(shape, dtype=np.int32)
+        r = {"status": i32(B), "ok_out": i32(B), "bounds": np.zeros((B, N, 4, 2)), "side": i32(B, W) if W > 0 else None, "first_blocked_state": i32(B),
+             "first_blocked_agent": i32(B), "width_min": np.zeros(B)}
+        no = PoNudgeOut(*[_np(r[k]) for k in self.NUDGE_KEYS])
+        npar = params if params is not None else default_nudge_params()
+        _check(lib().po_nudge_batch(self._h, C.byref(npar), C.byref(ni), C.byref(no)))
+        return r
+
+    def nudge_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: ref_x, ref_y, ref_z, t [B,N] f64, bounds [B,N,4,2] f64, agents (a uint8 tensor over AGENT_DTYPE records, or None when there
+        are none), first [S+1] i32 (+ n_points, ok, set_of i32 [B], side_prev [B,W] i32); out: status [B] i32, bounds [B,N,4,2] f64 (+ any of NUDGE_KEYS: side
+        [B,W] i32).  W is the second dimension of side or side_prev (0 without both).  Enqueued on the handle's stream, no synchronisation."""
+        from .abi import PoAgentLists, PoNudgeIn, PoNudgeOut
+
+        B, N = t["ref_x"].shape[0], t["ref_x"].shape[1]
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        ag = t.get("agents")
+        n_agents = 0 if ag is None else ag.numel() * ag.element_size() // AGENT_DTYPE.itemsize
+        wide = out.get("side") if out.get("side") is not None else t.get("side_prev")
+        W = 0 if wide is None else wide.shape[1]
+        lists = PoAgentLists(p(t, "agents") if n_agents else None, p(t, "first"), n_agents, t["first"].shape[0] - 1)
+        ni = PoNudgeIn(B, N, W, p(t, "ref_x"), p(t, "ref_y"), p(t, "ref_z"), p(t, "n_points"), p(t, "ok"), p(t, "t"), p(t, "bounds"), p(t, "set_of"),
+                       C.pointer(lists), p(t, "side_prev"))
+        no = PoNudgeOut(*[p(out, k) for k in self.NUDGE_KEYS])
+        npar = params if params is not None else default_nudge_params()
+        _check(lib().po_nudge_batch_device(self._h, C.byref(npar), C.byref(ni), C.byref(no)))
 
     def map_sample(self, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)

@@ -1458,6 +1458,71 @@ int po_stplan_batch(po_handle h, const po_stplan_params *p, const po_stplan_in *
     });
 }
 
+// ---- corridor nudge (po_nudge.hip) ---------------------------------------------------------------
+void po_default_nudge_params(po_nudge_params *p) {
+    if (!p) return;
+    *p = po_nudge_params{0.3, 1.0, 1.0, 0.2, 0};  // a starting point nobody has tuned
+}
+
+// What both entries can check without reading through a pointer of the structs (testable without a GPU)
+static bool nudge_args_ok(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0 || in->W < 0 || p->skip_states < 0) return false;
+    auto room = [](double v) { return std::isfinite(v) && v >= 0; };
+    if (!std::isfinite(p->margin) || !room(p->t_before) || !room(p->t_after) || !room(p->min_width)) return false;
+    const po_agent_lists *L = in->agents;
+    if (L && (L->S < 0 || L->n_agents < 0)) return false;
+    if (in->W == 0 && (in->side_prev || out->side)) return false;
+    if (out->bounds && out->bounds == in->bounds) return false;
+    if (in->B == 0) return true;
+    if (!in->ref_x || !in->ref_y || !in->ref_z || !in->t || !in->bounds || !out->bounds || !out->status || !L) return false;
+    return L->S >= 1 && L->first && (L->n_agents == 0 || L->agents);
+}
+
+int po_nudge_batch_device(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out) {
+    if (!nudge_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing to carve: no launch, whatever the handle holds
+    Lock g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    po::DevNudge D{};
+    D.B = in->B; D.N = in->N; D.W = in->W; D.S = in->agents->S; D.n_agents = in->agents->n_agents; D.skip_states = p->skip_states;
+    D.ref_x = in->ref_x; D.ref_y = in->ref_y; D.ref_z = in->ref_z; D.n_points = in->n_points; D.ok = in->ok; D.t = in->t; D.bounds_in = in->bounds;
+    D.set_of = in->set_of; D.agents = in->agents->agents; D.first = in->agents->first; D.side_prev = in->side_prev;
+    const po_params &q = h->params;
+    for (int j = 0; j < 4; ++j) D.d[j] = q.d[j];
+    D.radius = std::sqrt((q.car_length / 8) * (q.car_length / 8) + (q.car_width / 2) * (q.car_width / 2)) + q.safety_margin;  // po_bounds_batch's
+    D.margin = p->margin; D.t_before = p->t_before; D.t_after = p->t_after; D.min_width = p->min_width;
+    D.status = out->status; D.ok_out = out->ok_out; D.bounds = out->bounds; D.side = out->side; D.first_blocked_state = out->first_blocked_state;
+    D.first_blocked_agent = out->first_blocked_agent; D.width_min = out->width_min;
+    HIP_TRY(po_launch_nudge(&D, h->stream));
+    return PO_OK;
+}
+
+int po_nudge_batch(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out) {
+    if (!nudge_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
+    po_dynamic_in as_dynamic{};    // the lists are po_dynamic_batch's and so is what the host entry refuses in them
+    as_dynamic.B = in->B; as_dynamic.set_of = in->set_of; as_dynamic.agents = in->agents;
+    if (!dynamic_lists_ok(&as_dynamic)) return PO_ERR_INVALID;
+    const po_agent_lists *L = in->agents;
+    const size_t B = in->B, bn = B * (size_t)in->N, bw = B * (size_t)in->W;
+    Stage S;
+    const Slot<double> rx = S.in(in->ref_x, bn), ry = S.in(in->ref_y, bn), rz = S.in(in->ref_z, bn), t = S.in(in->t, bn), bin = S.in(in->bounds, 8 * bn);
+    const Slot<int> np = S.in(in->n_points, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B), first = S.in(L->first, (size_t)L->S + 1);
+    const Slot<int> sprev = S.in(in->side_prev, bw);
+    const Slot<po_agent> agents = S.in(L->n_agents > 0 ? L->agents : nullptr, (size_t)L->n_agents);
+    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernel skips it
+    auto opt_i = [&](int *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<int>{}; };
+    const Slot<int> status = S.out(out->status, B), ok_out = opt_i(out->ok_out, B), side = opt_i(out->side, bw);
+    const Slot<int> fs = opt_i(out->first_blocked_state, B), fa = opt_i(out->first_blocked_agent, B);
+    const Slot<double> bounds = S.out(out->bounds, 8 * bn), wmin = out->width_min ? S.out(out->width_min, B) : Slot<double>{};
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+        const po_agent_lists dl{agents, first, L->n_agents, L->S};
+        const po_nudge_in d{in->B, in->N, in->W, rx, ry, rz, np, ok, t, bin, set_of, &dl, sprev};
+        const po_nudge_out o{status, ok_out, bounds, side, fs, fa, wmin};
+        return po_nudge_batch_device(h, p, &d, &o);
+    });
+}
+
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------
 static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bounds, const int *n_valid) {
     if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return false;

@@ -17,7 +17,7 @@ enum { kLaunchSolve, kLaunchNewton, kLaunchFallback, kLaunchPolish };  // what a
 // the groups the shapes are dealt to the objects in (KP's two-level shapes: one lane per chunk / role-split / multi-group / the wide role-split shapes by SPL; the single-level mapping)
 enum { kGrpLane = 1, kGrpSplit = 2, kGrpMulti = 4, kGrpW56 = 8, kGrpW7 = 16, kGrpW8 = 32, kGrpOne = 64 };
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
-struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic; struct DevStplan;
+struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic; struct DevStplan; struct DevNudge;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
 
@@ -125,4 +125,8 @@ hipError_t po_launch_dynamic(const po::DevCar *c, const po::DevDynamic *a, hipSt
 // ---- po_stplan.hip: station-time speed planning (one workgroup per path: blocked cells over the lanes with the agent set through LDS in chunks, then the layered
 // search in LDS; dynamic LDS sized from K, a->Mb and U; device pointers) ----
 hipError_t po_launch_stplan(const po::DevCar *c, const po::DevStplan *a, hipStream_t st);
+
+// ---- po_nudge.hip: corridor nudge (one wave per path, lanes own fixed (state, circle) pairs of the corridor, which lives in the output; the path's agent set through
+// LDS in chunks; device pointers) ----
+hipError_t po_launch_nudge(const po::DevNudge *a, hipStream_t st);
 }  // extern "C"

@@ -141,6 +141,16 @@ struct DevStplan {
     int *status, *ok_out, *n_layers; double *cost; int *station, *cells; double *v_limit;
 };
 
+// corridor-nudge launch arguments (po_nudge.hip): po_nudge_in / po_nudge_out with the lists of po_agent_lists flattened, the fields of
+// po_nudge_params, and d and radius as DevBounds carries them.  bounds_in and bounds never alias.  Every output but status and bounds may be null.
+struct DevNudge {
+    int B, N, W, S, n_agents, skip_states;
+    const double *ref_x, *ref_y, *ref_z; const int *n_points, *ok; const double *t, *bounds_in; const int *set_of;
+    const po_agent *agents; const int *first; const int *side_prev;
+    double d[4], radius, margin, t_before, t_after, min_width;
+    int *status, *ok_out; double *bounds; int *side, *first_blocked_state, *first_blocked_agent; double *width_min;
+};
+
 #ifdef PO_MAP_DEVICE_CODE  // kernels and device functions: po_kernels.hip only (po_capi.cpp needs just the structs)
 // Layer k of the stack as a DevMap.  k is clamped into [0, M - 1] HERE, where it is read: a table that arrived through a device pointer was never validated, and a
 // bad entry must select a wrong layer, never an address outside the stack.
