@@ -1063,6 +1063,89 @@ typedef struct po_nudge_out {
 int po_nudge_batch(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out);         /* host pointers, synchronous */
 int po_nudge_batch_device(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out);  /* device pointers, on the stream, no synchronisation */
 
+/* ---- timed trajectory: sample speed-profiled paths at uniform time steps, emit them as agents (csrc/po_trajectory.hip) ----
+ * Everything the stages above produce is indexed by STATION: states[B][N][5] with v, a and t per state.  What leaves a planner is a trajectory sampled at
+ * uniform TIME steps.  This stage inverts t(s) by po_speed_batch*'s own model (constant acceleration per interval, t_{i+1} = t_i + 2 d_i / (v_i + v_{i+1})),
+ * so every consumer gets the same inversion; a stop, which a profile encodes as repeated times, comes out as a vehicle that stands at the stop state.  The same
+ * samples can be written as po_agent records (up to PO_TRAJ_MAX_DISCS discs along the heading), which po_dynamic_batch_device, po_stplan_batch_device and
+ * po_nudge_batch_device take as they are: vehicle A's plan is vehicle B's agent on the same stream.  out->states has the layout of every states array with
+ * N := K, and with out->t it is a timed path po_dynamic_batch* reads.  The stage reads no map and works on a handle without one.  The reference has no such stage.
+ *
+ * Definition (the bar is BIT equality).  The conventions are po_dynamic_batch's: every operation is one rounded IEEE double operation in the order written,
+ * nothing contracted; / is the correctly rounded one; a comparison with a NaN is false.  pcos and psin are po_pmath.h's.  t0, dt, K, D = n_discs, disc_offset,
+ * disc_radius, P = agent_pts, agent_stride, agent_flags are the fields of po_trajectory_params.  n = n_states[b] clamped into [0, N] (N when NULL); row i =
+ * (x_i, y_i, z_i, k_i, s_i); v_i = v[b][i], t_i = t[b][i].
+ *   Not sampled: status = 0, every entry of the path's output rows (states, v, a, t) 0, every index -1, first_held = -1 and the path's D agent records all zero
+ *       (n_pts = 0: they cover nothing by po_dynamic_batch's rule), when ok[b] == 0, or n < 1, or any x, y, z, k, s, v or t of rows < n is non-finite, or some
+ *       v_i fails v_i >= 0, or t_{i+1} < t_i for some i < n - 1.
+ *   End state E: the smallest i < n - 1 with v_i == 0, v_{i+1} == 0 and s_{i+1} - s_i > 0, and n - 1 when there is none: two states at rest with ground between
+ *       them.  po_speed_batch's clock does not advance across such an interval and a vehicle does not cross it; on a yielded profile E is the stop state.
+ *   Sample k < K:  T = t0 + (double)k * dt.  In this order:
+ *       T >= t_E: HELD.  The sample is row E, with v = v_E, a = 0, index = E.
+ *       Else T < t_0: the sample is row 0, with v = v_0, a = 0, index = 0.
+ *       Else i = the largest index with t_i <= T.  Then i < E and t_{i+1} > T (t is non-decreasing, so the search method cannot change i), and
+ *           Dt = t_{i+1} - t_i > 0;  tau = T - t_i;  acc = (v_{i+1} - v_i) / Dt;  sig = (v_i + (0.5 * acc) * tau) * tau;
+ *           ds = s_{i+1} - s_i;  lam = ds > 0 ? sig / ds : 0, then lam = lam < 0 ? 0 : lam, then lam = lam > 1 ? 1 : lam;
+ *           x = x_i + lam * (x_{i+1} - x_i), the same for y and k, and s = s_i + lam * ds;
+ *           dz = z_{i+1} - z_i;  if dz > PI: dz = dz - TWO_PI, else if dz < -PI: dz = dz + TWO_PI  (the doubles 3.141592653589793 and 6.283185307179586);
+ *           z = z_i + lam * dz, not wrapped again;
+ *           vv = v_i + acc * tau, then v = vv > 0 ? vv : 0;  a = acc;  index = i.
+ *       out->t[b][k] = T for every sample of a sampled path.
+ *   first_held = the smallest k with T_k >= t_E, K when there is none (T_k is non-decreasing in k: a rounded product and a rounded sum are monotone).
+ *   status = 1 when first_held == K: the whole horizon lies inside the path's time span.  Otherwise 2 when v_E == 0 (the vehicle stands there) and 3 when
+ *       v_E > 0: the path ends AT SPEED before the horizon does, and the samples from first_held on repeat the end state — a vehicle that freezes where its plan
+ *       ends, not one that drives on.  A caller that does not want that asks for a shorter horizon or a longer path.
+ *   Agents, D > 0: the record at slot b * D + d, d < D, has n_pts = P, flags = agent_flags, radius = disc_radius[d]; point j < P is sample k = j * agent_stride
+ *       with that sample's x, y, z and T:  t[j] = T,  x[j] = x + disc_offset[d] * pcos(z),  y[j] = y + disc_offset[d] * psin(z);  the points >= P are 0.  All
+ *       208 bytes of every record are written.  covering discs: disc_offset = po_params.d[0 .. 3] and disc_radius = po_nudge_batch's rad cover the vehicle as the
+ *       corridor stages see it (binding.covering_discs).
+ *   Known and stated, not fixed: x and y are chords between states, not arcs.  Within an interval the motion is the constant-acceleration model the profile's t
+ *       implies, not po_speed_batch's clamped a.  Where t0 + k * dt stops increasing in rounding, an agent's t is not strictly increasing; the HOST entry of
+ *       po_dynamic_batch refuses such a list (the device entries skip the segment of zero duration).  Composing agent sets (first[]) from the records is the
+ *       caller's job: a set is a contiguous range of slots.
+ *   Decided while building: disc_offset[d] and disc_radius[d] are checked for d < n_discs only, the entries behind are not read.  agent_pts, agent_stride and
+ *       agent_flags are checked whatever n_discs is, so a struct that is refused with discs is refused without them.  (P - 1) * agent_stride is formed in 64 bits.
+ *       "Aliasing" is an overlap of byte ranges: every output array given, over its full extent ([B][K][5], [B][K], [B], [B * D] records), against every input
+ *       array given over its own; with B = 0 every extent is empty and nothing overlaps.  Two outputs that overlap each other are the caller's own affair.
+ *       T = +inf (k * dt overflows) is held like any T >= t_E; T is never NaN because t0 and dt are finite.
+ * Return codes, both entries.  PO_ERR_INVALID: a NULL handle, params or struct; a negative B or N; t0 not finite; dt not finite or not > 0; K < 1; n_discs outside
+ *   0 .. PO_TRAJ_MAX_DISCS; a disc_offset that is not finite or a disc_radius that is negative or not finite (d < n_discs); agent_pts outside 1 .. PO_AGENT_MAX_PTS;
+ *   agent_stride < 1; (agent_pts - 1) * agent_stride >= K; unknown agent_flags bits; with B > 0 a NULL in->states, in->v, in->t, out->status or out->states, and a
+ *   NULL out->agents when n_discs > 0; an output that aliases an input.  B = 0: PO_OK after those checks, nothing launched, nothing written.
+ * `p` is a host pointer in both entries.  Deterministic: no atomics, no scratch, and a path's results depend neither on the batch size nor on its position in
+ * the batch.
+ * po_default_trajectory_params: {0, 0.1, 50, 0, {0}, {0}, 8, 7, PO_AGENT_HOLD_AFTER} — 5 s at 10 Hz, no agents; eight points span the horizon (7 * 7 = 49 < 50).
+ *   A starting point nobody has tuned. */
+#define PO_TRAJ_MAX_DISCS 4
+typedef struct po_trajectory_params {
+    double t0, dt;               /* sample k is at T_k = t0 + (double)k * dt; t0 finite, dt > 0 and finite */
+    int    K;                    /* >= 1 samples per path */
+    int    n_discs;              /* D in 0 .. PO_TRAJ_MAX_DISCS: agent records written per path (0: none) */
+    double disc_offset[PO_TRAJ_MAX_DISCS];  /* along the heading from the path point; finite */
+    double disc_radius[PO_TRAJ_MAX_DISCS];  /* >= 0, finite */
+    int    agent_pts;            /* P in 1 .. PO_AGENT_MAX_PTS */
+    int    agent_stride;         /* >= 1: agent point j is sample j * agent_stride; (P - 1) * agent_stride < K */
+    int    agent_flags;          /* PO_AGENT_HOLD_* bits only */
+} po_trajectory_params;
+void po_default_trajectory_params(po_trajectory_params *p);
+typedef struct po_trajectory_in {
+    int B, N;                    /* paths, rows per path (stride) */
+    const double *states;        /* [B][N][5] x, y, heading, k, s */
+    const int    *n_states;      /* optional [B] (NULL: N) */
+    const int    *ok;            /* optional [B] (NULL: all 1) */
+    const double *v, *t;         /* [B][N]: po_speed_out.v and po_speed_out.t */
+} po_trajectory_in;
+typedef struct po_trajectory_out {
+    int    *status;              /* [B] 0 not sampled, 1 inside the path's time span, 2 held at rest, 3 held at speed (the path ends before the horizon) */
+    double *states;              /* [B][K][5]: the states layout with N := K */
+    double *v, *a, *t;           /* optional [B][K] */
+    int    *index;               /* optional [B][K]: the state a sample is anchored at (i, E or 0); -1 when not sampled */
+    int    *first_held;          /* optional [B]: K when no sample is held; -1 when not sampled */
+    po_agent *agents;            /* [B * D] when D > 0: path b, disc d -> slot b * D + d */
+} po_trajectory_out;
+int po_trajectory_batch(po_handle h, const po_trajectory_params *p, const po_trajectory_in *in, const po_trajectory_out *out);         /* host pointers, synchronous */
+int po_trajectory_batch_device(po_handle h, const po_trajectory_params *p, const po_trajectory_in *in, const po_trajectory_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -1096,7 +1179,8 @@ const char *po_last_hip_error(void);
  * po_debug_get "world_cells") and the score-and-select entries (po_select_params, po_select_in, po_select_out, po_default_select_params, po_select_batch*) and
  * the speed-profile entries (po_speed_params, po_speed_in, po_speed_out, po_default_speed_params, po_speed_batch*) and the moving-obstacle entries (po_agent, po_agent_lists, po_dynamic_params, po_dynamic_in, po_dynamic_out,
  * po_default_dynamic_params, po_dynamic_batch*) and the station-time entries (po_stplan_params, po_stplan_in, po_stplan_out, po_default_stplan_params,
- * po_stplan_batch*) and the corridor-nudge entries (po_nudge_params, po_nudge_in, po_nudge_out, po_default_nudge_params, po_nudge_batch*) were added under 7 by
+ * po_stplan_batch*) and the corridor-nudge entries (po_nudge_params, po_nudge_in, po_nudge_out, po_default_nudge_params, po_nudge_batch*) and the timed-trajectory
+ * entries (po_trajectory_params, po_trajectory_in, po_trajectory_out, po_default_trajectory_params, po_trajectory_batch*) were added under 7 by
  * the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7

@@ -217,3 +217,21 @@ class PoNudgeIn(C.Structure):
 class PoNudgeOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("ok_out", C.c_void_p), ("bounds", C.c_void_p), ("side", C.c_void_p), ("first_blocked_state", C.c_void_p),
                 ("first_blocked_agent", C.c_void_p), ("width_min", C.c_void_p)]
+
+
+# ---- timed trajectory (po_trajectory_batch*) ----
+PO_TRAJ_MAX_DISCS = 4
+
+
+class PoTrajectoryParams(C.Structure):
+    _fields_ = [("t0", C.c_double), ("dt", C.c_double), ("K", C.c_int), ("n_discs", C.c_int), ("disc_offset", C.c_double * PO_TRAJ_MAX_DISCS),
+                ("disc_radius", C.c_double * PO_TRAJ_MAX_DISCS), ("agent_pts", C.c_int), ("agent_stride", C.c_int), ("agent_flags", C.c_int)]
+
+
+class PoTrajectoryIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("v", C.c_void_p), ("t", C.c_void_p)]
+
+
+class PoTrajectoryOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("states", C.c_void_p), ("v", C.c_void_p), ("a", C.c_void_p), ("t", C.c_void_p), ("index", C.c_void_p),
+                ("first_held", C.c_void_p), ("agents", C.c_void_p)]

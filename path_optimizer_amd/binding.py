@@ -35,7 +35,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_default_speed_params", "po_speed_batch", "po_speed_batch_device",
            "po_default_dynamic_params", "po_dynamic_batch", "po_dynamic_batch_device",
            "po_default_stplan_params", "po_stplan_batch", "po_stplan_batch_device",
-           "po_default_nudge_params", "po_nudge_batch", "po_nudge_batch_device"]
+           "po_default_nudge_params", "po_nudge_batch", "po_nudge_batch_device",
+           "po_default_trajectory_params", "po_trajectory_batch", "po_trajectory_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -118,6 +119,10 @@ def lib():
         L.po_default_nudge_params.restype = None
         L.po_nudge_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_nudge_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_default_trajectory_params.argtypes = [C.c_void_p]
+        L.po_default_trajectory_params.restype = None
+        L.po_trajectory_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_trajectory_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -180,6 +185,23 @@ def default_nudge_params():
     p = PoNudgeParams()
     lib().po_default_nudge_params(C.byref(p))
     return p
+
+
+def default_trajectory_params():
+    """po_default_trajectory_params: horizon, agent discs and agent points of po_trajectory_batch* (a starting point nobody has tuned)."""
+    from .abi import PoTrajectoryParams
+
+    p = PoTrajectoryParams()
+    lib().po_default_trajectory_params(C.byref(p))
+    return p
+
+
+def covering_discs(params):
+    """(offsets [4], radius) of the four covering circles of a parameter struct (PoParams or the oracle's: the same fields): the offsets po_params.d[j] along the
+    heading and the radius po_bounds_batch* and po_nudge_batch* derive, sqrt((car_length / 8)^2 + (car_width / 2)^2) + safety_margin, in that order of
+    operations.  What po_trajectory_params.disc_offset / disc_radius take to emit a vehicle as the corridor stages see it."""
+    rad = np.sqrt(np.float64(params.car_length / 8) * np.float64(params.car_length / 8) + np.float64(params.car_width / 2) * np.float64(params.car_width / 2))
+    return [float(params.d[j]) for j in range(4)], float(rad + np.float64(params.safety_margin))
 
 
 def problem_dims(form: int, N: int, keep: int):
@@ -1068,6 +1090,43 @@ class Engine:
         no = PoNudgeOut(*[p(out, k) for k in self.NUDGE_KEYS])
         npar = params if params is not None else default_nudge_params()
         _check(lib().po_nudge_batch_device(self._h, C.byref(npar), C.byref(ni), C.byref(no)))
+
+    # ---- timed trajectory: speed-profiled paths sampled at uniform time steps, and as agents ----
+    TRAJECTORY_KEYS = ("status", "states", "v", "a", "t", "index", "first_held", "agents")
+
+    def trajectory_batch(self, states, v, t, n_states=None, ok=None, params=None):
+        """Host-pointer entry of po_trajectory_batch.  states [B,N,5], v, t [B,N] (speed_batch's); optional n_states [B], ok [B].  Returns a dict: status,
+        first_held [B] i32, states [B,K,5], v, a, t [B,K], index [B,K] i32 and agents [B * n_discs] of AGENT_DTYPE (None with n_discs = 0): path b, disc d at
+        b * n_discs + d, what pack_agents passes through as (agents, first)."""
+        from .abi import PoTrajectoryIn, PoTrajectoryOut
+
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        B, N = states.shape[0], states.shape[1]
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        vv, tt = f(v), f(t)
+        ns, okk = _i32(n_states), _i32(ok)
+        tp = params if params is not None else default_trajectory_params()
+        K, D = max(int(tp.K), 0), max(int(tp.n_discs), 0)
+        ti = PoTrajectoryIn(B, N, _np(states), _np(ns), _np(okk), _np(vv), _np(tt))
+        i32 = lambda *shape: np.zeros(shape, dtype=np.int32)
+        r = {"status": i32(B), "states": np.zeros((B, K, 5)), "v": np.zeros((B, K)), "a": np.zeros((B, K)), "t": np.zeros((B, K)), "index": i32(B, K),
+             "first_held": i32(B), "agents": np.zeros(B * D, dtype=AGENT_DTYPE) if D > 0 else None}
+        to = PoTrajectoryOut(*[_np(r[k]) for k in self.TRAJECTORY_KEYS])
+        _check(lib().po_trajectory_batch(self._h, C.byref(tp), C.byref(ti), C.byref(to)))
+        return r
+
+    def trajectory_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: states [B,N,5], v, t [B,N] f64 (+ n_states, ok i32 [B]); out: status [B] i32, states [B,K,5] f64 (+ any of TRAJECTORY_KEYS:
+        v, a, t [B,K] f64, index [B,K] i32, first_held [B] i32, agents: a uint8 tensor over B * n_discs AGENT_DTYPE records, which dynamic_batch_device,
+        stplan_batch_device and nudge_batch_device take as their agents).  Enqueued on the handle's stream, no synchronisation."""
+        from .abi import PoTrajectoryIn, PoTrajectoryOut
+
+        B, N = t["states"].shape[0], t["states"].shape[1]
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        ti = PoTrajectoryIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "v"), p(t, "t"))
+        to = PoTrajectoryOut(*[p(out, k) for k in self.TRAJECTORY_KEYS])
+        tp = params if params is not None else default_trajectory_params()
+        _check(lib().po_trajectory_batch_device(self._h, C.byref(tp), C.byref(ti), C.byref(to)))
 
     def map_sample(self, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)

@@ -1523,6 +1523,74 @@ int po_nudge_batch(po_handle h, const po_nudge_params *p, const po_nudge_in *in,
     });
 }
 
+// ---- timed trajectory (po_trajectory.hip) --------------------------------------------------------
+void po_default_trajectory_params(po_trajectory_params *p) {
+    if (!p) return;
+    *p = po_trajectory_params{0.0, 0.1, 50, 0, {0, 0, 0, 0}, {0, 0, 0, 0}, 8, 7, PO_AGENT_HOLD_AFTER};  // a starting point nobody has tuned
+}
+
+// What both entries can check without reading through a pointer of the structs (testable without a GPU)
+static bool trajectory_args_ok(po_handle h, const po_trajectory_params *p, const po_trajectory_in *in, const po_trajectory_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0) return false;
+    if (!std::isfinite(p->t0) || !std::isfinite(p->dt) || !(p->dt > 0) || p->K < 1 || p->n_discs < 0 || p->n_discs > PO_TRAJ_MAX_DISCS) return false;
+    for (int d = 0; d < p->n_discs; ++d)
+        if (!std::isfinite(p->disc_offset[d]) || !std::isfinite(p->disc_radius[d]) || p->disc_radius[d] < 0) return false;
+    if (p->agent_pts < 1 || p->agent_pts > PO_AGENT_MAX_PTS || p->agent_stride < 1 || (long long)(p->agent_pts - 1) * p->agent_stride >= p->K) return false;
+    if (p->agent_flags & ~(PO_AGENT_HOLD_BEFORE | PO_AGENT_HOLD_AFTER)) return false;
+    const size_t B = in->B, bn = B * (size_t)in->N, bk = B * (size_t)p->K;
+    if (B > 0 && (!in->states || !in->v || !in->t || !out->status || !out->states || (p->n_discs > 0 && !out->agents))) return false;
+    // no output may overlap an input: byte ranges over the full extent of each array (B = 0: every extent is empty)
+    struct Range { const void *p; size_t bytes; };
+    const Range ins[] = {{in->states, 5 * bn * sizeof(double)}, {in->n_states, B * sizeof(int)}, {in->ok, B * sizeof(int)}, {in->v, bn * sizeof(double)},
+                         {in->t, bn * sizeof(double)}};
+    const Range outs[] = {{out->status, B * sizeof(int)}, {out->states, 5 * bk * sizeof(double)}, {out->v, bk * sizeof(double)}, {out->a, bk * sizeof(double)},
+                          {out->t, bk * sizeof(double)}, {out->index, bk * sizeof(int)}, {out->first_held, B * sizeof(int)},
+                          {out->agents, B * (size_t)p->n_discs * sizeof(po_agent)}};
+    for (const Range &o : outs)
+        for (const Range &i : ins) {
+            if (!o.p || !i.p || !o.bytes || !i.bytes) continue;
+            const uintptr_t ob = (uintptr_t)o.p, ib = (uintptr_t)i.p;
+            if (ob < ib + i.bytes && ib < ob + o.bytes) return false;
+        }
+    return true;
+}
+
+int po_trajectory_batch_device(po_handle h, const po_trajectory_params *p, const po_trajectory_in *in, const po_trajectory_out *out) {
+    if (!trajectory_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing to sample: no launch, whatever the handle holds
+    Lock g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    po::DevTrajectory D{};
+    D.B = in->B; D.N = in->N; D.K = p->K; D.D = p->n_discs; D.P = p->agent_pts; D.stride = p->agent_stride; D.flags = p->agent_flags;
+    D.states = in->states; D.n_states = in->n_states; D.ok = in->ok; D.v = in->v; D.t = in->t;
+    D.t0 = p->t0; D.dt = p->dt;
+    for (int d = 0; d < p->n_discs; ++d) { D.off[d] = p->disc_offset[d]; D.rad[d] = p->disc_radius[d]; }
+    D.status = out->status; D.o_states = out->states; D.o_v = out->v; D.o_a = out->a; D.o_t = out->t; D.index = out->index; D.first_held = out->first_held;
+    D.agents = p->n_discs > 0 ? out->agents : nullptr;
+    HIP_TRY(po_launch_trajectory(&D, h->stream));
+    return PO_OK;
+}
+
+int po_trajectory_batch(po_handle h, const po_trajectory_params *p, const po_trajectory_in *in, const po_trajectory_out *out) {
+    if (!trajectory_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
+    const size_t B = in->B, bn = B * (size_t)in->N, bk = B * (size_t)p->K;
+    Stage S;
+    const Slot<double> states = S.in(in->states, 5 * bn), v = S.in(in->v, bn), t = S.in(in->t, bn);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B);
+    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernel skips it
+    auto opt_i = [&](int *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<int>{}; };
+    auto opt_d = [&](double *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<double>{}; };
+    const Slot<int> status = S.out(out->status, B), index = opt_i(out->index, bk), fh = opt_i(out->first_held, B);
+    const Slot<double> os = S.out(out->states, 5 * bk), ov = opt_d(out->v, bk), oa = opt_d(out->a, bk), ot = opt_d(out->t, bk);
+    const Slot<po_agent> agents = p->n_discs > 0 ? S.out(out->agents, B * (size_t)p->n_discs) : Slot<po_agent>{};
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+        const po_trajectory_in d{in->B, in->N, states, ns, ok, v, t};
+        const po_trajectory_out o{status, os, ov, oa, ot, index, fh, agents};
+        return po_trajectory_batch_device(h, p, &d, &o);
+    });
+}
+
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------
 static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bounds, const int *n_valid) {
     if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return false;

@@ -18,6 +18,7 @@ enum { kLaunchSolve, kLaunchNewton, kLaunchFallback, kLaunchPolish };  // what a
 enum { kGrpLane = 1, kGrpSplit = 2, kGrpMulti = 4, kGrpW56 = 8, kGrpW7 = 16, kGrpW8 = 32, kGrpOne = 64 };
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
 struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic; struct DevStplan; struct DevNudge;
+struct DevTrajectory;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
 
@@ -129,4 +130,8 @@ hipError_t po_launch_stplan(const po::DevCar *c, const po::DevStplan *a, hipStre
 // ---- po_nudge.hip: corridor nudge (one wave per path, lanes own fixed (state, circle) pairs of the corridor, which lives in the output; the path's agent set through
 // LDS in chunks; device pointers) ----
 hipError_t po_launch_nudge(const po::DevNudge *a, hipStream_t st);
+
+// ---- po_trajectory.hip: timed trajectory (one wave per path: a validity sweep over the rows, then lanes over the samples, each with a binary search on the path's
+// t row; the agent records by the first lanes; no LDS; device pointers) ----
+hipError_t po_launch_trajectory(const po::DevTrajectory *a, hipStream_t st);
 }  // extern "C"

@@ -151,6 +151,15 @@ struct DevNudge {
     int *status, *ok_out; double *bounds; int *side, *first_blocked_state, *first_blocked_agent; double *width_min;
 };
 
+// timed-trajectory launch arguments (po_trajectory.hip): po_trajectory_in / po_trajectory_out and the fields of po_trajectory_params
+// (D = n_discs, P = agent_pts).  Every output but status and o_states may be null; agents is null exactly when D == 0.
+struct DevTrajectory {
+    int B, N, K, D, P, stride, flags;
+    const double *states; const int *n_states, *ok; const double *v, *t;
+    double t0, dt, off[PO_TRAJ_MAX_DISCS], rad[PO_TRAJ_MAX_DISCS];
+    int *status; double *o_states, *o_v, *o_a, *o_t; int *index, *first_held; po_agent *agents;
+};
+
 #ifdef PO_MAP_DEVICE_CODE  // kernels and device functions: po_kernels.hip only (po_capi.cpp needs just the structs)
 // Layer k of the stack as a DevMap.  k is clamped into [0, M - 1] HERE, where it is read: a table that arrived through a device pointer was never validated, and a
 // bad entry must select a wrong layer, never an address outside the stack.
