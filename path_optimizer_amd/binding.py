@@ -306,6 +306,25 @@ def pack_agents(sets):
     return agents, first
 
 
+def _agent_lists(agents):
+    """agents (what pack_agents takes) -> (the PoAgentLists of a host-pointer entry, agents, first).  The struct stores bare addresses: the CALLER holds the two
+    packed arrays in locals until its C call has returned, as for _i32."""
+    from .abi import PoAgentLists
+
+    ag, first = pack_agents(agents)
+    return PoAgentLists(_np(ag) if len(ag) else None, _np(first), len(ag), len(first) - 1), ag, first
+
+
+def _agent_lists_device(t):
+    """t["agents"] (a uint8 tensor over AGENT_DTYPE records, or None when there are none) and t["first"] [S + 1] i32 -> the PoAgentLists of a device-pointer entry
+    (the caller's dict holds the tensors)."""
+    from .abi import PoAgentLists
+
+    ag = t.get("agents")
+    n_agents = 0 if ag is None else ag.numel() * ag.element_size() // AGENT_DTYPE.itemsize
+    return PoAgentLists(C.c_void_p(ag.data_ptr()) if n_agents else None, C.c_void_p(t["first"].data_ptr()), n_agents, t["first"].shape[0] - 1)
+
+
 def pack_rings(shared, layers=None):
     """Rings -> the arrays of po_rings: (verts [n_verts, 2] float64, start [n_rings + 1] int32, flags [n_rings] int32, n_shared, first [M + 1] int32 or None).
     shared: a list of (xy array [n, 2], flag) every layer owns; layers: None, or M lists of (xy, flag), the rings of each layer alone.  flag is abi.PO_RING_SOLID or
@@ -971,15 +990,14 @@ class Engine:
         """Host-pointer entry of po_dynamic_batch.  states [B,N,5], t [B,N] (speed_batch's t), agents: what pack_agents takes; optional n_states [B], ok [B],
         set_of [B] (None: set 0), v_limit_in [B,N].  Returns a dict: status, ok_out, first_state, first_agent, stop_state [B] i32, gap_min, first_time [B], gap and
         v_limit [B,N] (None without want_rows)."""
-        from .abi import PoAgentLists, PoDynamicIn, PoDynamicOut
+        from .abi import PoDynamicIn, PoDynamicOut
 
         states = np.ascontiguousarray(states, dtype=np.float64)
         B, N = states.shape[0], states.shape[1]
         f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
         tt, vin = f(t), f(v_limit_in)
         ns, okk, so = _i32(n_states), _i32(ok), _i32(set_of)
-        ag, first = pack_agents(agents)
-        lists = PoAgentLists(_np(ag) if len(ag) else None, _np(first), len(ag), len(first) - 1)
+        lists, ag, first = _agent_lists(agents)
         di = PoDynamicIn(B, N, _np(states), _np(ns), _np(okk), _np(tt), _np(so), C.pointer(lists), _np(vin))
         i32 = lambda: np.zeros(B, dtype=np.int32)
         r = {"status": i32(), "ok_out": i32(), "gap_min": np.zeros(B), "first_state": i32(), "first_agent": i32(), "stop_state": i32(), "first_time": np.zeros(B),
@@ -992,13 +1010,11 @@ class Engine:
     def dynamic_batch_device(self, t: dict, out: dict, params=None):
         """Device-pointer entry: t: states [B,N,5] f64, t [B,N] f64, agents (a uint8 tensor over AGENT_DTYPE records, or None when there are none), first [S+1] i32
         (+ n_states, ok, set_of i32 [B], v_limit_in [B,N]); out: status [B] i32 (+ any of DYNAMIC_KEYS).  Enqueued on the handle's stream, no synchronisation."""
-        from .abi import PoAgentLists, PoDynamicIn, PoDynamicOut
+        from .abi import PoDynamicIn, PoDynamicOut
 
         B, N = t["states"].shape[0], t["states"].shape[1]
         p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
-        ag = t.get("agents")
-        n_agents = 0 if ag is None else ag.numel() * ag.element_size() // AGENT_DTYPE.itemsize
-        lists = PoAgentLists(p(t, "agents") if n_agents else None, p(t, "first"), n_agents, t["first"].shape[0] - 1)
+        lists = _agent_lists_device(t)
         di = PoDynamicIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "t"), p(t, "set_of"), C.pointer(lists), p(t, "v_limit_in"))
         do = PoDynamicOut(*[p(out, k) for k in self.DYNAMIC_KEYS])
         dp = params if params is not None else default_dynamic_params()
@@ -1011,15 +1027,14 @@ class Engine:
         """Host-pointer entry of po_stplan_batch.  states [B,N,5], v0 [B], agents: what pack_agents takes; optional n_states [B], ok [B], v_cap [B,N], set_of [B]
         (None: set 0), v_limit_in [B,N].  Returns a dict: status, ok_out, n_layers [B] i32, cost [B], station [B,17] i32, cells [B,K,128] i32 and v_limit [B,N]
         (the last two None without want_rows)."""
-        from .abi import PO_ST_MAX_LAYERS, PO_ST_MAX_STATIONS, PoAgentLists, PoStplanIn, PoStplanOut
+        from .abi import PO_ST_MAX_LAYERS, PO_ST_MAX_STATIONS, PoStplanIn, PoStplanOut
 
         states = np.ascontiguousarray(states, dtype=np.float64)
         B, N = states.shape[0], states.shape[1]
         f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
         vv, cap, vin = f(v0), f(v_cap), f(v_limit_in)
         ns, okk, so = _i32(n_states), _i32(ok), _i32(set_of)
-        ag, first = pack_agents(agents)
-        lists = PoAgentLists(_np(ag) if len(ag) else None, _np(first), len(ag), len(first) - 1)
+        lists, ag, first = _agent_lists(agents)
         si = PoStplanIn(B, N, _np(states), _np(ns), _np(okk), _np(vv), _np(cap), _np(so), C.pointer(lists), _np(vin))
         sp = params if params is not None else default_stplan_params()
         i32 = lambda *shape: np.zeros(shape, dtype=np.int32)
@@ -1033,13 +1048,11 @@ class Engine:
         """Device-pointer entry: t: states [B,N,5] f64, v0 [B] f64, agents (a uint8 tensor over AGENT_DTYPE records, or None when there are none), first [S+1] i32
         (+ n_states, ok, set_of i32 [B], v_cap, v_limit_in [B,N]); out: status [B] i32 (+ any of STPLAN_KEYS: station [B,17] i32, cells [B,K,128] i32).  Enqueued on
         the handle's stream, no synchronisation."""
-        from .abi import PoAgentLists, PoStplanIn, PoStplanOut
+        from .abi import PoStplanIn, PoStplanOut
 
         B, N = t["states"].shape[0], t["states"].shape[1]
         p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
-        ag = t.get("agents")
-        n_agents = 0 if ag is None else ag.numel() * ag.element_size() // AGENT_DTYPE.itemsize
-        lists = PoAgentLists(p(t, "agents") if n_agents else None, p(t, "first"), n_agents, t["first"].shape[0] - 1)
+        lists = _agent_lists_device(t)
         si = PoStplanIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "v0"), p(t, "v_cap"), p(t, "set_of"), C.pointer(lists), p(t, "v_limit_in"))
         so = PoStplanOut(*[p(out, k) for k in self.STPLAN_KEYS])
         sp = params if params is not None else default_stplan_params()
@@ -1053,16 +1066,15 @@ class Engine:
         n_points [B], ok [B], set_of [B] (None: set 0), side_prev [B,W] (the side of the last call).  W: columns of side (None: side_prev's, else the largest
         set, at least 1).  Returns a dict: status, ok_out, first_blocked_state, first_blocked_agent [B] i32, bounds [B,N,4,2] (solve_batch's), side [B,W] i32,
         width_min [B]."""
-        from .abi import PoAgentLists, PoNudgeIn, PoNudgeOut
+        from .abi import PoNudgeIn, PoNudgeOut
 
         f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
         rx, ry, rz, tt, bnd = f(ref_x), f(ref_y), f(ref_z), f(t), f(bounds)
         B, N = rx.shape[0], rx.shape[1]
         ns, okk, so, sp_ = _i32(n_points), _i32(ok), _i32(set_of), _i32(side_prev)
-        ag, first = pack_agents(agents)
+        lists, ag, first = _agent_lists(agents)
         if W is None:
             W = sp_.shape[1] if sp_ is not None else max(1, int(np.diff(first).max()) if len(first) > 1 else 1)
-        lists = PoAgentLists(_np(ag) if len(ag) else None, _np(first), len(ag), len(first) - 1)
         ni = PoNudgeIn(B, N, W, _np(rx), _np(ry), _np(rz), _np(ns), _np(okk), _np(tt), _np(bnd), _np(so), C.pointer(lists), _np(sp_))
         i32 = lambda *shape: np.zeros(shape, dtype=np.int32)
         r = {"status": i32(B), "ok_out": i32(B), "bounds": np.zeros((B, N, 4, 2)), "side": i32(B, W) if W > 0 else None, "first_blocked_state": i32(B),
@@ -1076,15 +1088,13 @@ class Engine:
         """Device-pointer entry: t: ref_x, ref_y, ref_z, t [B,N] f64, bounds [B,N,4,2] f64, agents (a uint8 tensor over AGENT_DTYPE records, or None when there
         are none), first [S+1] i32 (+ n_points, ok, set_of i32 [B], side_prev [B,W] i32); out: status [B] i32, bounds [B,N,4,2] f64 (+ any of NUDGE_KEYS: side
         [B,W] i32).  W is the second dimension of side or side_prev (0 without both).  Enqueued on the handle's stream, no synchronisation."""
-        from .abi import PoAgentLists, PoNudgeIn, PoNudgeOut
+        from .abi import PoNudgeIn, PoNudgeOut
 
         B, N = t["ref_x"].shape[0], t["ref_x"].shape[1]
         p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
-        ag = t.get("agents")
-        n_agents = 0 if ag is None else ag.numel() * ag.element_size() // AGENT_DTYPE.itemsize
         wide = out.get("side") if out.get("side") is not None else t.get("side_prev")
         W = 0 if wide is None else wide.shape[1]
-        lists = PoAgentLists(p(t, "agents") if n_agents else None, p(t, "first"), n_agents, t["first"].shape[0] - 1)
+        lists = _agent_lists_device(t)
         ni = PoNudgeIn(B, N, W, p(t, "ref_x"), p(t, "ref_y"), p(t, "ref_z"), p(t, "n_points"), p(t, "ok"), p(t, "t"), p(t, "bounds"), p(t, "set_of"),
                        C.pointer(lists), p(t, "side_prev"))
         no = PoNudgeOut(*[p(out, k) for k in self.NUDGE_KEYS])

@@ -1248,10 +1248,9 @@ int po_select_batch(po_handle h, const po_select_params *p, const po_select_in *
     if (!empty) {
         const Slot<double> states = S.in(in->states, 5 * B * N), goal = S.in(in->goal, B * (size_t)in->goal_stride), prev = S.in(Np ? in->prev_states : nullptr, 5 * G * Np);
         const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), gs = S.in(in->group_start, G + 1), pn = S.in(Np ? in->prev_n : nullptr, G);
-        // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernels skip it
-        const Slot<double> feat = out->feat ? S.out(out->feat, PO_N_FEAT * B) : Slot<double>{}, cost = out->cost ? S.out(out->cost, B) : Slot<double>{};
-        const Slot<double> bc = out->best_cost ? S.out(out->best_cost, G) : Slot<double>{}, ss = out->sel_states ? S.out(out->sel_states, 5 * G * N) : Slot<double>{};
-        const Slot<int> best = S.out(out->best, G), nf = out->n_feasible ? S.out(out->n_feasible, G) : Slot<int>{}, sn = out->sel_n ? S.out(out->sel_n, G) : Slot<int>{};
+        const Slot<double> feat = S.out_opt(out->feat, PO_N_FEAT * B), cost = S.out_opt(out->cost, B);
+        const Slot<double> bc = S.out_opt(out->best_cost, G), ss = S.out_opt(out->sel_states, 5 * G * N);
+        const Slot<int> best = S.out(out->best, G), nf = S.out_opt(out->n_feasible, G), sn = S.out_opt(out->sel_n, G);
         return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
             d.states = states; d.goal = goal; d.prev_states = prev; d.n_states = ns; d.ok = ok; d.group_start = gs; d.prev_n = pn;
             d.Np = (int)Np;
@@ -1303,9 +1302,7 @@ int po_speed_batch(po_handle h, const po_speed_params *p, const po_speed_in *in,
     Stage S;
     const Slot<double> states = S.in(in->states, 5 * bn), v0 = S.in(in->v0, B), ve = S.in(in->v_end, B), vl = S.in(in->v_limit, bn);
     const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B);
-    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernels skip it
-    const Slot<double> v = S.out(out->v, bn), a = S.out(out->a, bn), t = out->t ? S.out(out->t, bn) : Slot<double>{};
-    const Slot<double> tt = out->total_time ? S.out(out->total_time, B) : Slot<double>{};
+    const Slot<double> v = S.out(out->v, bn), a = S.out(out->a, bn), t = S.out_opt(out->t, bn), tt = S.out_opt(out->total_time, B);
     const Slot<int> status = S.out(out->status, B);
     return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
         const po_speed_in d{in->B, in->N, states, ns, ok, v0, ve, vl};
@@ -1320,26 +1317,22 @@ void po_default_dynamic_params(po_dynamic_params *p) {
     *p = po_dynamic_params{0.3, 5.0};  // a starting point nobody has tuned
 }
 
-// What both entries can check without reading through a pointer of the structs (testable without a GPU)
-static bool dynamic_args_ok(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out) {
-    if (!h || !p || !in || !out || in->B < 0 || in->N < 0) return false;
-    if (!std::isfinite(p->margin) || !std::isfinite(p->stop_distance) || p->stop_distance < 0) return false;
-    const po_agent_lists *L = in->agents;
+// ---- agent lists (po_agent_lists): what the entries of the stages that read agents share ----------------------------------------------
+// What both entries can check without reading through a pointer of the lists; a batch of B > 0 needs lists
+static bool agent_lists_shape_ok(const po_agent_lists *L, int B) {
     if (L && (L->S < 0 || L->n_agents < 0)) return false;
-    if (in->B == 0) return true;
-    if (!in->states || !in->t || !out->status || !L) return false;
-    return L->S >= 1 && L->first && (L->n_agents == 0 || L->agents);
+    if (B == 0) return true;
+    return L && L->S >= 1 && L->first && (L->n_agents == 0 || L->agents);
 }
-// The host entry reads the lists themselves: everything the device entry can only clamp is refused here, before the handle is touched
-static bool dynamic_lists_ok(const po_dynamic_in *in) {
-    const po_agent_lists *L = in->agents;
+// The host entries read the lists themselves: everything the device entries can only clamp is refused here, before the handle is touched
+static bool agent_lists_host_ok(const po_agent_lists *L, const int *set_of, int B) {
     if (L->first[0] != 0) return false;
     for (int k = 0; k < L->S; ++k)
         if (L->first[k + 1] < L->first[k]) return false;
     if (L->first[L->S] > L->n_agents) return false;
-    if (in->set_of)
-        for (int b = 0; b < in->B; ++b)
-            if (in->set_of[b] < 0 || in->set_of[b] >= L->S) return false;
+    if (set_of)
+        for (int b = 0; b < B; ++b)
+            if (set_of[b] < 0 || set_of[b] >= L->S) return false;
     for (int i = 0; i < L->n_agents; ++i) {
         const po_agent &g = L->agents[i];
         if (g.n_pts < 1 || g.n_pts > PO_AGENT_MAX_PTS || (g.flags & ~(PO_AGENT_HOLD_BEFORE | PO_AGENT_HOLD_AFTER))) return false;
@@ -1350,6 +1343,23 @@ static bool dynamic_lists_ok(const po_dynamic_in *in) {
         }
     }
     return true;
+}
+struct StagedAgents {
+    Slot<po_agent> agents;
+    Slot<int> first;
+    po_agent_lists dev(const po_agent_lists *L) const { return po_agent_lists{agents, first, L->n_agents, L->S}; }  // (after the block is reserved)
+};
+static void stage_agent_lists(Stage &S, const po_agent_lists *L, StagedAgents *q) {  // declares the arrays of a po_agent_lists on S
+    q->first = S.in(L->first, (size_t)L->S + 1);
+    q->agents = S.in(L->n_agents > 0 ? L->agents : nullptr, (size_t)L->n_agents);
+}
+
+// What both entries can check without reading through a pointer of the structs (testable without a GPU)
+static bool dynamic_args_ok(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0) return false;
+    if (!std::isfinite(p->margin) || !std::isfinite(p->stop_distance) || p->stop_distance < 0) return false;
+    if (!agent_lists_shape_ok(in->agents, in->B)) return false;
+    return in->B == 0 || (in->states && in->t && out->status);
 }
 
 int po_dynamic_batch_device(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out) {
@@ -1372,20 +1382,18 @@ int po_dynamic_batch_device(po_handle h, const po_dynamic_params *p, const po_dy
 int po_dynamic_batch(po_handle h, const po_dynamic_params *p, const po_dynamic_in *in, const po_dynamic_out *out) {
     if (!dynamic_args_ok(h, p, in, out)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
-    if (!dynamic_lists_ok(in)) return PO_ERR_INVALID;
-    const po_agent_lists *L = in->agents;
+    if (!agent_lists_host_ok(in->agents, in->set_of, in->B)) return PO_ERR_INVALID;
     const size_t B = in->B, bn = B * (size_t)in->N;
     Stage S;
     const Slot<double> states = S.in(in->states, 5 * bn), t = S.in(in->t, bn), vin = S.in(in->v_limit_in, bn);
-    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B), first = S.in(L->first, (size_t)L->S + 1);
-    const Slot<po_agent> agents = S.in(L->n_agents > 0 ? L->agents : nullptr, (size_t)L->n_agents);
-    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernel skips it
-    auto opt_i = [&](int *host) { return host ? S.out(host, B) : Slot<int>{}; };
-    auto opt_d = [&](double *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<double>{}; };
-    const Slot<int> status = S.out(out->status, B), ok_out = opt_i(out->ok_out), fs = opt_i(out->first_state), fa = opt_i(out->first_agent), ss = opt_i(out->stop_state);
-    const Slot<double> gmin = opt_d(out->gap_min, B), ft = opt_d(out->first_time, B), gap = opt_d(out->gap, bn), vl = opt_d(out->v_limit, bn);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B);
+    StagedAgents ag;
+    stage_agent_lists(S, in->agents, &ag);
+    const Slot<int> status = S.out(out->status, B), ok_out = S.out_opt(out->ok_out, B), fs = S.out_opt(out->first_state, B), fa = S.out_opt(out->first_agent, B);
+    const Slot<int> ss = S.out_opt(out->stop_state, B);
+    const Slot<double> gmin = S.out_opt(out->gap_min, B), ft = S.out_opt(out->first_time, B), gap = S.out_opt(out->gap, bn), vl = S.out_opt(out->v_limit, bn);
     return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
-        const po_agent_lists dl{agents, first, L->n_agents, L->S};
+        const po_agent_lists dl = ag.dev(in->agents);
         const po_dynamic_in d{in->B, in->N, states, ns, ok, t, set_of, &dl, vin};
         const po_dynamic_out o{status, ok_out, gmin, fs, fa, ss, ft, gap, vl};
         return po_dynamic_batch_device(h, p, &d, &o);
@@ -1405,11 +1413,8 @@ static bool stplan_args_ok(po_handle h, const po_stplan_params *p, const po_stpl
     auto wgt = [](double v) { return std::isfinite(v) && v >= 0; };
     if (!pos(p->dt) || !pos(p->a_max) || !pos(p->b_max) || !pos(p->v_max) || !wgt(p->w_acc) || !wgt(p->w_slow) || !std::isfinite(p->margin)) return false;
     if (p->K < 1 || p->K > PO_ST_MAX_LAYERS || p->stride < 1 || p->U < 1 || p->U > PO_ST_MAX_STEP) return false;
-    const po_agent_lists *L = in->agents;
-    if (L && (L->S < 0 || L->n_agents < 0)) return false;
-    if (in->B == 0) return true;
-    if (!in->states || !in->v0 || !out->status || !L) return false;
-    return L->S >= 1 && L->first && (L->n_agents == 0 || L->agents);
+    if (!agent_lists_shape_ok(in->agents, in->B)) return false;
+    return in->B == 0 || (in->states && in->v0 && out->status);
 }
 
 int po_stplan_batch_device(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out) {
@@ -1435,23 +1440,18 @@ int po_stplan_batch_device(po_handle h, const po_stplan_params *p, const po_stpl
 int po_stplan_batch(po_handle h, const po_stplan_params *p, const po_stplan_in *in, const po_stplan_out *out) {
     if (!stplan_args_ok(h, p, in, out)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
-    po_dynamic_in as_dynamic{};    // the lists are po_dynamic_batch's and so is what the host entry refuses in them
-    as_dynamic.B = in->B; as_dynamic.set_of = in->set_of; as_dynamic.agents = in->agents;
-    if (!dynamic_lists_ok(&as_dynamic)) return PO_ERR_INVALID;
-    const po_agent_lists *L = in->agents;
+    if (!agent_lists_host_ok(in->agents, in->set_of, in->B)) return PO_ERR_INVALID;
     const size_t B = in->B, bn = B * (size_t)in->N;
     Stage S;
     const Slot<double> states = S.in(in->states, 5 * bn), v0 = S.in(in->v0, B), cap = S.in(in->v_cap, bn), vin = S.in(in->v_limit_in, bn);
-    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B), first = S.in(L->first, (size_t)L->S + 1);
-    const Slot<po_agent> agents = S.in(L->n_agents > 0 ? L->agents : nullptr, (size_t)L->n_agents);
-    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernel skips it
-    auto opt_i = [&](int *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<int>{}; };
-    auto opt_d = [&](double *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<double>{}; };
-    const Slot<int> status = S.out(out->status, B), ok_out = opt_i(out->ok_out, B), nl = opt_i(out->n_layers, B);
-    const Slot<int> station = opt_i(out->station, B * (PO_ST_MAX_LAYERS + 1)), cells = opt_i(out->cells, B * (size_t)p->K * PO_ST_MAX_STATIONS);
-    const Slot<double> cost = opt_d(out->cost, B), vl = opt_d(out->v_limit, bn);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B);
+    StagedAgents ag;
+    stage_agent_lists(S, in->agents, &ag);
+    const Slot<int> status = S.out(out->status, B), ok_out = S.out_opt(out->ok_out, B), nl = S.out_opt(out->n_layers, B);
+    const Slot<int> station = S.out_opt(out->station, B * (PO_ST_MAX_LAYERS + 1)), cells = S.out_opt(out->cells, B * (size_t)p->K * PO_ST_MAX_STATIONS);
+    const Slot<double> cost = S.out_opt(out->cost, B), vl = S.out_opt(out->v_limit, bn);
     return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
-        const po_agent_lists dl{agents, first, L->n_agents, L->S};
+        const po_agent_lists dl = ag.dev(in->agents);
         const po_stplan_in d{in->B, in->N, states, ns, ok, v0, cap, set_of, &dl, vin};
         const po_stplan_out o{status, ok_out, nl, cost, station, cells, vl};
         return po_stplan_batch_device(h, p, &d, &o);
@@ -1469,13 +1469,10 @@ static bool nudge_args_ok(po_handle h, const po_nudge_params *p, const po_nudge_
     if (!h || !p || !in || !out || in->B < 0 || in->N < 0 || in->W < 0 || p->skip_states < 0) return false;
     auto room = [](double v) { return std::isfinite(v) && v >= 0; };
     if (!std::isfinite(p->margin) || !room(p->t_before) || !room(p->t_after) || !room(p->min_width)) return false;
-    const po_agent_lists *L = in->agents;
-    if (L && (L->S < 0 || L->n_agents < 0)) return false;
     if (in->W == 0 && (in->side_prev || out->side)) return false;
     if (out->bounds && out->bounds == in->bounds) return false;
-    if (in->B == 0) return true;
-    if (!in->ref_x || !in->ref_y || !in->ref_z || !in->t || !in->bounds || !out->bounds || !out->status || !L) return false;
-    return L->S >= 1 && L->first && (L->n_agents == 0 || L->agents);
+    if (!agent_lists_shape_ok(in->agents, in->B)) return false;
+    return in->B == 0 || (in->ref_x && in->ref_y && in->ref_z && in->t && in->bounds && out->bounds && out->status);
 }
 
 int po_nudge_batch_device(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out) {
@@ -1500,23 +1497,19 @@ int po_nudge_batch_device(po_handle h, const po_nudge_params *p, const po_nudge_
 int po_nudge_batch(po_handle h, const po_nudge_params *p, const po_nudge_in *in, const po_nudge_out *out) {
     if (!nudge_args_ok(h, p, in, out)) return PO_ERR_INVALID;
     if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
-    po_dynamic_in as_dynamic{};    // the lists are po_dynamic_batch's and so is what the host entry refuses in them
-    as_dynamic.B = in->B; as_dynamic.set_of = in->set_of; as_dynamic.agents = in->agents;
-    if (!dynamic_lists_ok(&as_dynamic)) return PO_ERR_INVALID;
-    const po_agent_lists *L = in->agents;
+    if (!agent_lists_host_ok(in->agents, in->set_of, in->B)) return PO_ERR_INVALID;
     const size_t B = in->B, bn = B * (size_t)in->N, bw = B * (size_t)in->W;
     Stage S;
     const Slot<double> rx = S.in(in->ref_x, bn), ry = S.in(in->ref_y, bn), rz = S.in(in->ref_z, bn), t = S.in(in->t, bn), bin = S.in(in->bounds, 8 * bn);
-    const Slot<int> np = S.in(in->n_points, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B), first = S.in(L->first, (size_t)L->S + 1);
+    const Slot<int> np = S.in(in->n_points, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B);
+    StagedAgents ag;
+    stage_agent_lists(S, in->agents, &ag);
     const Slot<int> sprev = S.in(in->side_prev, bw);
-    const Slot<po_agent> agents = S.in(L->n_agents > 0 ? L->agents : nullptr, (size_t)L->n_agents);
-    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernel skips it
-    auto opt_i = [&](int *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<int>{}; };
-    const Slot<int> status = S.out(out->status, B), ok_out = opt_i(out->ok_out, B), side = opt_i(out->side, bw);
-    const Slot<int> fs = opt_i(out->first_blocked_state, B), fa = opt_i(out->first_blocked_agent, B);
-    const Slot<double> bounds = S.out(out->bounds, 8 * bn), wmin = out->width_min ? S.out(out->width_min, B) : Slot<double>{};
+    const Slot<int> status = S.out(out->status, B), ok_out = S.out_opt(out->ok_out, B), side = S.out_opt(out->side, bw);
+    const Slot<int> fs = S.out_opt(out->first_blocked_state, B), fa = S.out_opt(out->first_blocked_agent, B);
+    const Slot<double> bounds = S.out(out->bounds, 8 * bn), wmin = S.out_opt(out->width_min, B);
     return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
-        const po_agent_lists dl{agents, first, L->n_agents, L->S};
+        const po_agent_lists dl = ag.dev(in->agents);
         const po_nudge_in d{in->B, in->N, in->W, rx, ry, rz, np, ok, t, bin, set_of, &dl, sprev};
         const po_nudge_out o{status, ok_out, bounds, side, fs, fa, wmin};
         return po_nudge_batch_device(h, p, &d, &o);
@@ -1578,12 +1571,9 @@ int po_trajectory_batch(po_handle h, const po_trajectory_params *p, const po_tra
     Stage S;
     const Slot<double> states = S.in(in->states, 5 * bn), v = S.in(in->v, bn), t = S.in(in->t, bn);
     const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B);
-    // an optional output the caller does not want is not declared: its slot stays a null pointer and the kernel skips it
-    auto opt_i = [&](int *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<int>{}; };
-    auto opt_d = [&](double *host, size_t cnt) { return host ? S.out(host, cnt) : Slot<double>{}; };
-    const Slot<int> status = S.out(out->status, B), index = opt_i(out->index, bk), fh = opt_i(out->first_held, B);
-    const Slot<double> os = S.out(out->states, 5 * bk), ov = opt_d(out->v, bk), oa = opt_d(out->a, bk), ot = opt_d(out->t, bk);
-    const Slot<po_agent> agents = p->n_discs > 0 ? S.out(out->agents, B * (size_t)p->n_discs) : Slot<po_agent>{};
+    const Slot<int> status = S.out(out->status, B), index = S.out_opt(out->index, bk), fh = S.out_opt(out->first_held, B);
+    const Slot<double> os = S.out(out->states, 5 * bk), ov = S.out_opt(out->v, bk), oa = S.out_opt(out->a, bk), ot = S.out_opt(out->t, bk);
+    const Slot<po_agent> agents = S.out_opt(p->n_discs > 0 ? out->agents : nullptr, B * (size_t)p->n_discs);
     return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
         const po_trajectory_in d{in->B, in->N, states, ns, ok, v, t};
         const po_trajectory_out o{status, os, ov, oa, ot, index, fh, agents};
@@ -1714,7 +1704,7 @@ int po_smooth_batch(po_handle h, const po_smooth_in *in, const po_smooth_out *ou
     // y / s: the device arrays always exist and the kernel writes them (a null host pointer only skips the copy back); raw: not wanted = not declared, the kernel skips it
     const Slot<double> ox = S.out(out->x, np), oy = S.out(out->y, np), os = S.out(out->s, np);
     const Slot<po_info> oinfo = S.out(out->info, B);
-    const Slot<double> oraw = out->raw ? S.out(out->raw, B * (size_t)nmax) : Slot<double>{};
+    const Slot<double> oraw = S.out_opt(out->raw, B * (size_t)nmax);
     return staged_call(h, S, &po_handle_s::smooth_io, false, [&] {
         const po_smooth_in d{in->kind, in->B, in->P, n_points, x, y, angle, k, s, lb, ub, l0};
         const po_smooth_out dout{ox, oy, os, oinfo, oraw};

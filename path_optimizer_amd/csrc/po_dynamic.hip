@@ -1,7 +1,8 @@
 // po_dynamic.hip — moving obstacles: B timed paths against per-instance sets of agents on piecewise-linear predicted trajectories, the
 // continuous-time closest approach of the six footprint circles to every agent, the first conflict and the v_limit rows that make po_speed_batch* stop short of it.
 // The definition is the comment at po_dynamic_batch in include/po_hip.h; this file matches it bit for bit, so it is compiled with -ffp-contract=off (see Makefile)
-// and every expression below keeps the order the definition writes.
+// and every expression below keeps the order the definition writes.  What it shares with the other readers of agents (the chunk through LDS, the walk over an
+// agent's pieces, the closest approach) is po_agents.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -9,30 +10,21 @@
 
 #include "../../include/po_hip.h"
 #include "../../include/po_pmath.h"
+#include "po_agents.hpp"
 #include "po_launch.hpp"
 #include "po_map.hpp"
 
 namespace po {
 
-// (tests/test_dynamic.py places its agent counts around this: DYN_CHUNK there repeats it and changes with it)
-constexpr int kDynChunk = 32;                       // agents per LDS chunk
-constexpr int kAgentWords = sizeof(po_agent) / 8;   // an agent as 8-byte words: (n_pts, flags), radius, t[8], x[8], y[8]
-static_assert(sizeof(po_agent) == 208 && kAgentWords == 2 + 3 * PO_AGENT_MAX_PTS, "po_agent is read as 26 words");
-
-__device__ __forceinline__ double dyn_min(double a, double b) { return b < a ? b : a; }
-__device__ __forceinline__ double dyn_max(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ bool dyn_finite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN and +-inf
-__device__ __forceinline__ int dyn_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // One wave per path, lanes over intervals, 64 intervals a tile.  A lane holds the six circle centres of its interval's first state and their differences to the
 // second one in registers (the circle loop is unrolled for that: a register array indexed by a loop counter would go to scratch) and walks the agents of the
-// path's set, which the wave moves through LDS kDynChunk at a time: every lane reads the same agent word, a broadcast.  A set that fits one chunk is loaded once,
+// path's set, which the wave moves through LDS kAgentChunk at a time: every lane reads the same agent word, a broadcast.  A set that fits one chunk is loaded once,
 // a longer one once per tile.  The wave is the whole workgroup, so every barrier below is reached by all of it: the loops around them have wave-uniform bounds.
 __global__ __launch_bounds__(64) void dynamic_check_kernel(DevCar c, DevDynamic a) {
-    __shared__ double ag_l[kDynChunk * kAgentWords];
-    __shared__ int np_l[kDynChunk];  // points of the agent; 0: it covers nothing
+    __shared__ double ag_l[kAgentChunk * kAgentWords];
+    __shared__ int np_l[kAgentChunk];  // points of the agent; 0: it covers nothing
     const int b = blockIdx.x, lane = threadIdx.x, N = a.N;
-    const int n = dyn_clamp(a.n_states ? a.n_states[b] : N, N);
+    const int n = ag_clamp(a.n_states ? a.n_states[b] : N, N);
     const double *st = a.states + (size_t)b * N * 5, *tr = a.t + (size_t)b * N;
     const double *lin = a.v_limit_in ? a.v_limit_in + (size_t)b * N : nullptr;
     double *grow = a.gap ? a.gap + (size_t)b * N : nullptr, *lrow = a.v_limit ? a.v_limit + (size_t)b * N : nullptr;
@@ -42,15 +34,15 @@ __global__ __launch_bounds__(64) void dynamic_check_kernel(DevCar c, DevDynamic 
     if (good)
         for (int i = lane; i < n; i += 64) {
             const double *r = st + 5 * (size_t)i;
-            finite = finite && dyn_finite(r[0]) && dyn_finite(r[1]) && dyn_finite(r[2]) && dyn_finite(tr[i]);
+            finite = finite && ag_finite(r[0]) && ag_finite(r[1]) && ag_finite(r[2]) && ag_finite(tr[i]);
         }
     const bool checked = good && !__any(!finite);
 
     double gmin = DBL_MAX;
     int fi = INT_MAX, fa = -1;  // the first interval of this lane below the margin, and its agent
     if (checked) {
-        const int k = dyn_clamp(a.set_of ? a.set_of[b] : 0, a.S - 1);
-        const int lo = dyn_clamp(a.first[k], a.n_agents), hi = dyn_clamp(a.first[k + 1], a.n_agents);
+        int lo, hi;
+        agent_set_range(a.first, a.set_of, b, a.S, a.n_agents, lo, hi);
         for (int t0 = 0; t0 < n - 1; t0 += 64) {
             const int i = t0 + lane;
             const bool in_path = i < n - 1;
@@ -71,72 +63,30 @@ __global__ __launch_bounds__(64) void dynamic_check_kernel(DevCar c, DevDynamic 
             const bool act = in_path && dt > 0;
             double g = DBL_MAX;
             int arg = -1;
-            for (int c0 = lo; c0 < hi; c0 += kDynChunk) {
-                const int cnt = (hi - c0) < kDynChunk ? (hi - c0) : kDynChunk;
-                if (t0 == 0 || hi - lo > kDynChunk) {  // (wave-uniform)
-                    __syncthreads();
-                    const double *src = reinterpret_cast<const double *>(a.agents + c0);
-                    for (int w = lane; w < cnt * kAgentWords; w += 64) ag_l[w] = src[w];
-                    __syncthreads();
-                    if (lane < cnt) {  // lane j judges agent j of the chunk
-                        const double *A = ag_l + lane * kAgentWords;
-                        int np = (int)(unsigned)(__double_as_longlong(A[0]) & 0xffffffffll);
-                        bool covers = np >= 1 && np <= PO_AGENT_MAX_PTS && A[1] >= 0;
-                        for (int j = 0; j < PO_AGENT_MAX_PTS; ++j)
-                            if (covers && j < np) covers = dyn_finite(A[2 + j]) && dyn_finite(A[10 + j]) && dyn_finite(A[18 + j]);
-                        np_l[lane] = covers ? np : 0;
-                    }
-                    __syncthreads();
-                }
+            for (int c0 = lo; c0 < hi; c0 += kAgentChunk) {
+                const int cnt = (hi - c0) < kAgentChunk ? (hi - c0) : kAgentChunk;
+                if (t0 == 0 || hi - lo > kAgentChunk) agent_chunk_load<64>(a.agents + c0, cnt, ag_l, np_l);  // (wave-uniform)
                 if (!act) continue;
                 for (int j = 0; j < cnt; ++j) {
                     const int np = np_l[j];
                     if (np == 0) continue;
-                    const double *A = ag_l + j * kAgentWords, *T = A + 2, *X = A + 2 + PO_AGENT_MAX_PTS, *Y = A + 2 + 2 * PO_AGENT_MAX_PTS;
-                    const int flags = (int)(__double_as_longlong(A[0]) >> 32);
-                    const double R = A[1];
-                    for (int p = -1; p < np; ++p) {  // p = -1: before; 0 .. np - 2: segment p; np - 1: after   (wave-uniform)
-                        double ta, tb, axa, aya, axb, ayb;
-                        if (p < 0) {
-                            if (!(flags & PO_AGENT_HOLD_BEFORE)) continue;
-                            ta = t_i; tb = dyn_min(t_n, T[0]);
-                            if (!(ta <= tb)) continue;
-                            axa = axb = X[0]; aya = ayb = Y[0];
-                        } else if (p == np - 1) {
-                            if (!(flags & PO_AGENT_HOLD_AFTER)) continue;
-                            ta = dyn_max(t_i, T[p]); tb = t_n;
-                            if (!(ta <= tb)) continue;
-                            axa = axb = X[p]; aya = ayb = Y[p];
-                        } else {
-                            const double D = T[p + 1] - T[p];
-                            if (!(D > 0)) continue;
-                            ta = dyn_max(t_i, T[p]); tb = dyn_min(t_n, T[p + 1]);
-                            if (!(ta <= tb)) continue;
-                            const double wa = (ta - T[p]) / D, wb = (tb - T[p]) / D;
-                            const double DX = X[p + 1] - X[p], DY = Y[p + 1] - Y[p];
-                            axa = X[p] + wa * DX; aya = Y[p] + wa * DY;
-                            axb = X[p] + wb * DX; ayb = Y[p] + wb * DY;
-                        }
+                    const double *G = ag_l + j * kAgentWords;
+                    const double R = agent_R(G);
+                    agent_pieces(G, np, t_i, t_n, [&](double ta, double tb, double axa, double aya, double axb, double ayb) {  // (wave-uniform)
                         const double ua = (ta - t_i) / dt, ub = (tb - t_i) / dt;
 #pragma unroll
                         for (int q = 0; q < 6; ++q) {
                             const double rax = (gx[q] + ua * ex[q]) - axa, ray = (gy[q] + ua * ey[q]) - aya;
                             const double rbx = (gx[q] + ub * ex[q]) - axb, rby = (gy[q] + ub * ey[q]) - ayb;
-                            const double dx = rbx - rax, dy = rby - ray, px = -rax, py = -ray;
-                            const double L2 = dx * dx + dy * dy, dot = px * dx + py * dy;
-                            double u = L2 > 0 ? dot / L2 : 0;
-                            u = u < 0 ? 0 : u;
-                            u = u > 1 ? 1 : u;
-                            const double qx = px - u * dx, qy = py - u * dy;
-                            const double gap = (sqrt(qx * qx + qy * qy) - c.cr[q]) - R;
+                            const double gap = agent_gap(rax, ray, rbx, rby, c.cr[q], R);
                             if (gap < g) { g = gap; arg = c0 + j; }
                         }
-                    }
+                    });
                 }
             }
             if (in_path) {
                 if (grow) grow[i] = g;
-                gmin = dyn_min(gmin, g);
+                gmin = ag_min(gmin, g);
                 if (fi == INT_MAX && g < a.margin) { fi = i; fa = arg; }
             }
         }
@@ -148,7 +98,7 @@ __global__ __launch_bounds__(64) void dynamic_check_kernel(DevCar c, DevDynamic 
     // the wave's verdict: integer minima and maxima and a minimum of doubles that are never NaN and never -0, so the butterflies' order does not matter
     int f = fi;
     for (int h = 32; h > 0; h >>= 1) {
-        gmin = dyn_min(gmin, __shfl_xor(gmin, h));
+        gmin = ag_min(gmin, __shfl_xor(gmin, h));
         const int o = __shfl_xor(f, h);
         f = o < f ? o : f;
     }

@@ -164,7 +164,7 @@ inline bool assignment_covers(const po_handle_s *h, int B) PO_REQUIRES(h->mu) { 
 // synchronises.  A slot converts to its device pointer once the block is reserved, so no entry computes an offset.  Every slot is aligned to 16 bytes.
 //   in(host, n)      n elements copied from host; host == nullptr: the array is absent, takes no room, and the slot is a null pointer
 //   out(host, n)     n elements the kernel writes, copied to host by copy_out(); host == nullptr: the device array exists all the same, only the copy is skipped
-//                    (an output the kernel must not write at all is simply not declared: a default-constructed Slot is a null pointer)
+//   out_opt(host, n) an optional output: host == nullptr: the caller does not want it, it is not declared, and the slot is a null pointer that the kernel skips
 //   scratch(n)       n elements that travel in neither direction
 // Copies go from / to the caller's own memory on the handle's stream, under mu; the block itself is under the lock its member names.
 class Stage;
@@ -190,6 +190,7 @@ class Stage : NoCopy {
 public:
     template <typename T> Slot<T> in(const T *host, size_t n) { return host ? add<T>(n, host, nullptr) : Slot<T>{}; }
     template <typename T> Slot<T> out(T *host, size_t n) { return add<T>(n, nullptr, host); }
+    template <typename T> Slot<T> out_opt(T *host, size_t n) { return host ? out(host, n) : Slot<T>{}; }
     template <typename T> Slot<T> scratch(size_t n) { return add<T>(n, nullptr, nullptr); }
     size_t bytes() const { return bytes_; }
     int reserve(po_handle h, DevBuf &buf, bool after_sync = false) PO_REQUIRES(h->mu) {

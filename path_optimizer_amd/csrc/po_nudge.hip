@@ -1,7 +1,8 @@
 // po_nudge.hip — corridor nudge: per path, the lateral interval every predicted agent of its set occupies on every (state, covering circle)
 // pair of the corridor while the vehicle is expected there, the side the vehicle passes each agent on, and the corridor bounds carved to that side, in the layout
 // po_batch_in.bounds reads.  The definition is the comment at po_nudge_batch in include/po_hip.h; this file matches it bit for bit, so it is compiled with
-// -ffp-contract=off (see Makefile) and every expression below keeps the order the definition writes.
+// -ffp-contract=off (see Makefile) and every expression below keeps the order the definition writes.  What it shares with the other readers of agents (the chunk
+// through LDS, the walk over an agent's pieces) is po_agents.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -9,22 +10,16 @@
 
 #include "../../include/po_hip.h"
 #include "../../include/po_pmath.h"
+#include "po_agents.hpp"
 #include "po_launch.hpp"
 #include "po_map.hpp"
 
 namespace po {
 
-// (tests/test_nudge.py places its agent counts and path lengths around these: NDG_CHUNK and NDG_TRIG there repeat them and change with them)
-constexpr int kNdgChunk = 32;                        // agents per LDS chunk
-constexpr int kNdgTrig = 384;                        // states whose cos / sin are kept in LDS; the states behind them compute theirs again per agent
-constexpr int kNdgAgentWords = sizeof(po_agent) / 8; // an agent as 8-byte words: (n_pts, flags), radius, t[8], x[8], y[8]
-static_assert(sizeof(po_agent) == 208 && kNdgAgentWords == 2 + 3 * PO_AGENT_MAX_PTS, "po_agent is read as 26 words");
+// (tests/test_nudge.py places its path lengths around this: NDG_TRIG there repeats it and changes with it)
+constexpr int kNdgTrig = 384;  // states whose cos / sin are kept in LDS; the states behind them compute theirs again per agent
 
-__device__ __forceinline__ double ndg_min(double a, double b) { return b < a ? b : a; }
-__device__ __forceinline__ double ndg_max(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ bool ndg_finite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN and +-inf
-__device__ __forceinline__ int ndg_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-__device__ __forceinline__ void ndg_fold(double c, double &lo, double &hi) { lo = ndg_min(lo, c); hi = ndg_max(hi, c); }
+__device__ __forceinline__ void ndg_fold(double c, double &lo, double &hi) { lo = ag_min(lo, c); hi = ag_max(hi, c); }
 
 // One piece of an agent, from (axa, aya) to (axb, ayb) in the world, on the pair whose frame is (cx, cy, cz, sz): the candidates of the definition, in its order.
 __device__ __forceinline__ void ndg_piece(double axa, double aya, double axb, double ayb, double cx, double cy, double cz, double sz, double rho, double &lo,
@@ -57,49 +52,24 @@ __device__ __forceinline__ void ndg_piece(double axa, double aya, double axb, do
 // The hull of the agent at G (26 words in LDS, np points) on one pair, over the window [w0, w1] of the pair's state.
 __device__ __forceinline__ void ndg_hull(const double *G, int np, double w0, double w1, double cx, double cy, double cz, double sz, double rho, double &lo,
                                          double &hi) {
-    const double *T = G + 2, *X = G + 2 + PO_AGENT_MAX_PTS, *Y = G + 2 + 2 * PO_AGENT_MAX_PTS;
-    const int flags = (int)(__double_as_longlong(G[0]) >> 32);
     lo = DBL_MAX; hi = -DBL_MAX;
-    for (int p = -1; p < np; ++p) {  // p = -1: before; 0 .. np - 2: segment p; np - 1: after   (wave-uniform)
-        double ta, tb, axa, aya, axb, ayb;
-        if (p < 0) {
-            if (!(flags & PO_AGENT_HOLD_BEFORE)) continue;
-            ta = w0; tb = ndg_min(w1, T[0]);
-            if (!(ta <= tb)) continue;
-            axa = axb = X[0]; aya = ayb = Y[0];
-        } else if (p == np - 1) {
-            if (!(flags & PO_AGENT_HOLD_AFTER)) continue;
-            ta = ndg_max(w0, T[p]); tb = w1;
-            if (!(ta <= tb)) continue;
-            axa = axb = X[p]; aya = ayb = Y[p];
-        } else {
-            const double D = T[p + 1] - T[p];
-            if (!(D > 0)) continue;
-            ta = ndg_max(w0, T[p]); tb = ndg_min(w1, T[p + 1]);
-            if (!(ta <= tb)) continue;
-            const double wa = (ta - T[p]) / D, wb = (tb - T[p]) / D;
-            const double DX = X[p + 1] - X[p], DY = Y[p + 1] - Y[p];
-            axa = X[p] + wa * DX; aya = Y[p] + wa * DY;
-            axb = X[p] + wb * DX; ayb = Y[p] + wb * DY;
-        }
-        ndg_piece(axa, aya, axb, ayb, cx, cy, cz, sz, rho, lo, hi);
-    }
+    agent_pieces(G, np, w0, w1, [&](double, double, double axa, double aya, double axb, double ayb) { ndg_piece(axa, aya, axb, ayb, cx, cy, cz, sz, rho, lo, hi); });
 }
 
 // One wave per path.  Pair p = 4 i + j (state i, circle j) belongs to lane p mod 64, for good: 64 is a multiple of 4, so a lane keeps its circle j = lane & 3 and
 // walks the states (lane >> 2) + 16 k.  The working corridor of a lane's pairs lives in out->bounds itself: the lane that wrote a pair is the one that reads it
-// again, so nothing needs synchronising, no LDS is sized by N and N has no limit.  The agents of the path's set move through LDS kNdgChunk at a time and are read
+// again, so nothing needs synchronising, no LDS is sized by N and N has no limit.  The agents of the path's set move through LDS kAgentChunk at a time and are read
 // as broadcasts; lane j of the wave judges agent j of the chunk: whether it covers anything, and whether its whole time extent, holds included, meets the path's
 // [min t - t_before, max t + t_after] at all — an agent that does not has no live piece on any pair, so skipping it changes no result.  Per live agent: one sweep
 // over the lane's pairs for hull and touch, rl, rr and f reduced across the wave; the decision, wave-uniform; and, only when the agent is passed on a side, a
 // second sweep that computes the hulls again and moves the bound (most agents touch nothing, so the hulls are not kept).  The wave is the whole workgroup, so every
 // barrier below is reached by all of it: the loops around them have wave-uniform bounds.
 __global__ __launch_bounds__(64) void nudge_kernel(DevNudge a) {
-    __shared__ double ag_l[kNdgChunk * kNdgAgentWords];
-    __shared__ int np_l[kNdgChunk];  // points of the agent; 0: it covers nothing, or is nowhere near the path in time
+    __shared__ double ag_l[kAgentChunk * kAgentWords];
+    __shared__ int np_l[kAgentChunk];  // points of the agent; 0: it covers nothing, or is nowhere near the path in time
     __shared__ double cz_l[kNdgTrig], sz_l[kNdgTrig];
     const int b = blockIdx.x, lane = threadIdx.x, N = a.N, W = a.W;
-    const int n = ndg_clamp(a.n_points ? a.n_points[b] : N, N);
+    const int n = ag_clamp(a.n_points ? a.n_points[b] : N, N);
     const size_t row = (size_t)b * N;
     const double *X = a.ref_x + row, *Y = a.ref_y + row, *Z = a.ref_z + row, *T = a.t + row, *bin = a.bounds_in + 8 * row;
     double *bo = a.bounds + 8 * row;
@@ -112,9 +82,9 @@ __global__ __launch_bounds__(64) void nudge_kernel(DevNudge a) {
     for (size_t p = lane; p < all_pairs; p += 64) {
         const double l = bin[2 * p], u = bin[2 * p + 1];
         bo[2 * p] = l; bo[2 * p + 1] = u;
-        if (p < pairs) finite = finite && ndg_finite(l) && ndg_finite(u);
+        if (p < pairs) finite = finite && ag_finite(l) && ag_finite(u);
     }
-    for (int i = lane; i < n; i += 64) finite = finite && ndg_finite(X[i]) && ndg_finite(Y[i]) && ndg_finite(Z[i]) && ndg_finite(T[i]);
+    for (int i = lane; i < n; i += 64) finite = finite && ag_finite(X[i]) && ag_finite(Y[i]) && ag_finite(Z[i]) && ag_finite(T[i]);
     const bool processed = (a.ok ? a.ok[b] != 0 : true) && n >= 1 && !__any(!finite);  // wave-uniform
 
     if (!processed) {
@@ -135,47 +105,39 @@ __global__ __launch_bounds__(64) void nudge_kernel(DevNudge a) {
     double tmin = DBL_MAX, tmax = -DBL_MAX;
     for (int i = lane; i < n; i += 64) {
         if (i < kNdgTrig) { cz_l[i] = po_pcos(Z[i]); sz_l[i] = po_psin(Z[i]); }
-        tmin = ndg_min(tmin, T[i] - a.t_before);
-        tmax = ndg_max(tmax, T[i] + a.t_after);
+        tmin = ag_min(tmin, T[i] - a.t_before);
+        tmax = ag_max(tmax, T[i] + a.t_after);
     }
     for (int h = 32; h > 0; h >>= 1) {
-        tmin = ndg_min(tmin, __shfl_xor(tmin, h));
-        tmax = ndg_max(tmax, __shfl_xor(tmax, h));
+        tmin = ag_min(tmin, __shfl_xor(tmin, h));
+        tmax = ag_max(tmax, __shfl_xor(tmax, h));
     }
     const int jq = lane & 3;
     const double dj = jq == 0 ? a.d[0] : (jq == 1 ? a.d[1] : (jq == 2 ? a.d[2] : a.d[3]));  // (selects: a kernel argument indexed by the lane would go to scratch)
     const size_t p_first = a.skip_states > 0 ? 4 * (size_t)a.skip_states : 0;  // pairs of rows < skip_states are never touched
 
-    const int k = ndg_clamp(a.set_of ? a.set_of[b] : 0, a.S - 1);
-    const int lo_a = ndg_clamp(a.first[k], a.n_agents), hi_a = ndg_clamp(a.first[k + 1], a.n_agents);
+    int lo_a, hi_a;
+    agent_set_range(a.first, a.set_of, b, a.S, a.n_agents, lo_a, hi_a);
     bool carved = false;
     int fb_state = -1, fb_agent = -1;  // the first blocking agent
-    for (int c0 = lo_a; c0 < hi_a; c0 += kNdgChunk) {
-        const int cnt = (hi_a - c0) < kNdgChunk ? (hi_a - c0) : kNdgChunk;
-        __syncthreads();  // cz_l, sz_l are written; the previous chunk is read
-        const double *src = reinterpret_cast<const double *>(a.agents + c0);
-        for (int w = lane; w < cnt * kNdgAgentWords; w += 64) ag_l[w] = src[w];
-        __syncthreads();
-        if (lane < cnt) {  // lane j judges agent j of the chunk
-            const double *G = ag_l + lane * kNdgAgentWords;
-            const int np = (int)(unsigned)(__double_as_longlong(G[0]) & 0xffffffffll), flags = (int)(__double_as_longlong(G[0]) >> 32);
-            bool live = np >= 1 && np <= PO_AGENT_MAX_PTS && G[1] >= 0;
+    for (int c0 = lo_a; c0 < hi_a; c0 += kAgentChunk) {
+        const int cnt = (hi_a - c0) < kAgentChunk ? (hi_a - c0) : kAgentChunk;
+        // (the load's first barrier: cz_l, sz_l are written; the previous chunk is read)
+        agent_chunk_load<64>(a.agents + c0, cnt, ag_l, np_l, [&](const double *G, int np) {  // an agent that covers something: is it near the path in time?
+            const double *Ta = agent_T(G);
+            const int flags = agent_flags(G);
             double t_lo = DBL_MAX, t_hi = -DBL_MAX;  // every piece lies within [t_lo, t_hi], but for the holds
             for (int j = 0; j < PO_AGENT_MAX_PTS; ++j)
-                if (live && j < np) {
-                    live = ndg_finite(G[2 + j]) && ndg_finite(G[10 + j]) && ndg_finite(G[18 + j]);
-                    t_lo = ndg_min(t_lo, G[2 + j]); t_hi = ndg_max(t_hi, G[2 + j]);
-                }
-            if (live && !(flags & PO_AGENT_HOLD_BEFORE) && tmax < t_lo) live = false;  // every window ends before the agent appears: tb < ta in every piece
-            if (live && !(flags & PO_AGENT_HOLD_AFTER) && tmin > t_hi) live = false;   // every window begins after it is gone
-            np_l[lane] = live ? np : 0;
-        }
-        __syncthreads();
+                if (j < np) { t_lo = ag_min(t_lo, Ta[j]); t_hi = ag_max(t_hi, Ta[j]); }
+            if (!(flags & PO_AGENT_HOLD_BEFORE) && tmax < t_lo) return false;  // every window ends before the agent appears: tb < ta in every piece
+            if (!(flags & PO_AGENT_HOLD_AFTER) && tmin > t_hi) return false;   // every window begins after it is gone
+            return true;
+        });
         for (int j = 0; j < cnt; ++j) {
             const int np = np_l[j], e = c0 + j - lo_a;
             int side = 0;
             if (np != 0 && p_first < pairs) {  // (wave-uniform)
-                const double *G = ag_l + j * kNdgAgentWords;
+                const double *G = ag_l + j * kAgentWords;
                 const double rho = (a.radius + G[1]) + a.margin;
                 double rl = DBL_MAX, rr = DBL_MAX;
                 int f = INT_MAX;
@@ -187,14 +149,14 @@ __global__ __launch_bounds__(64) void nudge_kernel(DevNudge a) {
                     ndg_hull(G, np, T[i] - a.t_before, T[i] + a.t_after, X[i] + dj * cz, Y[i] + dj * sz, cz, sz, rho, lo, hi);
                     const double Wl = bo[2 * p], Wu = bo[2 * p + 1];
                     if (lo <= hi && hi > Wl && lo < Wu) {
-                        rl = ndg_min(rl, Wu - hi);
-                        rr = ndg_min(rr, lo - Wl);
+                        rl = ag_min(rl, Wu - hi);
+                        rr = ag_min(rr, lo - Wl);
                         f = i < f ? i : f;
                     }
                 }
                 for (int h = 32; h > 0; h >>= 1) {  // rl and rr are never NaN
-                    rl = ndg_min(rl, __shfl_xor(rl, h));
-                    rr = ndg_min(rr, __shfl_xor(rr, h));
+                    rl = ag_min(rl, __shfl_xor(rl, h));
+                    rr = ag_min(rr, __shfl_xor(rr, h));
                     const int o = __shfl_xor(f, h);
                     f = o < f ? o : f;
                 }
@@ -236,9 +198,9 @@ __global__ __launch_bounds__(64) void nudge_kernel(DevNudge a) {
     for (size_t p = lane; p < pairs; p += 64) {
         double w = bo[2 * p + 1] - bo[2 * p];
         w = w == 0 ? 0.0 : w;  // -0.0 counts as +0.0: the minimum does not depend on the order of the fold
-        wmin = ndg_min(wmin, w);
+        wmin = ag_min(wmin, w);
     }
-    for (int h = 32; h > 0; h >>= 1) wmin = ndg_min(wmin, __shfl_xor(wmin, h));
+    for (int h = 32; h > 0; h >>= 1) wmin = ag_min(wmin, __shfl_xor(wmin, h));
     if (lane == 0) {
         const int status = fb_agent >= 0 ? 3 : (carved ? 2 : 1);
         a.status[b] = status;

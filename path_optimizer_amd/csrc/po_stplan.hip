@@ -1,7 +1,8 @@
 // po_stplan.hip — station-time speed planning: per path, the (time window, station) cells the agents of its set block, then a layered
 // shortest-path search over (station, stations advanced in the last step) that passes ahead of an agent, eases off behind it or stops, and the v_limit rows that
 // hand the plan to po_speed_batch*.  The definition is the comment at po_stplan_batch in include/po_hip.h; this file matches it bit for bit, so it is compiled with
-// -ffp-contract=off (see Makefile) and every expression below keeps the order the definition writes.
+// -ffp-contract=off (see Makefile) and every expression below keeps the order the definition writes.  What it shares with the other readers of agents (the chunk
+// through LDS, the walk over an agent's pieces, the closest approach) is po_agents.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -9,22 +10,14 @@
 
 #include "../../include/po_hip.h"
 #include "../../include/po_pmath.h"
+#include "po_agents.hpp"
 #include "po_launch.hpp"
 #include "po_map.hpp"
 
 namespace po {
 
-// (tests/test_stplan.py places its agent counts around this: ST_CHUNK there repeats it and changes with it)
-constexpr int kStChunk = 32;                        // agents per LDS chunk
-constexpr int kStThreads = 512;                     // one workgroup per path
-constexpr int kStAgentWords = sizeof(po_agent) / 8; // an agent as 8-byte words: (n_pts, flags), radius, t[8], x[8], y[8]
-static_assert(sizeof(po_agent) == 208 && kStAgentWords == 2 + 3 * PO_AGENT_MAX_PTS, "po_agent is read as 26 words");
+constexpr int kStThreads = 512;  // one workgroup per path
 static_assert(PO_ST_MAX_STEP + 1 <= 256 && PO_ST_MAX_STATIONS == 128, "back pointers are bytes; a cells row is indexed with >> 7");
-
-__device__ __forceinline__ double stp_min(double a, double b) { return b < a ? b : a; }
-__device__ __forceinline__ double stp_max(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ bool stp_finite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN and +-inf
-__device__ __forceinline__ int stp_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // The dynamic LDS of one workgroup, in doubles then ints then bytes; Mb bounds the stations of every path of the call (the launcher computes it from N and stride).
 //   A      max(2 * Mb * (U + 1), 12 * Mb) doubles: the circle centres of the stations in phase 1, the two cost layers in phase 2
@@ -37,17 +30,17 @@ __host__ __device__ inline size_t stp_lds_bytes(int K, int Mb, int U) {
 }
 
 // One workgroup per path.  Phase 1: lanes over the K * M cells; a lane holds the six circle centres of its cell's station in registers (the circle loop is unrolled
-// for that) and walks the agents of the path's set, which the workgroup moves through LDS kStChunk at a time: every lane reads the same agent word, a broadcast.
+// for that) and walks the agents of the path's set, which the workgroup moves through LDS kAgentChunk at a time: every lane reads the same agent word, a broadcast.
 // Phase 2: lanes over the M * (U + 1) states of a layer, one barrier a layer; wave 0 picks the layer's best candidate.  Every barrier is reached by the whole
 // workgroup: the loops around them have workgroup-uniform bounds, and the early return of a path that is not planned is uniform too.
 __global__ __launch_bounds__(kStThreads) void stplan_kernel(DevCar c, DevStplan a) {
     extern __shared__ double stp_lds[];
-    __shared__ double ag_l[kStChunk * kStAgentWords];
-    __shared__ int np_l[kStChunk];  // points of the agent; 0: it covers nothing
+    __shared__ double ag_l[kAgentChunk * kAgentWords];
+    __shared__ int np_l[kAgentChunk];  // points of the agent; 0: it covers nothing
     __shared__ int bad_l, plan_l[2], plan_st[PO_ST_MAX_LAYERS + 1], plan_u[PO_ST_MAX_LAYERS + 1];
     __shared__ double cost_l;
     const int b = blockIdx.x, tid = threadIdx.x, N = a.N, K = a.K, U1 = a.U + 1, Mb = a.Mb, stride = a.stride;
-    const int n = stp_clamp(a.n_states ? a.n_states[b] : N, N);
+    const int n = ag_clamp(a.n_states ? a.n_states[b] : N, N);
     const double *st = a.states + (size_t)b * N * 5;
     const double *lin = a.v_limit_in ? a.v_limit_in + (size_t)b * N : nullptr;
     double *lrow = a.v_limit ? a.v_limit + (size_t)b * N : nullptr;
@@ -60,14 +53,14 @@ __global__ __launch_bounds__(kStThreads) void stplan_kernel(DevCar c, DevStplan 
 
     int M = (n - 1) / stride + 1;
     M = M > PO_ST_MAX_STATIONS ? PO_ST_MAX_STATIONS : M;
-    const bool good = (a.ok ? a.ok[b] != 0 : true) && n >= 2 && stp_finite(v0) && v0 >= 0 && M >= 2;  // uniform
+    const bool good = (a.ok ? a.ok[b] != 0 : true) && n >= 2 && ag_finite(v0) && v0 >= 0 && M >= 2;  // uniform
     if (tid == 0) bad_l = 0;
     __syncthreads();
     if (good) {
         bool finite = true;
         for (int i = tid; i < n; i += kStThreads) {
             const double *r = st + 5 * (size_t)i;
-            finite = finite && stp_finite(r[0]) && stp_finite(r[1]) && stp_finite(r[2]) && stp_finite(r[4]);
+            finite = finite && ag_finite(r[0]) && ag_finite(r[1]) && ag_finite(r[2]) && ag_finite(r[4]);
         }
         if (!finite) bad_l = 1;
     }
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(kStThreads) void stplan_kernel(DevCar c, DevStplan 
         double vc = a.v_max;
         if (a.v_cap) {
             const double e = a.v_cap[(size_t)b * N + i];
-            if (e >= 0) vc = stp_min(vc, e);
+            if (e >= 0) vc = ag_min(vc, e);
         }
         Vc_l[m] = vc;
         const double cz = po_pcos(r[2]), sz = po_psin(r[2]);
@@ -112,23 +105,11 @@ __global__ __launch_bounds__(kStThreads) void stplan_kernel(DevCar c, DevStplan 
     for (int ci = tid; ci < nc; ci += kStThreads) cell_l[(ci / M) * Mb + ci % M] = -1;
 
     // ---- phase 1: blocked cells ----
-    const int ks = stp_clamp(a.set_of ? a.set_of[b] : 0, a.S - 1);
-    const int lo = stp_clamp(a.first[ks], a.n_agents), hi = stp_clamp(a.first[ks + 1], a.n_agents);
-    for (int c0 = lo; c0 < hi; c0 += kStChunk) {
-        const int cnt = (hi - c0) < kStChunk ? (hi - c0) : kStChunk;
-        __syncthreads();  // the stations are written; the previous chunk is read
-        const double *src = reinterpret_cast<const double *>(a.agents + c0);
-        for (int w = tid; w < cnt * kStAgentWords; w += kStThreads) ag_l[w] = src[w];
-        __syncthreads();
-        if (tid < cnt) {  // thread j judges agent j of the chunk
-            const double *G = ag_l + tid * kStAgentWords;
-            int np = (int)(unsigned)(__double_as_longlong(G[0]) & 0xffffffffll);
-            bool covers = np >= 1 && np <= PO_AGENT_MAX_PTS && G[1] >= 0;
-            for (int j = 0; j < PO_AGENT_MAX_PTS; ++j)
-                if (covers && j < np) covers = stp_finite(G[2 + j]) && stp_finite(G[10 + j]) && stp_finite(G[18 + j]);
-            np_l[tid] = covers ? np : 0;
-        }
-        __syncthreads();
+    int lo, hi;
+    agent_set_range(a.first, a.set_of, b, a.S, a.n_agents, lo, hi);
+    for (int c0 = lo; c0 < hi; c0 += kAgentChunk) {
+        const int cnt = (hi - c0) < kAgentChunk ? (hi - c0) : kAgentChunk;
+        agent_chunk_load<kStThreads>(a.agents + c0, cnt, ag_l, np_l);  // (its first barrier: the stations are written; the previous chunk is read)
         for (int cb = 0; cb < nc; cb += kStThreads) {
             const int ci = cb + tid;
             if (ci >= nc) continue;
@@ -142,44 +123,15 @@ __global__ __launch_bounds__(kStThreads) void stplan_kernel(DevCar c, DevStplan 
             for (int j = 0; j < cnt && found < 0; ++j) {
                 const int np = np_l[j];
                 if (np == 0) continue;
-                const double *G = ag_l + j * kStAgentWords, *T = G + 2, *X = G + 2 + PO_AGENT_MAX_PTS, *Y = G + 2 + 2 * PO_AGENT_MAX_PTS;
-                const int flags = (int)(__double_as_longlong(G[0]) >> 32);
-                const double R = G[1];
-                for (int p = -1; p < np; ++p) {  // p = -1: before; 0 .. np - 2: segment p; np - 1: after
-                    double ta, tb, axa, aya, axb, ayb;
-                    if (p < 0) {
-                        if (!(flags & PO_AGENT_HOLD_BEFORE)) continue;
-                        ta = tk; tb = stp_min(tk1, T[0]);
-                        if (!(ta <= tb)) continue;
-                        axa = axb = X[0]; aya = ayb = Y[0];
-                    } else if (p == np - 1) {
-                        if (!(flags & PO_AGENT_HOLD_AFTER)) continue;
-                        ta = stp_max(tk, T[p]); tb = tk1;
-                        if (!(ta <= tb)) continue;
-                        axa = axb = X[p]; aya = ayb = Y[p];
-                    } else {
-                        const double D = T[p + 1] - T[p];
-                        if (!(D > 0)) continue;
-                        ta = stp_max(tk, T[p]); tb = stp_min(tk1, T[p + 1]);
-                        if (!(ta <= tb)) continue;
-                        const double wa = (ta - T[p]) / D, wb = (tb - T[p]) / D;
-                        const double DX = X[p + 1] - X[p], DY = Y[p + 1] - Y[p];
-                        axa = X[p] + wa * DX; aya = Y[p] + wa * DY;
-                        axb = X[p] + wb * DX; ayb = Y[p] + wb * DY;
-                    }
+                const double *G = ag_l + j * kAgentWords;
+                const double R = agent_R(G);
+                agent_pieces(G, np, tk, tk1, [&](double, double, double axa, double aya, double axb, double ayb) {
 #pragma unroll
                     for (int q = 0; q < 6; ++q) {
-                        const double rax = gx[q] - axa, ray = gy[q] - aya, rbx = gx[q] - axb, rby = gy[q] - ayb;
-                        const double dx = rbx - rax, dy = rby - ray, px = -rax, py = -ray;
-                        const double L2 = dx * dx + dy * dy, dot = px * dx + py * dy;
-                        double u = L2 > 0 ? dot / L2 : 0;
-                        u = u < 0 ? 0 : u;
-                        u = u > 1 ? 1 : u;
-                        const double qx = px - u * dx, qy = py - u * dy;
-                        const double gap = (sqrt(qx * qx + qy * qy) - c.cr[q]) - R;
+                        const double gap = agent_gap(gx[q] - axa, gy[q] - aya, gx[q] - axb, gy[q] - ayb, c.cr[q], R);
                         if (gap < a.margin) found = c0 + j;
                     }
-                }
+                });
             }
             if (found >= 0) cell_l[k * Mb + m] = found;
         }
@@ -218,7 +170,7 @@ __global__ __launch_bounds__(kStThreads) void stplan_kernel(DevCar c, DevStplan 
             if (p >= 0 && p != M - 1 && (k > 1 || p == 0) && pre[j + 1] - pre[p] == 0) {
                 const double v = (S_l[j] - S_l[p]) / dt;
                 double cc = Vc_l[p];
-                for (int m = p + 1; m <= j; ++m) cc = stp_min(cc, Vc_l[m]);
+                for (int m = p + 1; m <= j; ++m) cc = ag_min(cc, Vc_l[m]);
                 if (u == 0 || (v > 0 && v <= cc)) {
                     const double dv = cc - v, slow = (a.w_slow * dv) * dv;
                     if (k == 1) {
@@ -288,7 +240,7 @@ __global__ __launch_bounds__(kStThreads) void stplan_kernel(DevCar c, DevStplan 
                     int k = 0;
                     while (k < nl - 1 && !(plan_st[k] <= m && m < plan_st[k + 1])) ++k;  // (station[0] = 0 <= m < station[nl], stations do not decrease)
                     const double V = (S_l[plan_st[k + 1]] - S_l[plan_st[k]]) / dt;
-                    val = L >= 0 ? stp_min(L, V) : V;
+                    val = L >= 0 ? ag_min(L, V) : V;
                 }
             }
             lrow[i] = val;

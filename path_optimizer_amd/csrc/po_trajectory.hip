@@ -9,13 +9,12 @@
 
 #include "../../include/po_hip.h"
 #include "../../include/po_pmath.h"
+#include "po_agents.hpp"  // kAgentWords: a record as 8-byte words
 #include "po_launch.hpp"
 #include "po_map.hpp"
 
 namespace po {
 
-constexpr int kAgentWords = sizeof(po_agent) / 8;  // an agent as 8-byte words: (n_pts, flags), radius, t[8], x[8], y[8]
-static_assert(sizeof(po_agent) == 208 && kAgentWords == 2 + 3 * PO_AGENT_MAX_PTS, "po_agent is written as 26 words");
 static_assert(PO_AGENT_MAX_PTS <= 64, "one lane per agent point");
 
 __device__ __forceinline__ bool trj_finite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN and +-inf

@@ -26,6 +26,25 @@ struct Agent {
     void add(double ti, double xi, double yi) { t.push_back(ti); x.push_back(xi); y.push_back(yi); }  // (one point with both flags: a static disc)
 };
 
+// sets -> the arrays of po_agent_lists: set k owns flat[first[k] .. first[k + 1]).  `who` names the caller ("Class::method") in the exception.
+inline void pack_agent_sets(const std::vector<std::vector<Agent>> &sets, const char *who, std::vector<po_agent> *flat, std::vector<int> *first) {
+    flat->clear();
+    first->assign(1, 0);
+    for (const auto &set : sets) {
+        for (const Agent &a : set) {
+            if (a.t.empty() || a.t.size() > PO_AGENT_MAX_PTS || a.x.size() != a.t.size() || a.y.size() != a.t.size())
+                throw std::invalid_argument(std::string(who) + ": an agent has 1 .. 8 points (t, x, y)");
+            po_agent g{};
+            g.n_pts = (int)a.t.size();
+            g.flags = (a.hold_before ? PO_AGENT_HOLD_BEFORE : 0) | (a.hold_after ? PO_AGENT_HOLD_AFTER : 0);
+            g.radius = a.radius;
+            for (size_t j = 0; j < a.t.size(); ++j) { g.t[j] = a.t[j]; g.x[j] = a.x[j]; g.y[j] = a.y[j]; }
+            flat->push_back(g);
+        }
+        first->push_back((int)flat->size());
+    }
+}
+
 struct DynamicResult {
     std::vector<int> status;                    // [B] 0: not checked, 1: free, 2: conflict, 3: conflict nearer than stop_distance
     std::vector<int> first_state, first_agent;  // [B] the first conflicting interval and its agent (index into the concatenated sets), -1 when free
@@ -68,20 +87,8 @@ public:
                 for (size_t i = 0; i < v_limit_in[b].size() && i < N; ++i) lim[b * N + i] = v_limit_in[b][i];
         }
         std::vector<po_agent> flat;
-        std::vector<int> first(1, 0);
-        for (const auto &set : sets) {
-            for (const Agent &a : set) {
-                if (a.t.empty() || a.t.size() > PO_AGENT_MAX_PTS || a.x.size() != a.t.size() || a.y.size() != a.t.size())
-                    throw std::invalid_argument("DynamicChecker::check: an agent has 1 .. 8 points (t, x, y)");
-                po_agent g{};
-                g.n_pts = (int)a.t.size();
-                g.flags = (a.hold_before ? PO_AGENT_HOLD_BEFORE : 0) | (a.hold_after ? PO_AGENT_HOLD_AFTER : 0);
-                g.radius = a.radius;
-                for (size_t j = 0; j < a.t.size(); ++j) { g.t[j] = a.t[j]; g.x[j] = a.x[j]; g.y[j] = a.y[j]; }
-                flat.push_back(g);
-            }
-            first.push_back((int)flat.size());
-        }
+        std::vector<int> first;
+        pack_agent_sets(sets, "DynamicChecker::check", &flat, &first);
         DynamicResult r;
         r.status.assign(B, 0); r.first_state.assign(B, -1); r.first_agent.assign(B, -1); r.stop_state.assign(B, -1);
         r.first_time.assign(B, 0.0); r.gap_min.assign(B, 0.0); r.gap.resize(B); r.v_limit.resize(B);

@@ -63,20 +63,8 @@ public:
                 for (size_t e = 0; e < side_prev[b].size() && e < W; ++e) prev[b * W + e] = side_prev[b][e];
         }
         std::vector<po_agent> flat;
-        std::vector<int> first(1, 0);
-        for (const auto &set : sets) {
-            for (const Agent &a : set) {
-                if (a.t.empty() || a.t.size() > PO_AGENT_MAX_PTS || a.x.size() != a.t.size() || a.y.size() != a.t.size())
-                    throw std::invalid_argument("CorridorNudger::nudge: an agent has 1 .. 8 points (t, x, y)");
-                po_agent g{};
-                g.n_pts = (int)a.t.size();
-                g.flags = (a.hold_before ? PO_AGENT_HOLD_BEFORE : 0) | (a.hold_after ? PO_AGENT_HOLD_AFTER : 0);
-                g.radius = a.radius;
-                for (size_t j = 0; j < a.t.size(); ++j) { g.t[j] = a.t[j]; g.x[j] = a.x[j]; g.y[j] = a.y[j]; }
-                flat.push_back(g);
-            }
-            first.push_back((int)flat.size());
-        }
+        std::vector<int> first;
+        pack_agent_sets(sets, "CorridorNudger::nudge", &flat, &first);
         Nudge r;
         r.status.assign(B, 0); r.first_blocked_state.assign(B, -1); r.first_blocked_agent.assign(B, -1); r.width_min.assign(B, 0.0);
         r.bounds = bounds; r.side.resize(B);

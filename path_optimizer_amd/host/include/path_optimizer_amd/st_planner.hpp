@@ -61,20 +61,8 @@ public:
                 for (size_t i = 0; i < v_limit_in[b].size() && i < N; ++i) lim[b * N + i] = v_limit_in[b][i];
         }
         std::vector<po_agent> flat;
-        std::vector<int> first(1, 0);
-        for (const auto &set : sets) {
-            for (const Agent &a : set) {
-                if (a.t.empty() || a.t.size() > PO_AGENT_MAX_PTS || a.x.size() != a.t.size() || a.y.size() != a.t.size())
-                    throw std::invalid_argument("StPlanner::plan: an agent has 1 .. 8 points (t, x, y)");
-                po_agent g{};
-                g.n_pts = (int)a.t.size();
-                g.flags = (a.hold_before ? PO_AGENT_HOLD_BEFORE : 0) | (a.hold_after ? PO_AGENT_HOLD_AFTER : 0);
-                g.radius = a.radius;
-                for (size_t j = 0; j < a.t.size(); ++j) { g.t[j] = a.t[j]; g.x[j] = a.x[j]; g.y[j] = a.y[j]; }
-                flat.push_back(g);
-            }
-            first.push_back((int)flat.size());
-        }
+        std::vector<int> first;
+        pack_agent_sets(sets, "StPlanner::plan", &flat, &first);
         StPlan r;
         r.status.assign(B, 0); r.n_layers.assign(B, 0); r.cost.assign(B, 0.0); r.station.resize(B); r.cells.resize(B); r.v_limit.resize(B);
         if (B == 0) return r;

@@ -29,7 +29,7 @@ NEW_ENTRIES = ["po_default_dynamic_params", "po_dynamic_batch", "po_dynamic_batc
 KEYS = ("status", "ok_out", "gap_min", "first_state", "first_agent", "stop_state", "first_time", "gap", "v_limit")
 DBL_MAX = select_ref.DBL_MAX
 BEFORE, AFTER = abi.PO_AGENT_HOLD_BEFORE, abi.PO_AGENT_HOLD_AFTER
-DYN_CHUNK = 32  # kDynChunk of po_dynamic.hip: agents per LDS chunk
+DYN_CHUNK = 32  # kAgentChunk of po_agents.hpp (po_dynamic.hip's chunk): agents per LDS chunk
 # The closed forms.  A gap is reached from the inputs through at most 32 roundings (centre 3, interpolation 2, relative vector 1, difference 1, L2 and dot 3 each,
 # quotient 1, closest point 2 per axis, squares and sum 3, sqrt 1, two subtractions; the window parameters add 2 each), every one on a quantity of magnitude
 # below 64 m (the cases below keep all coordinates inside +-32 m), so below 2^-53 * 64 each.  No cancellation amplifies them: every step is Lipschitz 1 in its inputs
@@ -39,8 +39,8 @@ CLOSED_TOL = 32 * 2.0 ** -53 * 64
 
 def test_boundary_cases_follow_the_kernel_constant():
     """The agent counts below are built from DYN_CHUNK: it must be the kernel's own constant."""
-    src = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_dynamic.hip")).read()
-    assert int(re.search(r"constexpr int kDynChunk = (\d+);", src).group(1)) == DYN_CHUNK
+    agents = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_agents.hpp")).read()
+    assert int(re.search(r"constexpr int kAgentChunk = (\d+);", agents).group(1)) == DYN_CHUNK
 
 
 def same(a, b):

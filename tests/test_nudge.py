@@ -32,14 +32,15 @@ NEW_ENTRIES = ["po_default_nudge_params", "po_nudge_batch", "po_nudge_batch_devi
 KEYS = ("status", "ok_out", "bounds", "side", "first_blocked_state", "first_blocked_agent", "width_min")
 DBL_MAX = select_ref.DBL_MAX
 BEFORE, AFTER = abi.PO_AGENT_HOLD_BEFORE, abi.PO_AGENT_HOLD_AFTER
-NDG_CHUNK, NDG_TRIG = 32, 384  # kNdgChunk, kNdgTrig of po_nudge.hip: agents per LDS chunk, states whose cos / sin are kept in LDS
+NDG_CHUNK, NDG_TRIG = 32, 384  # kAgentChunk of po_agents.hpp, kNdgTrig of po_nudge.hip: agents per LDS chunk, states whose cos / sin are kept in LDS
 GRID_D = (-0.75, 0.75, 2.25, 3.75)
 
 
 def test_boundary_cases_follow_the_kernel_constants():
     """The agent counts and the long path below are built from NDG_CHUNK and NDG_TRIG: they must be the kernel's own constants."""
     src = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_nudge.hip")).read()
-    assert int(re.search(r"constexpr int kNdgChunk = (\d+);", src).group(1)) == NDG_CHUNK
+    agents = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_agents.hpp")).read()
+    assert int(re.search(r"constexpr int kAgentChunk = (\d+);", agents).group(1)) == NDG_CHUNK
     assert int(re.search(r"constexpr int kNdgTrig = (\d+);", src).group(1)) == NDG_TRIG
 
 

@@ -32,14 +32,14 @@ NEW_ENTRIES = ["po_default_stplan_params", "po_stplan_batch", "po_stplan_batch_d
 KEYS = ("status", "ok_out", "n_layers", "cost", "station", "cells", "v_limit")
 DBL_MAX = select_ref.DBL_MAX
 BEFORE, AFTER = abi.PO_AGENT_HOLD_BEFORE, abi.PO_AGENT_HOLD_AFTER
-ST_CHUNK = 32  # kStChunk of po_stplan.hip: agents per LDS chunk
+ST_CHUNK = 32  # kAgentChunk of po_agents.hpp (po_stplan.hip's chunk): agents per LDS chunk
 MAX_M = abi.PO_ST_MAX_STATIONS
 
 
 def test_boundary_cases_follow_the_kernel_constant():
     """The agent counts below are built from ST_CHUNK: it must be the kernel's own constant."""
-    src = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_stplan.hip")).read()
-    assert int(re.search(r"constexpr int kStChunk = (\d+);", src).group(1)) == ST_CHUNK
+    agents = open(os.path.join(ROOT, "path_optimizer_amd", "csrc", "po_agents.hpp")).read()
+    assert int(re.search(r"constexpr int kAgentChunk = (\d+);", agents).group(1)) == ST_CHUNK
 
 
 def same(a, b):

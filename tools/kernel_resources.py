@@ -1,4 +1,4 @@
-"""Dev tool (CPU): registers / spills / scratch of every kernel in the objects libpo_hip.so is LINKED from, read from the gfx950 code object's metadata notes.
+"""Dev tool (CPU): registers / spills / scratch / static LDS of every kernel in the objects libpo_hip.so is LINKED from, read from the gfx950 code object's metadata notes.
 The object list is the Makefile's own (`make -pn` -> the prerequisites of ../libpo_hip.so), not a glob of .build/ — a box with left-over objects of earlier rounds used to
 put 131 rows of kernels that no longer ship into profiles/r5c/kernel_resources.txt.
     python tools/kernel_resources.py [substring of the object name ...]          (needs /opt/rocm/lib/llvm/bin/{llvm-objcopy,llvm-readelf})"""
@@ -59,7 +59,7 @@ def demangle(n):
 
 if __name__ == "__main__":
     pats = sys.argv[1:]
-    print(f"{'object':28s} {'kernel':62s} {'vgpr':>5s} {'agpr':>5s} {'spillV':>6s} {'spillS':>6s} {'scratch B/lane':>14s}")
+    print(f"{'object':28s} {'kernel':62s} {'vgpr':>5s} {'agpr':>5s} {'spillV':>6s} {'spillS':>6s} {'scratch B/lane':>14s} {'LDS B':>7s}")
     for base in sorted(linked_objects()):
         obj = os.path.join(ROOT, "path_optimizer_amd", "csrc", ".build", base)
         if not os.path.exists(obj):
@@ -67,4 +67,4 @@ if __name__ == "__main__":
         if pats and not any(p in base for p in pats):
             continue
         for k in kernels_of(obj):
-            print(f"{base:28s} {demangle(k['name'])[:62]:62s} {k.get('vgpr_count', '?'):>5s} {k.get('agpr_count', '?'):>5s} {k.get('vgpr_spill_count', '?'):>6s} {k.get('sgpr_spill_count', '?'):>6s} {k.get('private_segment_fixed_size', '?'):>14s}")
+            print(f"{base:28s} {demangle(k['name'])[:62]:62s} {k.get('vgpr_count', '?'):>5s} {k.get('agpr_count', '?'):>5s} {k.get('vgpr_spill_count', '?'):>6s} {k.get('sgpr_spill_count', '?'):>6s} {k.get('private_segment_fixed_size', '?'):>14s} {k.get('group_segment_fixed_size', '?'):>7s}")
