@@ -273,6 +273,10 @@ int po_device_count(void);
  * entry takes the handle's inner lock while it enqueues, owns no staging, and its scratch is ordered by the stream.  The library orders the calls; every call returns
  * what it would return in SOME serial order of the calls, i.e. what the same call returns on a handle nobody else uses (results do not depend on what a handle ran
  * before: tests/test_handle_contract.py).  Two calls on one handle never overlap on the device — use two handles for that.
+ * Stream capture: after one eager warm-up call of the same shape on the handle (a handle does not allocate during capture; po_select_batch_device grows its scratch in
+ * that call), po_solve_batch_device, po_speed_batch_device, po_trajectory_batch_device, po_dynamic_batch_device, po_stplan_batch_device, po_nudge_batch_device and
+ * po_select_batch_device only enqueue and may be captured into a graph on the handle's stream, alone or as a chain; po_plan_batch_device synchronises the stream between
+ * its groups and may NOT be captured.
  * NOT guaranteed: a thread that calls po_set_stream / po_set_map / po_set_map_occupancy* / po_set_map_stack* (po_set_map_stack_obstacles* and po_set_map_stack_scene* included) / po_set_world_occupancy* /
  * po_set_map_assignment* / po_debug_set while other threads solve on the same handle gets what it asked for — calls that
  * start afterwards use the new stream / map / switch, and the caller orders what is already enqueued on the old stream.  po_last_kernel_ms / po_last_phase_ms
