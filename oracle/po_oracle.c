@@ -1214,7 +1214,7 @@ resume_main:
              * its rounding alone (1e-16 x 1e6 x the unscaling) sits above the dual tolerance */
             double rb_in = rn_, pri_outer = -1.0;
             double rb_eq = prm->refine_newton_rho_eq > 0 ? (prm->refine_newton_rho_eq < 1e8 ? prm->refine_newton_rho_eq : 1e8) : 1e4;
-            /* the caps, defaulted and bounded exactly as the engine's make_dev_params does (csrc/po_capi.cpp): 0 in refine_newton_rho_eq_max is the documented "never grows" */
+            /* the caps, defaulted and bounded exactly as the engine's make_dev_params does (csrc/po_solve.cpp): 0 in refine_newton_rho_eq_max is the documented "never grows" */
             const double in_cap = prm->refine_newton_rho_max > 0 ? (prm->refine_newton_rho_max < OSQP_RHO_MAX ? prm->refine_newton_rho_max : OSQP_RHO_MAX) : 1e5;
             const double eq_cap = prm->refine_newton_rho_eq_max > 0 ? (prm->refine_newton_rho_eq_max < 1e8 ? prm->refine_newton_rho_eq_max : 1e8) : (prm->refine_newton_rho_eq_max < 0 ? 1e6 : 0.0); /* (below rb_eq: never grows) */
             const int cap_nw = prm->refine_newton_max > 0 ? prm->refine_newton_max : 300;

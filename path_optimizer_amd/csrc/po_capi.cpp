@@ -1,9 +1,8 @@
 // po_capi.cpp — the C ABI of libpo_hip.so (include/po_hip.h): handle management, host<->device staging,
-// kernel launches.  No torch types, no oracle, no CPU fallback: every entry point that computes runs the HIP
+// kernel launches (the solve entries: po_solve.cpp; the plan chain: po_plan.cpp).  No torch types, no oracle, no CPU fallback: every entry point that computes runs the HIP
 // kernels or returns an error code.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -14,37 +13,15 @@
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/po_hip.h"
-#include "po_device.hpp"
 #include "po_handle.hpp"
 #include "po_launch.hpp"
 #include "po_map.hpp"
 #include "po_smooth.hpp"
 
-namespace {
-thread_local std::string g_hip_err;
-struct CopySeg { char *dst; const char *src; size_t bytes; };
-// memcpy of a list of segments on `nthr` host threads (pieces of <= 2 MB handed out round-robin: every thread streams through every array)
-void parallel_copy(const std::vector<CopySeg> &segs, int nthr) {
-    std::vector<CopySeg> pieces;
-    const size_t kPiece = (size_t)2 << 20;
-    for (const CopySeg &sg : segs)
-        for (size_t o = 0; o < sg.bytes; o += kPiece) pieces.push_back({sg.dst + o, sg.src + o, std::min(kPiece, sg.bytes - o)});
-    if (nthr <= 1 || pieces.size() <= 1) {
-        for (const CopySeg &pc : pieces) std::memcpy(pc.dst, pc.src, pc.bytes);
-        return;
-    }
-    nthr = (int)std::min<size_t>((size_t)nthr, pieces.size());
-    std::vector<std::thread> th;
-    for (int t = 1; t < nthr; ++t)
-        th.emplace_back([&pieces, t, nthr] { for (size_t i = (size_t)t; i < pieces.size(); i += (size_t)nthr) std::memcpy(pieces[i].dst, pieces[i].src, pieces[i].bytes); });
-    for (size_t i = 0; i < pieces.size(); i += (size_t)nthr) std::memcpy(pieces[i].dst, pieces[i].src, pieces[i].bytes);
-    for (std::thread &t : th) t.join();
-}
-}  // namespace
+static thread_local std::string g_hip_err;
 
 bool hip_ok(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
@@ -277,408 +254,6 @@ int po_set_stream(po_handle h, void *hip_stream) {
     if (!h) return PO_ERR_INVALID;
     Lock g(h->mu);
     h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream.s;
-    return PO_OK;
-}
-
-static int make_dev_params(const po_handle_s *h, int form, int keep, po::DevParams *D) {
-    const po_params &p = h->params;
-    D->d1 = p.d[0]; D->d2 = p.d[1]; D->d3 = p.d[2]; D->d4 = p.d[3];
-    if (form == PO_K) {
-        D->w_dev = p.k_w_dev; D->w_c = p.k_w_curv; D->w_cr = p.k_w_curv_rate; D->w_s1 = p.w_slack; D->w_s2 = 0; D->w_u = 0; D->w_su = 0;
-    } else {
-        D->w_dev = p.w_dev; D->w_c = p.w_curv; D->w_cr = p.w_curv_rate; D->w_s1 = p.w_slack;
-        D->w_s2 = (form == PO_KPC) ? p.w_k_slack : 0.0;
-        D->w_u = keep * p.w_curv_rate;
-        D->w_su = (form == PO_KPC) ? p.w_kp_slack * keep : 0.0;
-    }
-    D->margin = p.margin;
-    D->kmax = std::tan(p.max_steer) / p.wheel_base;
-    D->max_steer = p.max_steer;
-    D->wheel_base = p.wheel_base;
-    D->sigma = p.sigma; D->alpha = p.alpha; D->rho0 = p.rho0; D->eps_abs = p.eps_abs; D->eps_rel = p.eps_rel;
-    D->eps_pinf = p.eps_prim_inf; D->adapt_tol = p.adapt_tol;
-    D->max_iter = p.max_iter; D->check_every = p.check_every; D->adapt_every = p.adapt_every;
-    D->end_heading = p.constraint_end_heading;
-    D->polish = p.polish; D->pol_delta = p.polish_delta > 0 ? p.polish_delta : 1e-6; D->pol_refine = p.polish_refine_iter < 0 ? 0 : p.polish_refine_iter;
-    D->refine = p.refine; D->ref_eps = p.refine_eps; D->ref_rounds = p.refine_rounds;
-    D->ref_extra = (p.refine && p.refine_extra_rounds > 0) ? p.refine_extra_rounds : 0;
-    // every refine_newton_* field is defaulted when it is not positive (a zero-initialised po_params must not silently disable the penalty growth) and held inside what
-    // the rest of the engine allows; the ESCALATED caps (refine_newton_escalate: up to 100 x) are clamped inside the phase to kRhoMax / 1e8 (po_fast.inc, oracle alike)
-    D->ref_nw_rho = p.refine_newton_rho > 0 ? std::min(p.refine_newton_rho, po::kRhoMax) : 100.0;
-    D->ref_nw_rho_eq = p.refine_newton_rho_eq > 0 ? std::min(p.refine_newton_rho_eq, 1e8) : 1e4;
-    D->ref_nw_rho_max = p.refine_newton_rho_max > 0 ? std::min(p.refine_newton_rho_max, po::kRhoMax) : 1e5;
-    D->ref_nw_rho_eq_max = p.refine_newton_rho_eq_max > 0 ? std::min(p.refine_newton_rho_eq_max, 1e8) : (p.refine_newton_rho_eq_max < 0 ? 1e6 : 0.0);  // 0: the equality penalty never grows (documented switch)
-    D->ref_ls_tol = p.refine_ls_tol > 0 ? p.refine_ls_tol : 1e-4;
-    D->ref_nw_final = p.refine_newton_final; D->ref_nw_esc = p.refine_newton_escalate; D->ref_nw_slice = 0; D->ref_ls_max = p.refine_ls_max > 0 ? p.refine_ls_max : 30; D->ref_nw_max = p.refine_newton_max > 0 ? p.refine_newton_max : 300;
-    return PO_OK;
-}
-
-static int validate(const po_batch_in *in, int *n, int *m, int *C) {
-    if (!in) return PO_ERR_INVALID;
-    if (in->B < 0) return PO_ERR_INVALID;
-    int rc = po_problem_dims(in->formulation, in->N, in->keep, n, m, C);
-    if (rc) return rc;
-    if (!in->ref_x || !in->ref_y || !in->ref_z || !in->ref_k || !in->ref_s || !in->bounds || !in->x0 || !in->goal_z) return PO_ERR_INVALID;
-    if (in->formulation == PO_KPC && (!in->max_k || !in->max_kp)) return PO_ERR_INVALID;
-    if (po_lds_bytes(in->formulation, in->N, *C, in->keep) > 160 * 1024) return PO_ERR_UNSUPPORTED;
-    return PO_OK;
-}
-
-static void fill_dev_batch(const po_handle_s *h, po::DevBatch *D, const po_batch_in *in, const po_batch_out *out, int n, int m, int C) PO_REQUIRES(h->mu) {
-    D->B = in->B; D->N = in->N; D->keep = in->keep; D->C = C;
-    D->ref_x = in->ref_x; D->ref_y = in->ref_y; D->ref_z = in->ref_z; D->ref_k = in->ref_k; D->ref_s = in->ref_s;
-    D->bounds = in->bounds; D->x0 = in->x0; D->goal_z = in->goal_z; D->max_k = in->max_k; D->max_kp = in->max_kp;
-    D->n_points = in->n_points;
-    D->order = in->order;
-    D->out_states = out ? out->states : nullptr;
-    D->out_info = out ? out->info : nullptr;
-    D->out_x = out ? out->x : nullptr;
-    D->dbg_cycles = nullptr;
-    D->only_deferred = 0;
-    D->perm_bits = 0;  // block -> path permutation (po_debug_set "identity_order": blockIdx order, dev tool)
-    if (!h->env_identity && in->B > 8)
-        while ((1 << D->perm_bits) < in->B) ++D->perm_bits;
-    D->scale = nullptr;
-    D->pol_state = nullptr; D->pol_stride = 0;
-    D->round = 0;
-    D->fb_list = nullptr;
-    D->nw_phase = 0; D->nw_state = nullptr; D->nw_stride = 0; D->nw_keys = nullptr; D->nw_list = nullptr;
-    D->nw_follows = 0;
-    D->fixed_len = (h->fixed_length && !in->n_points && po_has_fixed_length(in->formulation, in->N, C, in->keep)) ? 1 : 0;
-    D->n = n; D->m = m;
-}
-
-int po_solve_batch_device(po_handle h, const po_batch_in *in, const po_batch_out *out) {
-    if (!h || !out || !out->states || !out->info) return PO_ERR_INVALID;
-    int n, m, C;
-    int rc = validate(in, &n, &m, &C);
-    if (rc) return rc;
-    if (in->B == 0) return PO_OK;
-    Lock g(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
-    h->timed_host = false;  // (set again by po_solve_batch when this call is its inner solve: po_last_phase_ms never mixes this solve's events with an older call's)
-    po::DevParams P;
-    make_dev_params(h, in->formulation, in->keep, &P);
-    po::DevBatch D;
-    fill_dev_batch(h, &D, in, out, n, m, C);
-    const bool dbg = h->env_cycles;
-    if (dbg) {
-        if ((rc = h->dbg_buf.ensure(sizeof(long long) * 16 * (size_t)in->B))) return rc;
-        D.dbg_cycles = static_cast<long long *>(h->dbg_buf.p);
-        HIP_TRY(hipMemsetAsync(D.dbg_cycles, 0, sizeof(long long) * 16 * (size_t)in->B, h->stream));
-    }
-    if ((rc = h->scale_buf.ensure(sizeof(double) * 64 * (size_t)in->B))) return rc;
-    D.scale = static_cast<double *>(h->scale_buf.p);
-    h->fixed_used = D.fixed_len;
-    bool polish = false;
-    if (h->params.polish || h->params.refine) {  // OSQP's polish (opt-in) and the Newton refinement pick the ADMM state up from pol_buf, where the solve kernels leave it
-        const int sd = po_polish_state_doubles(in->formulation, in->N, C, in->keep);
-        if (sd > 0) {  // (shapes on the single-level mapping have neither kernel: status_polish / status_refine = PO_NOT_AVAILABLE, see below)
-            if ((rc = h->pol_buf.ensure(sizeof(double) * (size_t)sd * (size_t)in->B))) return rc;
-            D.pol_state = static_cast<double *>(h->pol_buf.p);
-            D.pol_stride = sd;
-            polish = h->params.polish && po_has_polish_kernel(in->formulation, in->N, C, in->keep);  // (role-split shapes, keep 6 .. 16: no polish kernel -> status_polish = PO_NOT_AVAILABLE)
-        }
-    }
-    const int rounds_total = (h->params.refine_rounds > 1 ? h->params.refine_rounds : 1) + P.ref_extra;
-    // refine = 2: plain warm-start launches, the Newton refinement as its own launch, then the (nearly always empty) fallback launch for the later rounds
-    const bool split = h->params.refine == 2 && D.pol_state != nullptr && rounds_total < 32;
-    if (split && ((rc = h->fb_buf.ensure(sizeof(int) * ((size_t)in->B + 1))) || (rc = h->fb_host.ensure(64)))) return rc;
-    int pd = 0;  // doubles of a path's parking block when the Newton launch is sliced, else 0
-    if (split) {
-        // SLICED LAUNCHES (engine-internal scheduling): the Newton launch is two — every path for nw_slice steps, the unfinished ones parked with a
-        // priority key; a one-workgroup sort; the parked paths in order of expected remaining work, longest first.  One launch in engine order ends on a tail of a few
-        // long paths (30 % of it on BASELINE config 3).  The operations and their order are unchanged: statuses and certificates do not depend on the slicing, solutions agree to round-off.
-        // Left alone the engine slices where it was measured to pay: one wave per path (NT = 64: 4 x CUs paths at a time) and at least two rounds of them — BASELINE config 3
-        // 4.76 -> 4.06 ms, K 5.41 -> 4.85, keep 8 6.15 -> 5.75, 2 048 paths of config 3 2.62 -> 2.53; two-wave shapes gain or lose 1 % (keep 2 / 3) or lose 10 % (KPC at N = 400:
-        // eight rounds, the re-entry of a 2 x 36 KB state per path), a batch of one round has no queueing tail to remove (config 2: + 10 % for the re-entry).
-        const bool slice_auto = in->B >= 2 * h->wave_slots && po_shape_threads(in->formulation, in->N, C, in->keep) == 64;
-        pd = (h->nw_slice > 0 && (slice_auto || h->nw_slice_forced)) ? po_newton_park_doubles(in->formulation, in->N, C, in->keep) : 0;
-        // (the parking blocks are 39 KB per path on top of the state block: a batch they do not fit beside is solved unsliced — scheduling is not worth an out-of-memory error)
-        if (pd > 0 && (h->nw_state_buf.ensure(sizeof(double) * (size_t)pd * (size_t)in->B) || h->nw_idx_buf.ensure(sizeof(int) * (2 * (size_t)in->B + 1)))) {
-            (void)hipGetLastError();
-            h->nw_state_buf.release();
-            pd = 0;
-        }
-        h->nw_last_B = pd > 0 ? in->B : 0;
-    }
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    h->timed_phases = false;
-    // per-path equilibration (h->params.scaling class-level Ruiz passes; 0 -> identity), then the fused solve.  The same launch resets what the Newton launches count in:
-    // the fall-back work list's count, and the park keys to -1 (a path no workgroup of the first sliced launch reaches — a malformed caller-side order — is not parked)
-    HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, static_cast<double *>(h->scale_buf.p), pd > 0 ? static_cast<int *>(h->nw_idx_buf.p) : nullptr,
-                            split ? static_cast<int *>(h->fb_buf.p) : nullptr, h->stream));
-    if (split) {
-        po::DevParams P1 = P;  // the warm start: the plain solve kernels, stopped where round 0 of the rounds stops (10^(R-1) x eps)
-        for (int r = 1; r < (h->params.refine_rounds > 1 ? h->params.refine_rounds : 1); ++r) { P1.eps_abs *= 10.0; P1.eps_rel *= 10.0; }
-        D.nw_follows = 1;  // (newton_kernel writes the outputs of the paths this launch reports SOLVED)
-        HIP_TRY(po_launch_solve(in->formulation, &D, &P1, h->stream, nullptr));
-        D.nw_follows = 0;
-        HIP_TRY(hipEventRecord(h->evp[0], h->stream));
-        D.fb_list = static_cast<int *>(h->fb_buf.p);  // (its count: zeroed by scale_kernel)
-        if (pd > 0) {
-            D.nw_state = static_cast<double *>(h->nw_state_buf.p); D.nw_stride = pd;
-            D.nw_keys = static_cast<int *>(h->nw_idx_buf.p); D.nw_list = D.nw_keys + in->B;
-            P.ref_nw_slice = h->nw_slice;
-            D.nw_phase = 1;
-            HIP_TRY(po_launch_newton(in->formulation, &D, &P, h->stream));
-            HIP_TRY(po_launch_nw_sort(D.nw_keys, in->B, D.nw_list, h->stream));
-            D.nw_phase = 2;
-            HIP_TRY(po_launch_newton(in->formulation, &D, &P, h->stream));
-            D.nw_phase = 0;
-        } else {
-            HIP_TRY(po_launch_newton(in->formulation, &D, &P, h->stream));
-        }
-        HIP_TRY(hipEventRecord(h->evp[1], h->stream));
-        h->timed_phases = true;
-        // The paths newton_kernel did not certify (rare) are on a device-side work list; newton_fallback_kernel takes them through the later rounds.  Its launch alone
-        // costs 0.5 ms whatever its grid (1.2 KB of private segment per lane: the runtime re-provisions scratch for it; 7 % of a BASELINE config-3 solve), so
-        // refine_chain = 2 reads the 4-byte count back and launches it only when there is something on the list — the call then returns when the Newton launch has
-        // finished (it blocks).  refine_chain = 3: always launched, the call stays asynchronous.
-        bool need_fb = true;
-        // a stream that is being captured cannot be waited on (the copy below would never run and a synchronise invalidates the capture): always issue the launch then
-        hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-        const bool capturing = hipStreamIsCapturing(h->stream, &cap_st) == hipSuccess && cap_st != hipStreamCaptureStatusNone;
-        if (h->params.refine_chain != 3 && !capturing) {
-            // the count lands in a pinned word the host SPINS on: a blocking hipStreamSynchronize wakes up through an interrupt — measured 0.5 ms, what the launch it
-            // is meant to save costs; falls back to the blocking wait after 20 ms of spinning (a long solve: the wake-up latency no longer matters)
-            volatile int *cnt = static_cast<volatile int *>(h->fb_host.p);
-            *cnt = -1;
-            HIP_TRY(hipMemcpyAsync(const_cast<int *>(cnt), D.fb_list, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            const auto ts0 = std::chrono::steady_clock::now();
-            unsigned spins = 0;
-            while (*cnt == -1) {
-                if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - ts0 > std::chrono::milliseconds(20)) { HIP_TRY(hipStreamSynchronize(h->stream)); break; }
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();
-#else
-                std::this_thread::yield();
-#endif
-            }
-            need_fb = *cnt != 0;
-        }
-        if (need_fb) HIP_TRY(po_launch_newton_fallback(in->formulation, &D, &P, h->stream));
-    } else {
-        HIP_TRY(po_launch_solve(in->formulation, &D, &P, h->stream, nullptr));
-    }
-    if (split) HIP_TRY(po_launch_finalize_status(D.out_info, in->B, h->stream));
-    if (polish) HIP_TRY(po_launch_polish(in->formulation, &D, &P, h->stream));
-    {   // asked for, but this shape has no kernel for it: say so per path (PO_NOT_AVAILABLE) instead of leaving the "off" value 0
-        const int no_refine = h->params.refine == 2 && !split, no_polish = h->params.polish && !polish;
-        if (no_refine || no_polish) HIP_TRY(po_launch_mark_unavailable(D.out_info, in->B, no_refine, no_polish, h->stream));
-    }
-    HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    if (dbg) {
-        long long c4[16];
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(hipMemcpy(c4, D.dbg_cycles, sizeof(c4), hipMemcpyDeviceToHost));
-        {   // batch totals of the factorisation counters
-            std::vector<long long> all(16 * (size_t)in->B);
-            HIP_TRY(hipMemcpy(all.data(), D.dbg_cycles, sizeof(long long) * all.size(), hipMemcpyDeviceToHost));
-            long long nf = 0, nb = 0;
-            double worst = 0;
-            for (int b = 0; b < in->B; ++b) {
-                nf += all[16 * (size_t)b + 13]; nb += all[16 * (size_t)b + 14];
-                double w; std::memcpy(&w, &all[16 * (size_t)b + 15], sizeof(w)); worst = std::fmax(worst, w);
-            }
-            std::fprintf(stderr, "[po] batch of %d (form %d, N %d, keep %d): %lld scan factorisations, %lld fell back to the sequential chain; worst relative disagreement scan vs recursion %.3e\n", in->B, in->formulation, in->N, in->keep, nf, nb, worst);
-        }
-        std::fprintf(stderr, "[po] path0 cycles: rhs %lld solve %lld update %lld over %lld iterations | solve phases F1 %lld F2 %lld F3B1 %lld B2 %lld B3 %lld | first factorisation: blocks %lld chain %lld | uniform row classes %lld | scan factorisations %lld, fell back to the sequential chain %lld\n",
-                     c4[0], c4[1], c4[2], c4[3], c4[4], c4[5], c4[6], c4[7], c4[8], c4[10], c4[11], c4[12], c4[13], c4[14]);
-    }
-    return PO_OK;
-}
-
-int po_solve_batch(po_handle h, const po_batch_in *in, const po_batch_out *out) {
-    if (!h || !out || !out->states || !out->info) return PO_ERR_INVALID;
-    int n, m, C;
-    int rc = validate(in, &n, &m, &C);
-    if (rc) return rc;
-    if (in->B == 0) return PO_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = in->B, N = in->N;
-    const bool kpc = in->formulation == PO_KPC;
-    // one staging block: 5 ref arrays + bounds(8) + (max_k, max_kp) per point, x0(3) + goal per path, then n_points / order (ints)
-    const size_t per_pt = 13 + (kpc ? 2 : 0);
-    if (in->n_points)
-        for (size_t b = 0; b < B; ++b)
-            if (in->n_points[b] < 2 || in->n_points[b] > in->N) return PO_ERR_INVALID;
-    if (in->order) {  // scheduling hint: must be a permutation (checked here; the device-pointer entry trusts its caller)
-        std::vector<char> seen(B, 0);
-        for (size_t b = 0; b < B; ++b) {
-            const int v = in->order[b];
-            if (v < 0 || (size_t)v >= B || seen[(size_t)v]) return PO_ERR_INVALID;
-            seen[(size_t)v] = 1;
-        }
-    }
-    const size_t in_bytes = sizeof(double) * (B * N * per_pt + B * 4 + 2 * ((B + 1) / 2 + 1));
-    const size_t out_bytes = sizeof(double) * (B * N * 5 + (out->x ? B * (size_t)n : 0)) + sizeof(po_info) * B;
-    Lock call(h->call_mu);  // the call lock, as in staged_call (po_handle.hpp); mu is NOT held while the host threads pack and unpack
-    hipStream_t st;
-    int nthr;
-    {
-        Lock g(h->mu);
-        if ((rc = h->in_buf.ensure(in_bytes)) || (rc = h->out_buf.ensure(out_bytes)) || (rc = h->pin_in.ensure(in_bytes)) || (rc = h->pin_out.ensure(out_bytes))) return rc;
-        st = h->stream;
-        nthr = h->host_threads > 0 ? h->host_threads : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-    }
-    // ---- pack: caller's (pageable) arrays -> the pinned block, on several host threads; the block goes to the device in slices as they fill ----
-    double *d = static_cast<double *>(h->in_buf.p);
-    char *pin = static_cast<char *>(h->pin_in.p);
-    po_batch_in din = *in;
-    std::vector<CopySeg> segs;
-    size_t o = 0;
-    auto up = [&](const double *src, size_t cnt, const double **dst) {
-        *dst = d + o;
-        segs.push_back({pin + o * sizeof(double), reinterpret_cast<const char *>(src), cnt * sizeof(double)});
-        o += cnt;
-    };
-    up(in->ref_x, B * N, &din.ref_x); up(in->ref_y, B * N, &din.ref_y); up(in->ref_z, B * N, &din.ref_z); up(in->ref_k, B * N, &din.ref_k); up(in->ref_s, B * N, &din.ref_s);
-    up(in->bounds, B * N * 8, &din.bounds); up(in->x0, B * 3, &din.x0); up(in->goal_z, B, &din.goal_z);
-    if (kpc) { up(in->max_k, B * N, &din.max_k); up(in->max_kp, B * N, &din.max_kp); }
-    size_t used = o * sizeof(double);
-    if (in->n_points) {
-        segs.push_back({pin + o * sizeof(double), reinterpret_cast<const char *>(in->n_points), sizeof(int) * B});
-        din.n_points = reinterpret_cast<const int *>(d + o);
-        used = o * sizeof(double) + sizeof(int) * B;
-    }
-    if (in->order) {
-        const size_t oo = o * sizeof(double) + sizeof(int) * ((B + 1) / 2) * 2;
-        segs.push_back({pin + oo, reinterpret_cast<const char *>(in->order), sizeof(int) * B});
-        din.order = reinterpret_cast<const int *>(reinterpret_cast<char *>(d) + oo);
-        used = oo + sizeof(int) * B;
-    }
-    double pack_ms, unpack_ms;
-    HIP_TRY(hipEventRecord(h->evh[0], st));
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        // the block in slices of 32 MB: slice k is on its way over PCIe while slice k + 1 is being packed (gaps between the int arrays travel as they are)
-        const size_t kSlice = (size_t)32 << 20;
-        for (size_t lo = 0; lo < used; lo += kSlice) {
-            const size_t hi = std::min(used, lo + kSlice);
-            std::vector<CopySeg> cur;
-            for (const CopySeg &sg : segs) {
-                const size_t s0 = (size_t)(sg.dst - pin), s1 = s0 + sg.bytes;
-                const size_t a0 = std::max(s0, lo), a1 = std::min(s1, hi);
-                if (a0 < a1) cur.push_back({pin + a0, sg.src + (a0 - s0), a1 - a0});
-            }
-            parallel_copy(cur, nthr);
-            HIP_TRY(hipMemcpyAsync(reinterpret_cast<char *>(d) + lo, pin + lo, hi - lo, hipMemcpyHostToDevice, st));
-        }
-        pack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    HIP_TRY(hipEventRecord(h->evh[1], st));
-    po_batch_out dout;
-    char *ob = static_cast<char *>(h->out_buf.p);
-    dout.states = reinterpret_cast<double *>(ob);
-    dout.x = out->x ? dout.states + B * N * 5 : nullptr;
-    dout.info = reinterpret_cast<po_info *>(ob + sizeof(double) * (B * N * 5 + (out->x ? B * (size_t)n : 0)));
-    rc = po_solve_batch_device(h, &din, &dout);
-    if (rc) return rc;
-    // ---- D2H into the pinned block (one copy), then unpack on the host threads ----
-    char *pout = static_cast<char *>(h->pin_out.p);
-    HIP_TRY(hipMemcpyAsync(pout, ob, out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(h->evh[2], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<CopySeg> us;
-        us.push_back({reinterpret_cast<char *>(out->states), pout, sizeof(double) * B * N * 5});
-        if (out->x) us.push_back({reinterpret_cast<char *>(out->x), pout + sizeof(double) * B * N * 5, sizeof(double) * B * (size_t)n});
-        us.push_back({reinterpret_cast<char *>(out->info), pout + sizeof(double) * (B * N * 5 + (out->x ? B * (size_t)n : 0)), sizeof(po_info) * B});
-        parallel_copy(us, nthr);
-        unpack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    Lock g(h->mu);
-    h->host_pack_ms = pack_ms; h->host_unpack_ms = unpack_ms;
-    h->timed_host = true;
-    return PO_OK;
-}
-
-// What the last po_solve_batch (host pointers) spent where, ms: [0] pack + H2D (stream time from the start of the call to the last H2D slice: the pack runs
-// under the copies), [1] the solve (= po_last_kernel_ms), [2] D2H, [3] host pack alone (wall), [4] host unpack (wall).  And, for the split scheduling of
-// refine = 2, the solve's own phases: [5] equilibration + warm-start launches, [6] the Newton launch, [7] the per-round fallback launches + status sweep (0 otherwise).
-int po_last_phase_ms(po_handle h, float *ms8) {
-    if (!h || !ms8) return PO_ERR_INVALID;
-    Lock g(h->mu);
-    if (!h->timed) return PO_ERR_INVALID;
-    for (int i = 0; i < 8; ++i) ms8[i] = 0.0f;
-    HIP_TRY(hipEventSynchronize(h->ev1));
-    HIP_TRY(hipEventElapsedTime(&ms8[1], h->ev0, h->ev1));
-    if (h->timed_host) {
-        HIP_TRY(hipEventSynchronize(h->evh[2]));
-        HIP_TRY(hipEventElapsedTime(&ms8[0], h->evh[0], h->evh[1]));
-        HIP_TRY(hipEventElapsedTime(&ms8[2], h->ev1, h->evh[2]));
-        ms8[3] = (float)h->host_pack_ms; ms8[4] = (float)h->host_unpack_ms;
-    }
-    if (h->timed_phases) {
-        HIP_TRY(hipEventElapsedTime(&ms8[5], h->ev0, h->evp[0]));
-        HIP_TRY(hipEventElapsedTime(&ms8[6], h->evp[0], h->evp[1]));
-        HIP_TRY(hipEventElapsedTime(&ms8[7], h->evp[1], h->ev1));
-    }
-    return PO_OK;
-}
-
-int po_assemble_batch(po_handle h, const po_batch_in *in, double *l, double *u, double *dyn) {
-    if (!h || !l || !u || !dyn) return PO_ERR_INVALID;
-    if (in && in->n_points) return PO_ERR_INVALID;  // diagnostics work on uniform batches only
-    int n, m, C;
-    int rc = validate(in, &n, &m, &C);
-    if (rc) return rc;
-    if (in->B == 0) return PO_OK;
-    const size_t B = in->B, N = in->N;
-    const bool kpc = in->formulation == PO_KPC;
-    Stage S;  // the inputs, then the three outputs side by side
-    const Slot<double> rx = S.in(in->ref_x, B * N), ry = S.in(in->ref_y, B * N), rz = S.in(in->ref_z, B * N), rk = S.in(in->ref_k, B * N), rs = S.in(in->ref_s, B * N);
-    const Slot<double> bd = S.in(in->bounds, B * N * 8), x0 = S.in(in->x0, B * 3), gz = S.in(in->goal_z, B);
-    const Slot<double> mk = S.in(kpc ? in->max_k : nullptr, B * N), mkp = S.in(kpc ? in->max_kp : nullptr, B * N);
-    const size_t out_from = (S.bytes() + 15) & ~(size_t)15;  // where dl will start
-    const Slot<double> dl = S.out(l, B * (size_t)m), du = S.out(u, B * (size_t)m), dd = S.out(dyn, B * (N - 1) * 3);
-    return staged_call(h, S, &po_handle_s::asm_buf, false, [&]() -> int {  // (no device twin: the launch itself, under mu like one)
-        Lock g(h->mu);
-        po_batch_in din = *in;
-        din.ref_x = rx; din.ref_y = ry; din.ref_z = rz; din.ref_k = rk; din.ref_s = rs; din.bounds = bd; din.x0 = x0; din.goal_z = gz;
-        if (kpc) { din.max_k = mk; din.max_kp = mkp; }
-        HIP_TRY(hipMemsetAsync(dl, 0, S.bytes() - out_from, h->stream));
-        po::DevParams P;
-        make_dev_params(h, in->formulation, in->keep, &P);
-        po::DevBatch D;
-        fill_dev_batch(h, &D, &din, nullptr, n, m, C);
-        HIP_TRY(po_launch_assemble(in->formulation, &D, &P, dl, du, dd, h->stream));
-        return PO_OK;
-    });
-}
-
-int po_scaling_batch(po_handle h, const po_batch_in *in, double *out) {
-    if (!h || !out) return PO_ERR_INVALID;
-    if (in && in->n_points) return PO_ERR_INVALID;  // diagnostics work on uniform batches only
-    int n, m, C;
-    int rc = validate(in, &n, &m, &C);
-    if (rc) return rc;
-    if (in->B == 0) return PO_OK;
-    const size_t B = in->B, N = in->N;
-    Stage S;
-    const Slot<double> rs = S.in(in->ref_s, B * N), sc = S.out(out, 64 * B);
-    return staged_call(h, S, &po_handle_s::asm_buf, false, [&]() -> int {  // (no device twin: the launch itself, under mu like one)
-        Lock g(h->mu);
-        po_batch_in din = *in;
-        din.ref_s = rs;
-        po::DevParams P;
-        make_dev_params(h, in->formulation, in->keep, &P);
-        po::DevBatch D;
-        fill_dev_batch(h, &D, &din, nullptr, n, m, C);
-        HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, sc, nullptr, nullptr, h->stream));  // (diagnostic: no solve follows, nothing to reset)
-        return PO_OK;
-    });
-}
-
-int po_last_kernel_ms(po_handle h, float *ms) {
-    if (!h || !ms) return PO_ERR_INVALID;
-    Lock g(h->mu);
-    if (!h->timed) return PO_ERR_INVALID;
-    HIP_TRY(hipEventSynchronize(h->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
     return PO_OK;
 }
 

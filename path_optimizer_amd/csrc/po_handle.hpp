@@ -1,4 +1,4 @@
-// po_handle.hpp — what the two host files of libpo_hip.so (po_capi.cpp, po_plan.cpp) share: error plumbing, the owning buffers, the annotated locks, the handle, the
+// po_handle.hpp — what the host files of libpo_hip.so (po_capi.cpp, po_solve.cpp, po_plan.cpp) share: error plumbing, the owning buffers, the annotated locks, the handle, the
 // staging helper of the host-pointer entries (Stage), the one staged call they all make and the spline argument check.  Private: not part of include/po_hip.h, and
 // nothing here is exported (hidden visibility).
 #pragma once
@@ -193,6 +193,11 @@ public:
     template <typename T> Slot<T> out_opt(T *host, size_t n) { return host ? out(host, n) : Slot<T>{}; }
     template <typename T> Slot<T> scratch(size_t n) { return add<T>(n, nullptr, nullptr); }
     size_t bytes() const { return bytes_; }
+    // f(offset, bytes, host source or nullptr, host destination or nullptr) for every declared array, in order: for an entry that moves the block itself and keeps a
+    // mirror of it at the same offsets (po_solve_batch: its pinned blocks and pipelined copy)
+    template <typename F> void each(F f) const {
+        for (const Item &it : items_) f(it.off, it.bytes, it.src, it.dst);
+    }
     int reserve(po_handle h, DevBuf &buf, bool after_sync = false) PO_REQUIRES(h->mu) {
         PO_TRY(after_sync ? grow_after_sync(h, buf, bytes_) : buf.ensure(bytes_));
         base_ = static_cast<char *>(buf.p);

@@ -5,9 +5,10 @@
 //                                   in ONE launch, per-path state resident in VGPRs / LDS
 //   assemble_kernel                 diagnostic: the assembled bounds / data-dependent A entries in the
 //                                   reference row order, for bit-exact comparison with the oracle
-// and the DISPATCHER of the solve kernels, which live in objects of their own (po_solve_form.hip): the shape of a batch and its LDS bytes are resolved once per launch,
-// the table of shapes (po_solve_common.hpp) names the group of the row that equals it, the list of objects (po_launch.hpp) the one object to call.  The size and
-// capability queries (po_polish_state_doubles, ...) are answered here from the same table.
+// and the DISPATCHER of the solve kernels, which live in objects of their own (po_solve_form.hip): po_resolve_solve resolves the shape of a batch ONCE per call of a solve
+// entry (po_solve.cpp) into a SolveShape (po_launch.hpp) — the shape, its LDS bytes, the group of the row of the table of shapes (po_solve_common.hpp) that equals it,
+// and every size and capability the host asks about — and the launches take that: the list of objects (po_launch.hpp) names the one object to call.  The exported size
+// and capability queries (po_polish_state_doubles, ...) read the same resolution.
 //
 // Replaces, per path, the work behind /root/reference/src/solver/solver.cpp:46-77 (setHessianMatrix,
 // setConstraintMatrix, osqp_setup, osqp_solve, getOptimizedPath).
@@ -75,8 +76,8 @@ extern "C" hipError_t po_launch_mark_unavailable(po_info *info, int B, int refin
     hipLaunchKernelGGL(po::mark_unavailable_kernel, dim3((B + 255) / 256), dim3(256), 0, st, info, B, refine, polish);
     return hipGetLastError();
 }
-// ---- the dispatcher of the solve kernels.  Every launch resolves the shape of the batch and its LDS bytes ONCE, finds the group of the table row that equals the shape
-// (po_solve_common.hpp) and calls the ONE object that holds that formulation, kind and group (po_launch.hpp) with both; what that entry returns is the result.
+// ---- the dispatcher of the solve kernels.  The shape of a batch is resolved ONCE per call of a solve entry (po_resolve_solve, below); a launch calls the ONE object that
+// holds that formulation, kind and group (po_launch.hpp) with the shape and its LDS bytes; what that entry returns is the result.
 namespace po {
 namespace {
 using Entry = hipError_t(int, const Shape &, size_t, const DevBatch *, const DevParams *, hipStream_t);
@@ -84,42 +85,32 @@ struct Object { Entry *entry; int form, kind, groups; };
 #define PO_X(name, form, kind, groups) {&name, form, kind, groups},
 const Object kObjects[] = {PO_SOLVE_OBJECTS(PO_X)};
 #undef PO_X
-struct Resolved { Shape s; size_t lds; int group; bool fixed; };
-// lds is set whenever the shape resolves (po_launch_solve reports it even when it is over the limit)
-hipError_t resolve(int form, const DevBatch *in, Resolved *r) {
-    r->lds = 0;
-    if (!resolve_shape(form, in->N, in->C, in->keep, &r->s)) return hipErrorInvalidValue;
-    r->lds = lds_of(form, in->N, in->C, r->s);
-    r->group = group_of(form, r->s);
-#ifdef PO_DEV_HEADLINE  // (the KP objects of `make dev` hold their one shape whatever its group: the first linked object of the kind is asked)
-    if (form == F_KP && r->group) r->group = ~0;
-#endif
-    // a listed length (DevBatch::fixed_len, set from po_has_fixed_length): the kernels compiled for that length
-    r->fixed = in->fixed_len && in->n_points == nullptr && is_fixed_shape(form, in->N, in->C, in->keep, r->s);
-    return r->lds > 160 * 1024 ? hipErrorInvalidValue : hipSuccess;
-}
-hipError_t call(int form, int kind, int launch, const Resolved &r, const DevBatch *in, const DevParams *P, hipStream_t st) {
+template <int F, bool TWO, int SPL, int NT, int NWX> struct RowSizes { static constexpr int state = 0, park = 0; };  // the single-level mapping: neither Newton nor polish
+template <int F, int SPL, int NT, int NWX> struct RowSizes<F, true, SPL, NT, NWX> {
+    static constexpr int state = Fast<F, SPL, NT, true, NWX>::kStateDoubles * NT, park = Fast<F, SPL, NT, true, NWX>::kParkDoubles * NT + kNwParkScalars;
+};
+hipError_t call(int form, int kind, int launch, const SolveShape &r, const DevBatch *in, const DevParams *P, hipStream_t st) {
+    if (!r.nt || r.lds > kLdsLimit) return hipErrorInvalidValue;
+    const Shape s{.nt = r.nt, .spl = r.spl, .two = r.two != 0, .nwx = r.nwx};
     for (const Object &o : kObjects)
-        if (o.form == form && o.kind == kind && (o.groups & r.group) && o.entry) return o.entry(launch, r.s, r.lds, in, P, st);
+        if (o.form == form && o.kind == kind && (o.groups & r.group) && o.entry) return o.entry(launch, s, r.lds, in, P, st);
     return hipErrorNotSupported;  // no row equals the shape, or (dev builds) the object is not linked
 }
+// a listed length (DevBatch::fixed_len, set from the schedule's `fixed`): the kernels compiled for that length
+bool fixed(const SolveShape &r, const DevBatch *in) { return r.fixed && in->fixed_len && in->n_points == nullptr; }
 }  // namespace
 }  // namespace po
 // Two launches on the same stream for the two-level mapping: the uniform-row-class variant first (solves what it can, defers the rest; a listed length: the one compiled
 // for that length), then the general variant, which solves only what the first deferred (po_fast.inc, solve_kernel_fast).  Shapes without a uniform variant (the
 // single-level mapping, K on multi-wave blocks): the general variant alone.
-extern "C" hipError_t po_launch_solve(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out) {
+extern "C" hipError_t po_launch_solve(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
     using namespace po;
-    Resolved r;
-    hipError_t e = resolve(form, in, &r);
-    if (lds_out && r.lds) *lds_out = r.lds;
-    if (e != hipSuccess) return e;
-    const bool uni = form == F_K ? has_uni_variant<F_K>(r.s) : has_uni_variant<F_KP>(r.s);
+    hipError_t e;
     DevBatch copy = *in;
     copy.only_deferred = 0;
-    if (uni && (e = call(form, r.fixed ? kObjFixUni : kObjUni, kLaunchSolve, r, &copy, P, st)) != hipSuccess) return e;
-    copy.only_deferred = uni ? 1 : 0;
-    return call(form, kObjGen, kLaunchSolve, r, &copy, P, st);
+    if (s->uni && (e = call(form, fixed(*s, in) ? kObjFixUni : kObjUni, kLaunchSolve, *s, &copy, P, st)) != hipSuccess) return e;
+    copy.only_deferred = s->uni ? 1 : 0;
+    return call(form, kObjGen, kLaunchSolve, *s, &copy, P, st);
 }
 // no internal "in flight" status reaches the caller (finalize_status_kernel)
 extern "C" hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_t st) {
@@ -129,20 +120,17 @@ extern "C" hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_
 
 // the launches that pick up the state block of a two-level shape: the Newton refinement of round 0 (po_params.refine = 2; a listed length: the kernel compiled for it), the
 // fallback launch for what it hands back, and the polish
-static hipError_t launch_two_level(int form, int launch, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
+static hipError_t launch_two_level(int form, int launch, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
     using namespace po;
-    Resolved r;
-    const hipError_t e = resolve(form, in, &r);
-    if (!r.lds || !r.s.two) return hipErrorInvalidValue;
-    if (launch == kLaunchPolish && !has_polish_kernel(r.s)) return hipSuccess;
-    if (e != hipSuccess) return e;
-    const int kind = (launch == kLaunchNewton && r.fixed) ? (in->nw_phase == 2 ? kObjFixNewton2 : kObjFixNewton1) : (launch == kLaunchPolish ? kObjGen : kObjNewton);
-    return call(form, kind, launch, r, in, P, st);
+    if (!s->two) return hipErrorInvalidValue;
+    if (launch == kLaunchPolish && !s->polish) return hipSuccess;
+    const int kind = (launch == kLaunchNewton && fixed(*s, in)) ? (in->nw_phase == 2 ? kObjFixNewton2 : kObjFixNewton1) : (launch == kLaunchPolish ? kObjGen : kObjNewton);
+    return call(form, kind, launch, *s, in, P, st);
 }
-extern "C" hipError_t po_launch_newton(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchNewton, in, P, st); }
-extern "C" hipError_t po_launch_newton_fallback(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchFallback, in, P, st); }
+extern "C" hipError_t po_launch_newton(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchNewton, s, in, P, st); }
+extern "C" hipError_t po_launch_newton_fallback(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchFallback, s, in, P, st); }
 // OSQP's polish (po_params.polish) on the paths the two solve launches reported solved; same stream, after them (a shape without a polish kernel: nothing to do)
-extern "C" hipError_t po_launch_polish(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchPolish, in, P, st); }
+extern "C" hipError_t po_launch_polish(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchPolish, s, in, P, st); }
 namespace po {
 // the parked paths (keys[b] >= 0) in descending key order, ties in path order (a stable counting sort: deterministic): list[0] = count, list[1 ..] = path ids.
 // One workgroup of kNwSortThreads threads, thread t owns the contiguous range of paths [t * per, (t + 1) * per).
@@ -214,46 +202,45 @@ extern "C" hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipSt
     hipLaunchKernelGGL(po::nw_sort_kernel, dim3(1), dim3(po::kNwSortThreads), 0, st, keys, B, list);
     return hipGetLastError();
 }
-// ---- the size and capability queries: functions of the resolved shape and of class constants of its table row; no object is asked.  (K has no held controls: C = 0)
-namespace po {
-namespace {
-template <int F, bool TWO, int SPL, int NT, int NWX> struct RowSizes { static constexpr int state = 0, park = 0; };  // the single-level mapping: neither Newton nor polish
-template <int F, int SPL, int NT, int NWX> struct RowSizes<F, true, SPL, NT, NWX> {
-    static constexpr int state = Fast<F, SPL, NT, true, NWX>::kStateDoubles * NT, park = Fast<F, SPL, NT, true, NWX>::kParkDoubles * NT + kNwParkScalars;
-};
-int row_doubles(int form, int N, int C, int keep, bool park) {
+// ---- the resolution of a batch's shape, and the queries that read it: functions of the resolved shape and of class constants of its table row; no object is asked
+extern "C" int po_resolve_solve(int form, int N, int C, int keep, po::SolveShape *r) {
+    using namespace po;
+    *r = SolveShape{};
+    r->lds = (size_t)1 << 30;
     Shape s;
+    // K has no held controls: its shape is that of C = 0, whatever the caller's C (po_problem_dims: N - 1) — normalised here and nowhere else ...
     if (!resolve_shape(form, N, form == F_K ? 0 : C, keep, &s)) return 0;
-#define PO_X(F_, TWO_, SPL_, NT_, NWX_, G_) if (form == F_ && is_shape(s, TWO_, SPL_, NT_, NWX_)) return park ? RowSizes<F_, TWO_, SPL_, NT_, NWX_>::park : RowSizes<F_, TWO_, SPL_, NT_, NWX_>::state;
-    PO_SHAPE_ROWS(PO_X)
-#undef PO_X
-    return 0;
-}
-}  // namespace
-}  // namespace po
-// doubles per path of the state block the solve kernels leave for the Newton refinement and the polish (0: shape without either: the single-level mapping)
-extern "C" int po_polish_state_doubles(int form, int N, int C, int keep) { return po::row_doubles(form, N, C, keep, false); }
-// doubles per path of the block a PARKED Newton path lives in between the two sliced launches (Fast::park_io + kNwParkScalars)
-extern "C" int po_newton_park_doubles(int form, int N, int C, int keep) { return po::row_doubles(form, N, C, keep, true); }
-// is there a length-specialised instantiation for a (non-ragged) batch of this shape?  (KP only; this object is built with the list of lengths, PO_FIXED_LIST)
-extern "C" int po_has_fixed_length(int form, int N, int C, int keep) {
-    po::Shape s;
-    if (!po::resolve_shape(form, N, C, keep, &s) || !po::is_fixed_shape(form, N, C, keep, s) || po::lds_of(form, N, C, s) > 160 * 1024) return 0;
-#define PO_X(N_) if (N == N_) return 1;
+    r->nt = s.nt; r->spl = s.spl; r->two = s.two; r->nwx = s.nwx;
+    // ... but its LDS bytes are those of the caller's C: the single-level layout (LayoutF, !two) keeps room for C controls in every formulation, K's single-level batches
+    // (N > 512) have always been launched with, and refused by, that size, and tests/golden/shape_queries.json pins it.  (The two-level layout does not read C.)
+    r->lds = lds_of(form, N, C, s);
+    r->group = group_of(form, s);
+#ifdef PO_DEV_HEADLINE  // (the KP objects of `make dev` hold their one shape whatever its group: the first linked object of the kind is asked)
+    if (form == F_KP && r->group) r->group = ~0;
+#endif
+    r->uni = form == F_K ? has_uni_variant<F_K>(s) : has_uni_variant<F_KP>(s);
+    r->polish = has_polish_kernel(s);  // (the role-split shapes of keep 6 .. 16 and the single-level mapping have none)
+    bool listed = false;  // a length-specialised instantiation for a (non-ragged) batch of this shape?  (KP only; this object is built with the list, PO_FIXED_LIST)
+#define PO_X(N_) listed = listed || N == N_;
     PO_FIXED_LIST(PO_X)
 #undef PO_X
-    return 0;
+    r->fixed = listed && is_fixed_shape(form, N, C, keep, s) && r->lds <= kLdsLimit;
+#define PO_X(F_, TWO_, SPL_, NT_, NWX_, G_) if (form == F_ && is_shape(s, TWO_, SPL_, NT_, NWX_)) { r->state_doubles = RowSizes<F_, TWO_, SPL_, NT_, NWX_>::state; r->park_doubles = RowSizes<F_, TWO_, SPL_, NT_, NWX_>::park; }
+    PO_SHAPE_ROWS(PO_X)
+#undef PO_X
+    return 1;
 }
+static po::SolveShape resolved(int form, int N, int C, int keep) { po::SolveShape r; po_resolve_solve(form, N, C, keep, &r); return r; }
+// dynamic LDS bytes of the batch's kernels (1 GB: no shape)
+extern "C" size_t po_lds_bytes(int form, int N, int C, int keep) { return resolved(form, N, C, keep).lds; }
 // threads per path of the shape this batch runs in (0: unsupported)
-extern "C" int po_shape_threads(int form, int N, int C, int keep) {
-    po::Shape s;
-    return po::resolve_shape(form, N, form == po::F_K ? 0 : C, keep, &s) ? s.nt : 0;
-}
-// does the shape of this batch have a polish kernel?  (the role-split shapes of keep 6 .. 16 and the single-level mapping do not)
-extern "C" int po_has_polish_kernel(int form, int N, int C, int keep) {
-    po::Shape s;
-    return po::resolve_shape(form, N, form == po::F_K ? 0 : C, keep, &s) && po::has_polish_kernel(s);
-}
+extern "C" int po_shape_threads(int form, int N, int C, int keep) { return resolved(form, N, C, keep).nt; }
+// doubles per path of the state block the solve kernels leave for the Newton refinement and the polish (0: shape without either: the single-level mapping)
+extern "C" int po_polish_state_doubles(int form, int N, int C, int keep) { return resolved(form, N, C, keep).state_doubles; }
+// doubles per path of the block a PARKED Newton path lives in between the two sliced launches (Fast::park_io + kNwParkScalars)
+extern "C" int po_newton_park_doubles(int form, int N, int C, int keep) { return resolved(form, N, C, keep).park_doubles; }
+extern "C" int po_has_polish_kernel(int form, int N, int C, int keep) { return resolved(form, N, C, keep).polish; }
+extern "C" int po_has_fixed_length(int form, int N, int C, int keep) { return resolved(form, N, C, keep).fixed; }
 
 // nw_keys ([B]) / fb_count (one int), when set: reset by the same launch (scale_kernel) — the solve needs no fill of its own between its launches
 extern "C" hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, int *nw_keys, int *fb_count, hipStream_t st) {
@@ -272,11 +259,3 @@ extern "C" hipError_t po_launch_assemble(int form, const po::DevBatch *in, const
     else hipLaunchKernelGGL(assemble_kernel<F_K>, dim3(in->B), dim3(64), 0, st, *in, *P, l, u, dyn);
     return hipGetLastError();
 }
-
-extern "C" size_t po_lds_bytes(int form, int N, int C, int keep) {
-    using namespace po;
-    Shape s;
-    if (!resolve_shape(form, N, C, keep, &s)) return (size_t)1 << 30;
-    return lds_of(form, N, C, s);
-}
-

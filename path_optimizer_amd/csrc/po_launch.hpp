@@ -16,6 +16,16 @@ enum { kObjUni, kObjGen, kObjNewton, kObjFixUni, kObjFixNewton1, kObjFixNewton2 
 enum { kLaunchSolve, kLaunchNewton, kLaunchFallback, kLaunchPolish };  // what an entry is asked to launch (Newton: phase 1 or 2 by DevBatch::nw_phase)
 // the groups the shapes are dealt to the objects in (KP's two-level shapes: one lane per chunk / role-split / multi-group / the wide role-split shapes by SPL; the single-level mapping)
 enum { kGrpLane = 1, kGrpSplit = 2, kGrpMulti = 4, kGrpW56 = 8, kGrpW7 = 16, kGrpW8 = 32, kGrpOne = 64 };
+// Everything the host asks about the shape of a batch (formulation, N, C, keep), filled ONCE per call by po_resolve_solve and handed to the launches.  A plain struct
+// of host-side answers: no kernel sees it.
+struct SolveShape {
+    int nt, spl, two, nwx;            // the Shape of po_solve_common.hpp (nt == 0: no shape holds the batch)
+    size_t lds;                       // dynamic LDS bytes of its kernels (no shape: 1 GB; may exceed the 160 KB a launch can have: the entries refuse that)
+    int group;                        // the group of the table row that equals the shape (0: none)
+    int uni, polish, fixed;           // a uniform-row-class variant exists / a polish kernel exists / a length-specialised instantiation exists for this length
+    int state_doubles, park_doubles;  // doubles per path of the state block and of a parked Newton path's block (0: the single-level mapping)
+};
+constexpr size_t kLdsLimit = 160 * 1024;
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
 struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic; struct DevStplan; struct DevNudge;
 struct DevTrajectory;
@@ -24,10 +34,12 @@ struct DevSmooth;                                                               
 
 extern "C" {
 // ---- po_kernels.hip: the solve, by formulation ----
-hipError_t po_launch_solve(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st, size_t *lds_out);
-hipError_t po_launch_newton(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
-hipError_t po_launch_newton_fallback(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
-hipError_t po_launch_polish(int form, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+// the shape of a batch, resolved: 1 and *s filled, or 0 when no shape holds it (*s zeroed, lds = 1 GB).  The four launches take what it filled and resolve nothing.
+int po_resolve_solve(int form, int N, int C, int keep, po::SolveShape *s);
+hipError_t po_launch_solve(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+hipError_t po_launch_newton(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+hipError_t po_launch_newton_fallback(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+hipError_t po_launch_polish(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
 hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_t st);
 hipError_t po_launch_mark_unavailable(po_info *info, int B, int refine, int polish, hipStream_t st);
 hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipStream_t st);
@@ -39,6 +51,11 @@ int po_polish_state_doubles(int form, int N, int C, int keep);
 int po_newton_park_doubles(int form, int N, int C, int keep);
 int po_has_polish_kernel(int form, int N, int C, int keep);
 int po_has_fixed_length(int form, int N, int C, int keep);
+
+// ---- po_solve.cpp: what a solve of B paths of this shape will launch (plan_solve: no HIP call, no handle), exported for tests/test_solve_plan.py like the queries above.
+// out[9]: split, state block, polish, sliced, fixed, the refine mark, the polish mark, count read back, warm-start decades (its eps is 10^that times the caller's)
+int po_plan_solve(int form, int N, int keep, int B, int ragged, int refine, int refine_rounds, int refine_extra_rounds, int refine_chain, int polish, int nw_slice,
+                  int slice_forced, int fixed_on, int wave_slots, int *out);
 
 // ---- po_solve_form.hip: the objects that hold the solve kernels.  X(object, formulation, kind, shape groups it holds): ONE entry per object, named like the object (the
 // Makefile compiles <object>.o with -DPO_ENTRY=<object>), one signature for all.  The object reads its own row here; the dispatcher (po_kernels.hip) builds its route

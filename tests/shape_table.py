@@ -74,7 +74,7 @@ def shape_of(form, N, keep, lds=lds_bytes):
         s = pick_shape(form, N, C, 0)  # resolve_shape: keep 0 forces the single-level candidates (K re-enters its own two-level mapping)
         if s is None:
             return None
-    if lds(form, N, keep) > LDS_LIMIT:  # po_capi.cpp validate(): PO_ERR_UNSUPPORTED
+    if lds(form, N, keep) > LDS_LIMIT:  # po_solve.cpp validate(): PO_ERR_UNSUPPORTED
         return None
     return s
 

@@ -1,4 +1,4 @@
-"""The fixed-length kernels' scalars and the fills moved into scale_kernel (csrc/po_fast.inc, csrc/po_scale.hpp, csrc/po_capi.cpp).
+"""The fixed-length kernels' scalars and the fills moved into scale_kernel (csrc/po_fast.inc, csrc/po_scale.hpp, csrc/po_solve.cpp).
 
 The length-specialised kernels of KP's headline shape (N = 200, keep 4) take the number of controls as a constant and keep a pass's wave-uniform row steps in scalar
 registers.  Neither touches an operation or its order, so the claim is EXACT equality with the generic kernels — stricter than tests/test_fixed_length.py on purpose.
