@@ -1106,7 +1106,8 @@ int po_nudge_batch_device(po_handle h, const po_nudge_params *p, const po_nudge_
  *   Known and stated, not fixed: x and y are chords between states, not arcs.  Within an interval the motion is the constant-acceleration model the profile's t
  *       implies, not po_speed_batch's clamped a.  Where t0 + k * dt stops increasing in rounding, an agent's t is not strictly increasing; the HOST entry of
  *       po_dynamic_batch refuses such a list (the device entries skip the segment of zero duration).  Composing agent sets (first[]) from the records is the
- *       caller's job: a set is a contiguous range of slots.
+ *       caller's job: a set is a contiguous range of slots.  (po_agentsets_batch*, below, composes them on the device: per ego path the records of the other
+ *       vehicles and of a perception list that can matter to it, in the layout the consumers read.)
  *   Decided while building: disc_offset[d] and disc_radius[d] are checked for d < n_discs only, the entries behind are not read.  agent_pts, agent_stride and
  *       agent_flags are checked whatever n_discs is, so a struct that is refused with discs is refused without them.  (P - 1) * agent_stride is formed in 64 bits.
  *       "Aliasing" is an overlap of byte ranges: every output array given, over its full extent ([B][K][5], [B][K], [B], [B * D] records), against every input
@@ -1150,6 +1151,87 @@ typedef struct po_trajectory_out {
 int po_trajectory_batch(po_handle h, const po_trajectory_params *p, const po_trajectory_in *in, const po_trajectory_out *out);         /* host pointers, synchronous */
 int po_trajectory_batch_device(po_handle h, const po_trajectory_params *p, const po_trajectory_in *in, const po_trajectory_out *out);  /* device pointers, on the stream, no synchronisation */
 
+/* ---- agent sets: per ego path, the agents that can matter to it (csrc/po_agentsets.hip) ----
+ * The moving-obstacle stages read agents in SETS, contiguous ranges of one po_agent array, and po_trajectory_batch* writes a fleet's own plans as records at slot
+ * b * D + d.  With three or more vehicles in a scene "everybody but me" is not a contiguous range, and a vehicle handed the whole range conflicts with its own
+ * discs.  This stage composes the sets on the device: for each of B ego paths it copies, into one output array and in the po_agent_lists layout the three consumers
+ * read, the records of a POOL (a set of the source lists: a world, a scene) that are not the ego's own and that come near the path in space and in time.  Two
+ * sources: src[0], the fleet (po_trajectory_out.agents), where records have owners, and src[1], optional, a perception list nobody owns.  With it
+ * speed -> trajectory -> agent sets -> dynamic / stplan / nudge stays on one stream for any number of vehicles.  The stage reads no map and works on a handle
+ * without one.  The reference has no such stage.
+ *
+ * Definition (the bar is BIT equality with tests/agentsets_ref.py).  The conventions are po_dynamic_batch's: every operation is one rounded IEEE double operation
+ * in the order written; a comparison with a NaN is false; min(a, b) = b < a ? b : a; max(a, b) = b > a ? b : a.  n = n_states[b] clamped into [0, N] (N when
+ * NULL); row i = (x_i, y_i, ...); t_i = t[b][i].  reach, t_before, t_after, win_lo, win_hi, owner_div are the fields of po_agentsets_params.
+ *   Not composed: status = 0, count = 0, an empty set (first[b + 1] == first[b]), when ok[b] == 0, or n < 1, or any x, y of rows < n is non-finite, or (with t
+ *       given) any t of rows < n is non-finite.
+ *   Path box and time span:  exl, exh, eyl, eyh = the minimum and maximum of x_i, y_i over rows < n.  With t: W0 = (min t_i) - t_before, W1 = (max t_i) + t_after
+ *       (minimum and maximum, not first and last).  Without t: W0 = win_lo, W1 = win_hi.  These values only enter comparisons and are never written, so the order
+ *       of the reductions and the sign of a zero cannot show.
+ *   Candidates of ego b, in this order: the records of its pool of source 0, ascending, then those of its pool of source 1.  Pool of source s: k = pool_of[b]
+ *       clamped into [0, S_s - 1] (0 when NULL); lo = first_s[k], hi = first_s[k + 1], each clamped into [0, n_agents_s]; records lo .. hi - 1 (none when hi <= lo).
+ *       A NULL src[1], or one with S = 0 or n_agents = 0, contributes nothing.
+ *   A candidate a (its index into the array of its source), with np = n_pts points (T_j, X_j, Y_j), radius R and flags, is KEPT iff all of these hold:
+ *       it covers something by po_dynamic_batch's rule: 1 <= np <= 8, R >= 0, and every T_j, X_j, Y_j with j < np finite;
+ *       source 0 only: its owner is not b.  The owner is owner[a] when owner is given, else a / owner_div when owner_div > 0, else there is none;
+ *       time:  A0 <= W1 and A1 >= W0, where A0 = the minimum of T_j, j < np, or -inf with PO_AGENT_HOLD_BEFORE, and A1 = the maximum of T_j, or +inf with
+ *           PO_AGENT_HOLD_AFTER (minimum and maximum because a device entry reads lists nobody validated; every piece the consumers walk lies in [A0, A1]);
+ *       space: with rr = R + reach and axl, axh, ayl, ayh the minimum and maximum of X_j, Y_j, j < np:
+ *           axl - rr <= exh,  axh + rr >= exl,  ayl - rr <= eyh,  ayh + rr >= eyl.
+ *   Outputs.  count[b] = the number kept.  F_0 = 0, F_{b+1} = F_b + count[b] in 64 bits; first[b] = min(F_b, capacity) for b = 0 .. B.  The r-th kept candidate
+ *       of ego b goes to slot p = F_b + r when p < capacity: all 208 bytes are copied as they are (the points at and behind n_pts too), and src_index[p] = a for
+ *       source 0, src[0]->n_agents + a for source 1.  Slots at and behind first[B] are not written.  status[b] = 0 when not composed, otherwise 2 when
+ *       F_b + count[b] > capacity, else 1.  total[0] = F_B.  set_of[b] = b.  A clipped set is a prefix of the full one: the caller sees it in status and total
+ *       and calls again with room (capacity = 0 is the counting call).  {out->agents, out->first, n_agents = capacity, S = B} is a po_agent_lists, and with
+ *       out->set_of as their set_of the consumers take it as it is.
+ *   reach.  A po_dynamic_batch* with margin m cannot miss an agent when reach >= max_q (hypot(cx_q, cy_q) + cr_q) + m over the six footprint circles
+ *       (binding.footprint_reach).  For po_nudge_batch* reach must also cover the corridor's width and d_j; for po_stplan_batch* the margin of that stage.
+ *   Known and stated, not fixed: the box is that of the whole path, loose for long curved paths.  No nearest-first ordering and no cap per set: a clipped call
+ *       clips the LAST sets.  Oriented-box agents are out of scope, as in the consumers.
+ *   Decided while building: "overlap" is an overlap of byte ranges, out->agents over capacity records against each source array over its n_agents records.
+ *       src[0]->n_agents + src[1]->n_agents must fit an int (src_index is one).  The HOST entry moves out->agents and out->src_index in both directions, so the
+ *       slots that are not written keep the caller's bytes there too.
+ * Return codes, both entries.  PO_ERR_INVALID: a NULL handle, params or struct; a negative B, N, capacity or owner_div; a reach, t_before or t_after that is
+ *   negative or not finite; win_lo or win_hi not finite, or win_lo > win_hi; with B > 0 a NULL in->states, in->src[0], out->first, out->count or out->status, and a
+ *   NULL out->agents when capacity > 0; src[0] refused as po_dynamic_batch refuses its lists (negative S or n_agents, S = 0, a NULL first, NULL agents with
+ *   n_agents > 0), src[1] likewise unless it is NULL or has S = 0 or n_agents = 0; the two n_agents together beyond INT_MAX; out->agents overlapping a source array.  The HOST entry reads the lists and also
+ *   refuses what po_dynamic_batch's host entry refuses, for both sources, with pool_of in the place of set_of.  The DEVICE entry reads everything clamped and never
+ *   reads outside the buffers.  B = 0: PO_OK after those checks, nothing launched, nothing written.
+ * `p`, `in->src[s]` (the structs) are host pointers in both entries; the arrays inside are device pointers for the device entry.  Deterministic: no atomics and no
+ * scratch allocation (out->count and out->first carry the intermediates, so the entries only enqueue), and an ego's set, taken as contents and order, depends
+ * neither on B nor on its position in the batch.
+ * po_default_agentsets_params: {5.0, 0, 0, 0, 8, 0} — a starting point nobody has tuned. */
+#define PO_SETS_SOURCES 2
+typedef struct po_agentsets_params {
+    double reach;               /* >= 0, finite: a record is kept when its box, grown by radius + reach, meets the path's box */
+    double t_before, t_after;   /* >= 0, finite: the path's time span is widened by these (po_nudge_params' windows) */
+    double win_lo, win_hi;      /* finite, win_lo <= win_hi: the time span when in->t is NULL (po_stplan: 0 and K * dt) */
+    int    owner_div;           /* >= 0: without in->owner, record a of source 0 belongs to ego a / owner_div (po_trajectory's n_discs); 0: nobody owns it */
+} po_agentsets_params;
+void po_default_agentsets_params(po_agentsets_params *p);
+typedef struct po_agentsets_in {
+    int B, N;                   /* ego paths, rows per path (stride) */
+    const double *states;       /* [B][N][5] x, y, heading, k, s */
+    const int    *n_states;     /* optional [B] (NULL: N) */
+    const int    *ok;           /* optional [B] (NULL: all 1) */
+    const double *t;            /* optional [B][N]: po_speed_out.t */
+    const po_agent_lists *src[PO_SETS_SOURCES]; /* src[0] required (the fleet: po_trajectory_out.agents), src[1] optional (perception); each in POOLS: first[S_s + 1] */
+    const int    *pool_of;      /* optional [B] (NULL: pool 0): the pool of BOTH sources ego b draws from, clamped per source */
+    const int    *owner;        /* optional [src[0]->n_agents]: the ego a record belongs to, or any value outside [0, B) for none */
+} po_agentsets_in;
+typedef struct po_agentsets_out {
+    int        capacity;        /* records out->agents holds */
+    po_agent  *agents;          /* [capacity] */
+    int       *first;           /* [B + 1]: with agents and n_agents = capacity, S = B a po_agent_lists the consumers take */
+    int       *count;           /* [B]: records kept for ego b, before clipping */
+    int       *status;          /* [B] 0 not composed (empty set), 1 complete, 2 clipped by capacity */
+    int       *set_of;          /* optional [B]: b, what the consumers take as set_of */
+    int       *src_index;       /* optional [capacity]: where slot p came from: a (source 0) or src[0]->n_agents + a (source 1) */
+    long long *total;           /* optional [1]: the sum of count */
+} po_agentsets_out;
+int po_agentsets_batch(po_handle h, const po_agentsets_params *p, const po_agentsets_in *in, const po_agentsets_out *out);         /* host pointers, synchronous */
+int po_agentsets_batch_device(po_handle h, const po_agentsets_params *p, const po_agentsets_in *in, const po_agentsets_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -1184,7 +1266,8 @@ const char *po_last_hip_error(void);
  * the speed-profile entries (po_speed_params, po_speed_in, po_speed_out, po_default_speed_params, po_speed_batch*) and the moving-obstacle entries (po_agent, po_agent_lists, po_dynamic_params, po_dynamic_in, po_dynamic_out,
  * po_default_dynamic_params, po_dynamic_batch*) and the station-time entries (po_stplan_params, po_stplan_in, po_stplan_out, po_default_stplan_params,
  * po_stplan_batch*) and the corridor-nudge entries (po_nudge_params, po_nudge_in, po_nudge_out, po_default_nudge_params, po_nudge_batch*) and the timed-trajectory
- * entries (po_trajectory_params, po_trajectory_in, po_trajectory_out, po_default_trajectory_params, po_trajectory_batch*) were added under 7 by
+ * entries (po_trajectory_params, po_trajectory_in, po_trajectory_out, po_default_trajectory_params, po_trajectory_batch*) and the agent-set
+ * entries (po_agentsets_params, po_agentsets_in, po_agentsets_out, po_default_agentsets_params, po_agentsets_batch*) were added under 7 by
  * the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7

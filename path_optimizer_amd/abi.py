@@ -235,3 +235,21 @@ class PoTrajectoryIn(C.Structure):
 class PoTrajectoryOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("states", C.c_void_p), ("v", C.c_void_p), ("a", C.c_void_p), ("t", C.c_void_p), ("index", C.c_void_p),
                 ("first_held", C.c_void_p), ("agents", C.c_void_p)]
+
+
+# ---- agent sets (po_agentsets_batch*) ----
+PO_SETS_SOURCES = 2
+
+
+class PoAgentsetsParams(C.Structure):
+    _fields_ = [("reach", C.c_double), ("t_before", C.c_double), ("t_after", C.c_double), ("win_lo", C.c_double), ("win_hi", C.c_double), ("owner_div", C.c_int)]
+
+
+class PoAgentsetsIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("t", C.c_void_p),
+                ("src", C.POINTER(PoAgentLists) * PO_SETS_SOURCES), ("pool_of", C.c_void_p), ("owner", C.c_void_p)]
+
+
+class PoAgentsetsOut(C.Structure):
+    _fields_ = [("capacity", C.c_int), ("agents", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p), ("status", C.c_void_p), ("set_of", C.c_void_p),
+                ("src_index", C.c_void_p), ("total", C.c_void_p)]

@@ -36,7 +36,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_default_dynamic_params", "po_dynamic_batch", "po_dynamic_batch_device",
            "po_default_stplan_params", "po_stplan_batch", "po_stplan_batch_device",
            "po_default_nudge_params", "po_nudge_batch", "po_nudge_batch_device",
-           "po_default_trajectory_params", "po_trajectory_batch", "po_trajectory_batch_device"]
+           "po_default_trajectory_params", "po_trajectory_batch", "po_trajectory_batch_device",
+           "po_default_agentsets_params", "po_agentsets_batch", "po_agentsets_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -123,6 +124,10 @@ def lib():
         L.po_default_trajectory_params.restype = None
         L.po_trajectory_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_trajectory_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_default_agentsets_params.argtypes = [C.c_void_p]
+        L.po_default_agentsets_params.restype = None
+        L.po_agentsets_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_agentsets_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -202,6 +207,29 @@ def covering_discs(params):
     operations.  What po_trajectory_params.disc_offset / disc_radius take to emit a vehicle as the corridor stages see it."""
     rad = np.sqrt(np.float64(params.car_length / 8) * np.float64(params.car_length / 8) + np.float64(params.car_width / 2) * np.float64(params.car_width / 2))
     return [float(params.d[j]) for j in range(4)], float(rad + np.float64(params.safety_margin))
+
+
+def default_agentsets_params():
+    """po_default_agentsets_params: reach, time windows and owner rule of po_agentsets_batch* (a starting point nobody has tuned)."""
+    from .abi import PoAgentsetsParams
+
+    p = PoAgentsetsParams()
+    lib().po_default_agentsets_params(C.byref(p))
+    return p
+
+
+def footprint_reach(params, margin):
+    """The reach (po_agentsets_params.reach) with which po_dynamic_batch* at this margin cannot miss an agent: no footprint circle's edge is farther from the path
+    point than max_q (hypot(cx_q, cy_q) + cr_q) over the six circles of a parameter struct (PoParams or the oracle's; car_geometry.cpp:38-56 as po_capi.cpp's
+    make_car writes it), plus the margin, plus 1e-6 of slack for the roundings of the rotated centres."""
+    width, back, front = params.car_width, params.car_length / 2.0 - params.rear_axle_to_center, params.car_length / 2.0 + params.rear_axle_to_center
+    length, bx, shift = front + back, (front - back) / 2.0, width / 4.0
+    small_r = float(np.sqrt(2 * (shift * shift)))
+    large_r = float(np.sqrt(width * width + ((length - width) / 2.0) * ((length - width) / 2.0))) / 2
+    cx = [-back + shift, -back + shift, front - shift, front - shift, bx + (length - width) / 4, bx - (length - width) / 4]
+    cy = [-width / 2.0 + shift, width / 2.0 - shift, -width / 2.0 + shift, width / 2.0 - shift, 0.0, 0.0]
+    cr = [small_r] * 4 + [large_r] * 2
+    return max(float(np.hypot(cx[q], cy[q])) + cr[q] for q in range(6)) + float(margin) + 1e-6
 
 
 def problem_dims(form: int, N: int, keep: int):
@@ -1137,6 +1165,62 @@ class Engine:
         to = PoTrajectoryOut(*[p(out, k) for k in self.TRAJECTORY_KEYS])
         tp = params if params is not None else default_trajectory_params()
         _check(lib().po_trajectory_batch_device(self._h, C.byref(tp), C.byref(ti), C.byref(to)))
+
+    # ---- agent sets: per ego path, the agents that can matter to it ----
+    AGENTSETS_KEYS = ("agents", "first", "count", "status", "set_of", "src_index", "total")
+
+    def agentsets_batch(self, states, t, sources, pool_of=None, owner=None, capacity=None, params=None, n_states=None, ok=None):
+        """Host-pointer entry of po_agentsets_batch.  states [B,N,5], t [B,N] or None (the window of params), sources: one or two of what pack_agents takes (the
+        fleet in pools, then perception in pools); optional pool_of [B], owner [n_agents of source 0], n_states, ok [B].  capacity None: one counting call with
+        capacity 0, then a call with room for `total` records.  Returns a dict: agents [capacity] of AGENT_DTYPE, first [B + 1], count, status, set_of [B] i32,
+        src_index [capacity] i32, total (int), capacity; (agents, first) is what pack_agents passes through and set_of what the consumers take."""
+        from .abi import PoAgentsetsIn, PoAgentsetsOut
+
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        B, N = states.shape[0], states.shape[1]
+        tt = None if t is None else np.ascontiguousarray(t, dtype=np.float64)
+        ns, okk, pool, own = _i32(n_states), _i32(ok), _i32(pool_of), _i32(owner)
+        if not 1 <= len(sources) <= 2:
+            raise ValueError("sources: the fleet's lists, then optionally perception's")
+        held = [_agent_lists(s) for s in sources]  # (struct, agents, first): the arrays live until the C calls have returned
+        src = (C.POINTER(type(held[0][0])) * 2)(C.pointer(held[0][0]), C.pointer(held[1][0]) if len(held) > 1 else None)
+        ai = PoAgentsetsIn(B, N, _np(states), _np(ns), _np(okk), _np(tt), src, _np(pool), _np(own))
+        ap = params if params is not None else default_agentsets_params()
+        i32 = lambda n: np.zeros(n, dtype=np.int32)
+
+        def call(cap):
+            r = {"agents": np.zeros(cap, dtype=AGENT_DTYPE), "first": i32(B + 1), "count": i32(B), "status": i32(B), "set_of": i32(B), "src_index": i32(cap),
+                 "total": np.zeros(1, dtype=np.int64)}
+            ao = PoAgentsetsOut(cap, *[_np(r[k]) if len(r[k]) else None for k in self.AGENTSETS_KEYS])
+            _check(lib().po_agentsets_batch(self._h, C.byref(ap), C.byref(ai), C.byref(ao)))
+            return r
+
+        if capacity is None:
+            capacity = int(call(0)["total"][0])
+            if capacity >= 2 ** 31:
+                raise PoError(f"agentsets_batch: {capacity} records do not fit one call")
+        r = call(int(capacity))
+        r["total"], r["capacity"] = int(r["total"][0]), int(capacity)
+        return r
+
+    def agentsets_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: states [B,N,5] f64, agents (a uint8 tensor over AGENT_DTYPE records, or None) and first [S+1] i32 of the fleet (+ t [B,N] f64,
+        n_states, ok, pool_of i32 [B], owner i32 [n_agents], and agents1 / first1: the perception list); out: agents (a uint8 tensor over `capacity` records;
+        None: capacity 0, the counting call), first [B+1], count, status [B] i32 (+ set_of [B] i32, src_index [capacity] i32, total [1] i64).  out's agents,
+        first and set_of are what dynamic_batch_device, stplan_batch_device and nudge_batch_device take.  Enqueued on the handle's stream, no synchronisation."""
+        from .abi import PoAgentLists, PoAgentsetsIn, PoAgentsetsOut
+
+        B, N = t["states"].shape[0], t["states"].shape[1]
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        l0 = _agent_lists_device(t)
+        l1 = _agent_lists_device({"agents": t.get("agents1"), "first": t["first1"]}) if t.get("first1") is not None else None
+        src = (C.POINTER(PoAgentLists) * 2)(C.pointer(l0), C.pointer(l1) if l1 is not None else None)
+        ai = PoAgentsetsIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "t"), src, p(t, "pool_of"), p(t, "owner"))
+        ag = out.get("agents")
+        cap = 0 if ag is None else ag.numel() * ag.element_size() // AGENT_DTYPE.itemsize
+        ao = PoAgentsetsOut(cap, *[p(out, k) for k in self.AGENTSETS_KEYS])
+        ap = params if params is not None else default_agentsets_params()
+        _check(lib().po_agentsets_batch_device(self._h, C.byref(ap), C.byref(ai), C.byref(ao)))
 
     def map_sample(self, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)

@@ -1156,6 +1156,79 @@ int po_trajectory_batch(po_handle h, const po_trajectory_params *p, const po_tra
     });
 }
 
+// ---- agent sets (po_agentsets.hip) ----------------------------------------------------------------
+void po_default_agentsets_params(po_agentsets_params *p) {
+    if (!p) return;
+    *p = po_agentsets_params{5.0, 0.0, 0.0, 0.0, 8.0, 0};  // a starting point nobody has tuned
+}
+
+// Source 1 is optional: NULL, or a list with no pool or no record, contributes nothing (and then none of its pointers is looked at)
+static bool agentsets_src1_used(const po_agent_lists *L) { return L && L->S > 0 && L->n_agents > 0; }
+
+// What both entries can check without reading through a pointer of the structs (testable without a GPU)
+static bool agentsets_args_ok(po_handle h, const po_agentsets_params *p, const po_agentsets_in *in, const po_agentsets_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0 || out->capacity < 0 || p->owner_div < 0) return false;
+    auto room = [](double v) { return std::isfinite(v) && v >= 0; };
+    if (!room(p->reach) || !room(p->t_before) || !room(p->t_after) || !std::isfinite(p->win_lo) || !std::isfinite(p->win_hi) || !(p->win_lo <= p->win_hi)) return false;
+    const po_agent_lists *L0 = in->src[0], *L1 = in->src[1];
+    if (!agent_lists_shape_ok(L0, in->B)) return false;
+    if (!agent_lists_shape_ok(L1, 0) || (agentsets_src1_used(L1) && !agent_lists_shape_ok(L1, in->B))) return false;
+    if (L0 && agentsets_src1_used(L1) && (long long)L0->n_agents + L1->n_agents > std::numeric_limits<int>::max()) return false;  // src_index is an int
+    if (in->B > 0 && (!in->states || !out->first || !out->count || !out->status || (out->capacity > 0 && !out->agents))) return false;
+    // out->agents may not overlap a source array: byte ranges over the full extent of each
+    for (const po_agent_lists *L : {L0, L1}) {
+        if (!L || !L->agents || L->n_agents <= 0 || !out->agents || out->capacity <= 0) continue;
+        const uintptr_t ob = (uintptr_t)out->agents, ib = (uintptr_t)L->agents;
+        if (ob < ib + (size_t)L->n_agents * sizeof(po_agent) && ib < ob + (size_t)out->capacity * sizeof(po_agent)) return false;
+    }
+    return true;
+}
+
+int po_agentsets_batch_device(po_handle h, const po_agentsets_params *p, const po_agentsets_in *in, const po_agentsets_out *out) {
+    if (!agentsets_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing to compose: no launch, whatever the handle holds
+    Lock g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    po::DevAgentSets D{};
+    D.B = in->B; D.N = in->N; D.capacity = out->capacity; D.owner_div = p->owner_div;
+    D.states = in->states; D.n_states = in->n_states; D.ok = in->ok; D.t = in->t; D.pool_of = in->pool_of; D.owner = in->owner;
+    for (int s = 0; s < PO_SETS_SOURCES; ++s) {
+        const po_agent_lists *L = in->src[s];
+        if (s == 1 && !agentsets_src1_used(L)) continue;  // S = 0: the kernels skip the source
+        D.agents[s] = L->agents; D.first[s] = L->first; D.n_agents[s] = L->n_agents; D.S[s] = L->S;
+    }
+    D.reach = p->reach; D.t_before = p->t_before; D.t_after = p->t_after; D.win_lo = p->win_lo; D.win_hi = p->win_hi;
+    D.o_agents = out->agents; D.o_first = out->first; D.count = out->count; D.status = out->status; D.o_set_of = out->set_of; D.src_index = out->src_index;
+    D.total = out->total;
+    HIP_TRY(po_launch_agentsets(&D, h->stream));
+    return PO_OK;
+}
+
+int po_agentsets_batch(po_handle h, const po_agentsets_params *p, const po_agentsets_in *in, const po_agentsets_out *out) {
+    if (!agentsets_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
+    const bool two = agentsets_src1_used(in->src[1]);
+    if (!agent_lists_host_ok(in->src[0], in->pool_of, in->B) || (two && !agent_lists_host_ok(in->src[1], in->pool_of, in->B))) return PO_ERR_INVALID;
+    const size_t B = in->B, bn = B * (size_t)in->N, cap = (size_t)out->capacity;
+    Stage S;
+    const Slot<double> states = S.in(in->states, 5 * bn), t = S.in(in->t, bn);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), pool = S.in(in->pool_of, B), owner = S.in(in->owner, (size_t)in->src[0]->n_agents);
+    StagedAgents ag[PO_SETS_SOURCES];
+    stage_agent_lists(S, in->src[0], &ag[0]);
+    if (two) stage_agent_lists(S, in->src[1], &ag[1]);
+    // agents and src_index are written up to first[B] only: they travel in both directions, so the slots behind keep the caller's bytes
+    const Slot<po_agent> agents = S.inout(cap > 0 ? out->agents : nullptr, cap);
+    const Slot<int> sidx = S.inout(cap > 0 ? out->src_index : nullptr, cap);
+    const Slot<int> first = S.out(out->first, B + 1), count = S.out(out->count, B), status = S.out(out->status, B), set_of = S.out_opt(out->set_of, B);
+    const Slot<long long> total = S.out_opt(out->total, 1);
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+        const po_agent_lists d0 = ag[0].dev(in->src[0]), d1 = two ? ag[1].dev(in->src[1]) : po_agent_lists{};
+        const po_agentsets_in d{in->B, in->N, states, ns, ok, t, {&d0, two ? &d1 : nullptr}, pool, owner};
+        const po_agentsets_out o{out->capacity, agents, first, count, status, set_of, sidx, total};
+        return po_agentsets_batch_device(h, p, &d, &o);
+    });
+}
+
 // ---- corridor-bounds producer ------------------------------------------------------------------------------------
 static bool bounds_args_ok(po_handle h, const po_bounds_in *in, const double *bounds, const int *n_valid) {
     if (!h || !in || in->B < 0 || in->N < 1 || in->K < 3) return false;

@@ -165,6 +165,7 @@ inline bool assignment_covers(const po_handle_s *h, int B) PO_REQUIRES(h->mu) { 
 //   in(host, n)      n elements copied from host; host == nullptr: the array is absent, takes no room, and the slot is a null pointer
 //   out(host, n)     n elements the kernel writes, copied to host by copy_out(); host == nullptr: the device array exists all the same, only the copy is skipped
 //   out_opt(host, n) an optional output: host == nullptr: the caller does not want it, it is not declared, and the slot is a null pointer that the kernel skips
+//   inout(host, n)   an output the kernel writes only in part: copied from host and back, so what is not written keeps the caller's bytes; host == nullptr: as out_opt
 //   scratch(n)       n elements that travel in neither direction
 // Copies go from / to the caller's own memory on the handle's stream, under mu; the block itself is under the lock its member names.
 class Stage;
@@ -191,6 +192,7 @@ public:
     template <typename T> Slot<T> in(const T *host, size_t n) { return host ? add<T>(n, host, nullptr) : Slot<T>{}; }
     template <typename T> Slot<T> out(T *host, size_t n) { return add<T>(n, nullptr, host); }
     template <typename T> Slot<T> out_opt(T *host, size_t n) { return host ? out(host, n) : Slot<T>{}; }
+    template <typename T> Slot<T> inout(T *host, size_t n) { return host ? add<T>(n, host, host) : Slot<T>{}; }
     template <typename T> Slot<T> scratch(size_t n) { return add<T>(n, nullptr, nullptr); }
     size_t bytes() const { return bytes_; }
     // f(offset, bytes, host source or nullptr, host destination or nullptr) for every declared array, in order: for an entry that moves the block itself and keeps a

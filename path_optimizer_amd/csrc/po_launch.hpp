@@ -28,7 +28,7 @@ struct SolveShape {
 constexpr size_t kLdsLimit = 160 * 1024;
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
 struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic; struct DevStplan; struct DevNudge;
-struct DevTrajectory;
+struct DevTrajectory; struct DevAgentSets;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
 
@@ -151,4 +151,8 @@ hipError_t po_launch_nudge(const po::DevNudge *a, hipStream_t st);
 // ---- po_trajectory.hip: timed trajectory (one wave per path: a validity sweep over the rows, then lanes over the samples, each with a binary search on the path's
 // t row; the agent records by the first lanes; no LDS; device pointers) ----
 hipError_t po_launch_trajectory(const po::DevTrajectory *a, hipStream_t st);
+
+// ---- po_agentsets.hip: agent sets (count: one wave per ego, lanes over the rows, then over the candidates 64 at a time; scan: one workgroup over count; gather:
+// one wave per ego, the same decisions, the kept records copied by the whole wave; skipped when capacity is 0; 256 bytes of LDS; device pointers) ----
+hipError_t po_launch_agentsets(const po::DevAgentSets *a, hipStream_t st);
 }  // extern "C"

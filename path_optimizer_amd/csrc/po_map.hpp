@@ -160,6 +160,16 @@ struct DevTrajectory {
     int *status; double *o_states, *o_v, *o_a, *o_t; int *index, *first_held; po_agent *agents;
 };
 
+// agent-set launch arguments (po_agentsets.hip): po_agentsets_in / po_agentsets_out and the fields of po_agentsets_params; the two sources
+// side by side (S[1] = 0: source 1 contributes nothing).  t, pool_of, owner, o_set_of, src_index and total may be null; o_agents is null only with capacity 0.
+struct DevAgentSets {
+    int B, N, capacity, owner_div;
+    const double *states; const int *n_states, *ok; const double *t; const int *pool_of, *owner;
+    const po_agent *agents[PO_SETS_SOURCES]; const int *first[PO_SETS_SOURCES]; int n_agents[PO_SETS_SOURCES], S[PO_SETS_SOURCES];
+    double reach, t_before, t_after, win_lo, win_hi;
+    po_agent *o_agents; int *o_first, *count, *status, *o_set_of, *src_index; long long *total;
+};
+
 #ifdef PO_MAP_DEVICE_CODE  // kernels and device functions: po_kernels.hip only (po_capi.cpp needs just the structs)
 // Layer k of the stack as a DevMap.  k is clamped into [0, M - 1] HERE, where it is read: a table that arrived through a device pointer was never validated, and a
 // bad entry must select a wrong layer, never an address outside the stack.
