@@ -293,14 +293,17 @@ int po_set_stream(po_handle h, void *hip_stream);
  * at least two rounds of the device's wave slots (2 x 4 x CUs = 2048 paths) on shapes that run one wave per path, a value set here applies to every batch.  Scheduling only: the same operations in the same
  * order — statuses and certificates do not depend on it, the solutions agree to round-off (the kernels of the two launches are compiled separately; identical bit for bit on the
  * BASELINE KP / K shapes, <= 1e-10 elsewhere); BASELINE config 3: 4.76 -> 4.06 ms), "fixed_length" (default 1; 0: the generic kernels also for the path lengths the library was built with kernels
- * of their own for — the Makefile's PO_FIXED_N, KP with keep 4, non-ragged batches of exactly such a length; same operations in the same order, separately compiled).
+ * of their own for — the Makefile's PO_FIXED_N, KP with keep 4, non-ragged batches of exactly such a length; same operations in the same order, separately compiled),
+ * "fixed_classes" (default 1; 0: the Newton launches of those lengths without the constant-class kernels, which take every path whose stage-local rows are all
+ * inequalities and leave the others to the kernels without the constants; bit for bit the same results).
  * Unknown key: PO_ERR_INVALID. */
 int po_debug_set(po_handle h, const char *key, int value);
 /* Developer read-back (synchronises the stream): "fallback_paths" = how many paths the Newton launch of the last solve with refine = 2 did not certify and handed to
  * the fallback launch; "newton_parked" = how many went on into the second of the sliced Newton launches (-1: the last solve was not sliced); "map_ptr" = the device
  * address of the handle's map layer — layer 0 of the stack (0: no map; does not synchronise — po_set_map_occupancy_device / po_set_map_stack_occupancy_device with
  * an unchanged size and layer count must leave it where it is); "map_layers" = M, the number of layers the handle holds (0: no map; does not synchronise); "fixed_length_used" = 1 when the last solve ran the
- * length-specialised kernels, 0 when it ran the generic ones (does not synchronise); "dp_waves_used" = 8 or 1, the waves per instance of the handle's last DP lattice
+ * length-specialised kernels, 0 when it ran the generic ones (does not synchronise); "fixed_classes_used" = how many paths of the last solve the constant-class Newton
+ * kernels took (0: it did not run them); "dp_waves_used" = 8 or 1, the waves per instance of the handle's last DP lattice
  * search — po_dp_search_batch* or the search inside po_plan_batch* (0: none yet; does not synchronise): one wave above 512 instances, under "dp_one_wave", and when
  * the eight-wave reduction scratch does not fit in LDS beside the spline; "smooth_variant_used" = 100 * kind + 10 * waves + WPE, the instantiation of the smoothing kernel
  * that the handle's last po_smooth_batch* call launched: kind 0 .. 2, 1 / 4 / 8 waves per QP, WPE the occupancy bound it was compiled for (11, 42, 43 or 82; 0: no call

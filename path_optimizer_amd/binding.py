@@ -46,7 +46,7 @@ class PoError(RuntimeError):
 
 _ENV_DEBUG = {"PO_IDENTITY_ORDER": "identity_order", "PO_DEBUG_CYCLES": "debug_cycles", "PO_SMOOTH_SEQ": "smooth_seq",
               "PO_SMOOTH_WAVES": "smooth_waves", "PO_SMOOTH_NOPAD": "smooth_nopad", "PO_SMOOTH_DEBUG": "smooth_debug", "PO_DP_ONE_WAVE": "dp_one_wave", "PO_NEWTON_SLICE": "newton_slice",
-              "PO_FIXED_LENGTH": "fixed_length"}
+              "PO_FIXED_LENGTH": "fixed_length", "PO_FIXED_CLASSES": "fixed_classes"}
 
 
 def lib():
@@ -400,8 +400,8 @@ class Engine:
             raise
 
     def debug_set(self, key: str, value: int):
-        """po_debug_set: developer A/B switches (identity_order, debug_cycles, host_threads, smooth_seq, smooth_waves, smooth_nopad, smooth_debug, dp_one_wave, newton_slice, fixed_length).
-        Read-only keys go through debug_get: fixed_length_used, dp_waves_used (8 or 1: the variant of the last DP lattice search; dp_one_wave = 1 forces 1), smooth_variant_used (100 * kind + 10 * waves + WPE of the last smoothing launch), fallback_paths,
+        """po_debug_set: developer A/B switches (identity_order, debug_cycles, host_threads, smooth_seq, smooth_waves, smooth_nopad, smooth_debug, dp_one_wave, newton_slice, fixed_length, fixed_classes).
+        Read-only keys go through debug_get: fixed_length_used, fixed_classes_used (paths of the last solve the constant-class Newton kernels took), dp_waves_used (8 or 1: the variant of the last DP lattice search; dp_one_wave = 1 forces 1), smooth_variant_used (100 * kind + 10 * waves + WPE of the last smoothing launch), fallback_paths,
         newton_parked, map_ptr, map_layers."""
         _check(lib().po_debug_set(self._h, key.encode(), int(value)))
 

@@ -166,6 +166,7 @@ int po_debug_set(po_handle h, const char *key, int value) {
     else if (k == "debug_cycles") h->env_cycles = value != 0;
     else if (k == "newton_slice") { h->nw_slice = value > 0 ? (int)value : 0; h->nw_slice_forced = value > 0; }  // (set explicitly: also on batches the engine would not slice)
     else if (k == "fixed_length") h->fixed_length = value != 0;  // (0: the generic kernels also for the lengths of PO_FIXED_N; an A/B switch, the results do not depend on it)
+    else if (k == "fixed_classes") h->fixed_classes = value != 0;  // (0: no constant-class Newton kernels; an A/B switch, the results do not depend on it)
     else if (k == "smooth_seq") h->env_smooth_seq = value != 0;
     else if (k == "smooth_waves") h->env_smooth_waves = value;
     else if (k == "smooth_nopad") h->env_smooth_nopad = value != 0;
@@ -213,6 +214,16 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
         *value = c;
         return PO_OK;
     }
+    if (k == "fixed_classes_used") {  // how many paths of the last solve the constant-class Newton kernels were given (0: it did not run them): the flags on the device, summed
+        *value = 0;
+        if (!h->nw_idx_buf.p || h->std_flag_at < 0 || h->std_B <= 0) return PO_OK;
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        std::vector<int> flag((size_t)h->std_B);
+        HIP_TRY(hipMemcpy(flag.data(), static_cast<int *>(h->nw_idx_buf.p) + h->std_flag_at, sizeof(int) * flag.size(), hipMemcpyDeviceToHost));
+        for (int f : flag) *value += f != 0;
+        return PO_OK;
+    }
     if (k == "newton_parked") {  // sliced Newton launches: how many paths of the last solve went on into the second launch (-1: the last solve was not sliced)
         *value = -1;
         if (!h->nw_idx_buf.p || h->nw_last_B <= 0) return PO_OK;
@@ -221,6 +232,10 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
         int c = 0;
         HIP_TRY(hipMemcpy(&c, static_cast<int *>(h->nw_idx_buf.p) + h->nw_last_B, sizeof(int), hipMemcpyDeviceToHost));
         *value = c;
+        if (h->std_left2_at >= 0) {  // (the constant-class kernels ran: the parked paths are on two lists)
+            HIP_TRY(hipMemcpy(&c, static_cast<int *>(h->nw_idx_buf.p) + h->std_left2_at, sizeof(int), hipMemcpyDeviceToHost));
+            *value += c;
+        }
         return PO_OK;
     }
     if (k == "newton_list_ok") {  // sliced Newton launches: is the second launch's list what nw_sort_kernel promises — every parked path exactly once, keys non-increasing, ties in path
@@ -230,20 +245,28 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->stream));
         const int B = h->nw_last_B;
-        std::vector<int> kl(2 * (size_t)B + 1);
+        // (the constant-class kernels ran: two lists, each ordered like that, which hold every parked path exactly once between them)
+        const bool two_lists = h->std_left2_at >= 0;
+        std::vector<int> kl(two_lists ? (size_t)h->std_left2_at + (size_t)B + 1 : 2 * (size_t)B + 1);
         HIP_TRY(hipMemcpy(kl.data(), h->nw_idx_buf.p, sizeof(int) * kl.size(), hipMemcpyDeviceToHost));
-        const int *keys = kl.data(), *list = kl.data() + B;
-        const int n = list[0];
-        int parked = 0;
+        const int *keys = kl.data();
+        int parked = 0, listed = 0;
         for (int b = 0; b < B; ++b) parked += keys[b] >= 0;
-        bool ok = n == parked;
+        bool ok = true;
         std::vector<char> seen((size_t)B, 0);
-        for (int i = 0; ok && i < n; ++i) {
-            const int b = list[1 + i];
-            ok = b >= 0 && b < B && keys[b] >= 0 && !seen[(size_t)b];
-            if (ok) seen[(size_t)b] = 1;
-            if (ok && i > 0) { const int a = list[i]; ok = keys[a] > keys[b] || (keys[a] == keys[b] && a < b); }
+        for (const int *list : {kl.data() + B, two_lists ? kl.data() + h->std_left2_at : nullptr}) {
+            if (!list) continue;
+            const int n = list[0];
+            ok = ok && n >= 0 && n <= B;
+            for (int i = 0; ok && i < n; ++i) {
+                const int b = list[1 + i];
+                ok = b >= 0 && b < B && keys[b] >= 0 && !seen[(size_t)b];
+                if (ok) seen[(size_t)b] = 1;
+                if (ok && i > 0) { const int a = list[i]; ok = keys[a] > keys[b] || (keys[a] == keys[b] && a < b); }
+            }
+            listed += n;
         }
+        ok = ok && listed == parked;
         *value = ok ? 1 : 0;
         return PO_OK;
     }

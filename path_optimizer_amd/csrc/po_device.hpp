@@ -74,6 +74,23 @@ struct DevBatch {
     // the Makefile's PO_FIXED_N, and po_debug_set("fixed_length", 0) has not switched them off.  Read by the launchers only; no kernel looks at it.
     int fixed_len;
 };
+// The constant-class Newton kernels of a fixed length (newton_kernel_std, po_fast.inc): the packed classes by type they take as constants — every stage-local row an
+// inequality (0), KP's one control row free (2) (refine_phase_newton's CK says which passes take them: DESIGN.md section 36) — and the
+// lists that split a batch between them and the kernels without the constants.  The lists live behind keys [B] and list [1 + B] in the block DevBatch::nw_keys points
+// to (the engine sets nw_keys for them on an unsliced solve too); scale_kernel resets them, newton_std_select_kernel fills them.
+constexpr unsigned kStdClsLoc = 0u, kStdClsCtl = 2u;
+struct StdLists {
+    int *left1;  // [B]: slot i = the path of the first (or only) launch's workgroup i when it is NOT standard, else -1 (the format of DevBatch::order)
+    int *left2;  // count, then ids: the parked paths that are not standard, in launch order (the format of DevBatch::nw_list; the standard ones are on nw_list itself)
+    int *order;  // [B]: slot i = that path when it IS standard, else -1
+    int *flag;   // [B]: 1 the path is standard (their number: po_debug_get "fixed_classes_used")
+};
+constexpr size_t std_left2_index(size_t B) { return 3 * B + 1; }
+constexpr size_t std_flag_index(size_t B) { return 5 * B + 2; }
+constexpr size_t std_lists_ints(size_t B) { return std_flag_index(B) + B; }
+__host__ __device__ inline StdLists std_lists(int *nw_keys, int B) {
+    return {nw_keys + 2 * B + 1, nw_keys + std_left2_index(B), nw_keys + 4 * B + 2, nw_keys + std_flag_index(B)};
+}
 
 template <int F> struct FormTraits;
 template <> struct FormTraits<F_KP> {

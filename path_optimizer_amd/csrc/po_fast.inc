@@ -4162,7 +4162,10 @@ constexpr int kNwStagnation = 8;
 // point, on return st.cls* hold the row classes of the bounds and v is expressed for the type-based step vector at rho_solve.
 // PH: 0 the whole phase; 1 first of the two sliced launches (parks); 2 second (resumes) — compile-time, each with its own register allocation (one body with both
 // at run time: 77 -> 207 spilled VGPRs, the launch 3.8 -> 4.9 ms)
-template <int F, int SPL, int NT, int NWX, int PH = 0, int NFIX = 0>
+// CK (fixed lengths only; DESIGN.md section 36): the row classes BY TYPE that every pass of the phase decodes are compile-time constants — all stage-local rows
+// inequalities, KP's control row free; the caller has checked that the path's classes are those (newton_kernel_std).  The end rows keep their run-time class.  The
+// same operations on the same numbers: only the class tests fold.
+template <int F, int SPL, int NT, int NWX, int PH = 0, int NFIX = 0, bool CK = false>
 __device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, NWX, NFIX> &fx, typename Fast<F, SPL, NT, true, NWX, NFIX>::LS &st, const DevParams &P, double rho_solve, double rp0, double rd0,
                                                          int slice = 0, double *park = nullptr, int *park_key = nullptr) {
     constexpr bool resume = PH == 2;
@@ -4175,11 +4178,19 @@ __device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, 
         for (int s = 0; s < FormTraits<F>::NS; ++s) { st.hi[q][s] = 0; st.gs[q][s] = 0; st.hv[q][s][0] = st.hv[q][s][1] = st.hv[q][s][2] = 0; }
     }
     st.hiu = st.hus = st.gsu = 0;
+    static_assert(!CK || (NFIX > 0 && F == F_KP), "constant row classes: the fixed-length KP kernels only");
     fx.bound_classes(st);
     unsigned cls0[SPL];
 #pragma unroll
     for (int q = 0; q < SPL; ++q) cls0[q] = st.cls[q];
     const unsigned clse0 = st.clse, clsc0 = st.clsc;
+    // CK: reclass_pass and nw_reexpress_pass get the constants (cls_k, clsc_k) in place of the run-time classes by type.  The direction pass and the line search do NOT:
+    // with the constants their surviving rows were compiled with other multiply-add contractions and config 3 differed from the parent's results (DESIGN.md section 36)
+    unsigned cls_std[SPL];
+#pragma unroll
+    for (int q = 0; q < SPL; ++q) cls_std[q] = kStdClsLoc;
+    const unsigned *const cls_k = CK ? cls_std : cls0;
+    const unsigned clsc_k = CK ? kStdClsCtl : clsc0;
     // (every scalar the phase carries from step to step is WAVE-UNIFORM and is kept in scalar registers on purpose: uni(), po_device.hpp)
     double rb = uni(fmin(fmax(P.ref_nw_rho, kRhoMin), kRhoMax)), pri_outer = -1.0;
     rho_solve = uni(rho_solve); rp0 = uni(rp0); rd0 = uni(rd0);
@@ -4209,11 +4220,11 @@ __device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, 
 #define PO_NW_TICK(i)
 #endif
     PO_FRESH_LANE_ID(fx);
-    if constexpr (!resume) fx.nw_reexpress_pass(st, rho_solve / rb, kRhoEqOverIneq * rho_solve / fx.nw_req, cls0, clse0, clsc0);  // w = a.x + y / rho_i with the multipliers of the ADMM point
+    if constexpr (!resume) fx.nw_reexpress_pass(st, rho_solve / rb, kRhoEqOverIneq * rho_solve / fx.nw_req, cls_k, clse0, clsc_k);  // w = a.x + y / rho_i with the multipliers of the ADMM point
     for (;;) {
         PO_FRESH_LANE_ID(fx);
         PO_MARK("nw_reclass");
-        (void)fx.reclass_pass(st, cls0, clse0, clsc0, rb, rb, 3);  // rows outside their bounds: class 0 (step rho), inside: class 2 (RHO_MIN)
+        (void)fx.reclass_pass(st, cls_k, clse0, clsc_k, rb, rb, 3);  // rows outside their bounds: class 0 (step rho), inside: class 2 (RHO_MIN)
         PO_NW_TICK(0)
         PO_MARK("nw_residual");
         R = fx.template residual_pass_two<false>(st, rb);                      // (x, z = clip(w), y = rho (w - z)): the dual residual is the gradient of the merit
@@ -4256,7 +4267,7 @@ __device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, 
             }
             pri_outer = R.rp;
             PO_FRESH_LANE_ID(fx);
-            fx.nw_reexpress_pass(st, ratio, ratio_eq, cls0, clse0, clsc0);
+            fx.nw_reexpress_pass(st, ratio, ratio_eq, cls_k, clse0, clsc_k);
             quiet = false;
             continue;
         }
@@ -4361,7 +4372,7 @@ __device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, 
                tcy[0], tcy[1], tcy[2], fx.dbgc[0], fx.dbgc[1], fx.dbgc[2], tcy[3], tcy[4], tcy[5], tcy[6], tcy[7]);
 #endif
 #undef PO_NW_TICK
-    (void)fx.reclass_pass(st, cls0, clse0, clsc0, rb, rho_solve, 2, fx.nw_req, kRhoEqOverIneq * rho_solve);
+    (void)fx.reclass_pass(st, cls_k, clse0, clsc_k, rb, rho_solve, 2, fx.nw_req, kRhoEqOverIneq * rho_solve);
     fx.nw_req = 0.0;
     RefineOut o = {!R.bad && (stop || (R.rp <= rp0 && R.rd <= rd0)), stop && !R.bad, it2, nfac, R, false};
     return o;
@@ -4585,70 +4596,42 @@ template <int F, int SPL, int NT, int NWX = 1> __global__ PO_KERNEL_ATTR __launc
     }
 }
 
-template <int F, int SPL, int NT, int NWX = 1, int PH = 1, int NFIX = 0> __global__ PO_KERNEL_ATTR __launch_bounds__(NT) void newton_kernel(DevBatch in, DevParams P) {
-    using FX = Fast<F, SPL, NT, true, NWX, NFIX>;
+// The kernel's text is po_newton_kernel.inc: newton_kernel, and newton_kernel_std — the Newton launches of a fixed length with the STANDARD row classes as compile-time
+// constants (DESIGN.md section 36): every stage-local row an inequality, KP's control row free, which is every path with positive margin and kmax and non-degenerate
+// corridors.  Which paths those are is decided by newton_std_select_kernel (below) in a launch of its own; the engine hands newton_kernel_std the standard paths and
+// newton_kernel of the same phase and length the others, right behind it (std_lists, po_device.hpp).  (The test at the entry of newton_kernel_std itself was tried
+// first: with nothing else changed the kernel then computed other roundings — 3.8 of 4.1 million elements of config 3 differed from the parent's by up to 1.3e-13; DESIGN.md section 36.)
+#define PO_NW_KERNEL newton_kernel
+#define PO_NW_CK false
+#include "po_newton_kernel.inc"
+#undef PO_NW_KERNEL
+#undef PO_NW_CK
+#define PO_NW_KERNEL newton_kernel_std
+#define PO_NW_CK true
+#include "po_newton_kernel.inc"
+#undef PO_NW_KERNEL
+#undef PO_NW_CK
+// Workgroup i looks at the path the first Newton launch gives workgroup i (the caller's order, else the engine's permutation): are its row classes by type the standard
+// ones on every lane?  (load() leaves the classes of the bounds in st.cls*; one wave per path: the vote is block-uniform.)  Slot i of StdLists::order or of
+// StdLists::left1 gets the path — both were filled with -1 by scale_kernel, and a first launch's workgroup leaves on -1 —, flag[path] says which, for the sort that
+// splits the parked paths between the two second launches.  Reads only the inputs of the path.
+template <int F, int SPL, int NT, int NFIX> __global__ PO_KERNEL_ATTR __launch_bounds__(NT) void newton_std_select_kernel(DevBatch in, DevParams P) {
+    static_assert(NT == 64, "constant row classes: one wave per path");
+    using FX = Fast<F, SPL, NT, true, 1, NFIX>;
     extern __shared__ double smem[];
-    // SLICED LAUNCHES (in.nw_phase; the engine's default on one-wave shapes, DESIGN.md section 11): phase 1 runs every path for at most P.ref_nw_slice Newton steps — every path takes
-    // that many, so the launch has no tail — and parks what is not finished (state block of its own, a priority key); nw_sort_kernel orders the parked paths by expected
-    // remaining work, longest first; phase 2 (workgroup i takes entry i of that list; workgroups start in index order) finishes them.  The tail of a single launch — a
-    // 35-step path that happens to start last while the mean is 14 — was 30 % of it.  The same operations in the same order: statuses and certificates do not depend on the slicing, solutions agree to round-off (two separately compiled kernels).
-    // PH = 1 with P.ref_nw_slice = 0 (no parking block: po_debug_set "newton_slice" 0) is the single launch.
-#ifdef PO_NW_TRACE
-    const long long tk0_ = __builtin_readcyclecounter();
-#endif
-    int b;
-    if constexpr (PH == 2) {
-        if ((int)blockIdx.x >= in.nw_list[0]) return;
-        b = in.nw_list[1 + blockIdx.x];
-    } else b = in.order ? in.order[blockIdx.x] : perm_index(blockIdx.x, in.perm_bits, in.B);
+    const int b = in.order ? in.order[blockIdx.x] : perm_index(blockIdx.x, in.perm_bits, in.B);
     if ((unsigned)b >= (unsigned)in.B) return;
-    po_info *oi = in.out_info + b;
-    const bool slicing = PH == 2 || P.ref_nw_slice > 0;
-    if (oi->status != PO_STATUS_SOLVED) return;  // (non-finite inputs, out of iterations, infeasible: reported as the solve left them)
     FX fx(P, in, smem, b);
     typename FX::LS st;
     fx.load(st);
-    // (the state block is read BEFORE the LDS set-up: behind its barriers the 70 loads would start a round trip of their own after those of load() and scale_to_lds())
-    double *state = in.pol_state + (size_t)b * in.pol_stride;
-    double *pstate = slicing ? in.nw_state + (size_t)b * in.nw_stride : nullptr, *pscal = slicing ? pstate + (size_t)FX::kParkDoubles * NT : nullptr;
-    if constexpr (PH == 2) fx.template park_io<false>(st, pstate); else fx.template state_io<false>(st, state);
-    for (int i = fx.tid; i < fx.L.total; i += NT) smem[i] = 0.0;
-    __syncthreads();
-    fx.scale_to_lds();
-    // (wave-uniform and alive until the kernel's last lines: scalar registers — uni(), po_device.hpp)
-    const int lo_it = uni(oi->iters), lo_nref = uni(oi->n_refactor);
-    const double lo_rho = uni(oi->rho), rp0 = uni(oi->r_prim), rd0 = uni(oi->r_dual);
-    const int rounds = P.ref_rounds > 1 ? P.ref_rounds : 1, rounds_total = rounds + P.ref_extra;
-    const bool last = 1 >= rounds_total;
-#ifdef PO_NW_TRACE
-    const long long tk1_ = __builtin_readcyclecounter();
-#endif
-    const RefineOut ro = refine_phase_newton<F, SPL, NT, NWX, PH, NFIX>(fx, st, P, lo_rho, rp0, rd0, slicing ? P.ref_nw_slice : 1 << 30, pscal, slicing ? in.nw_keys + b : nullptr);
-    __syncthreads();
-#ifdef PO_NW_TRACE
-    const long long tk2_ = __builtin_readcyclecounter();
-    if (fx.b == 0 && fx.tid == 0) printf("  dev kernel PH %d: entry %lld cycles (load, LDS set-up, state block), phase %lld (%d steps)\n", PH, tk1_ - tk0_, tk2_ - tk1_, ro.it);
-#endif
-    if constexpr (PH == 1) if (ro.parked) { fx.template park_io<true>(st, pstate); return; }  // (po_info and the state block of the solved point stay as the warm start left them)
-    const bool hand_back = !ro.stop && !last;
-    // the state block after this kernel is read by the fallback rounds (a path handed back) and by polish_kernel: a finished path's state is not stored otherwise
-    // (147 MB of writes per BASELINE batch).  Attempt not taken: the solved point stays in the block, and comes back into st for the outputs below
-    if (ro.take) { if (hand_back || P.polish) fx.template state_io<true>(st, state); }
-    else if (!hand_back) fx.template state_io<false>(st, state);
-    if (hand_back) {
-        if (fx.tid == 0) {
-            oi->status = kStatusDeferred - 1; oi->iters = lo_it + ro.it; oi->status_polish = lo_it; oi->n_refactor = lo_nref + ro.nfac;
-            if (ro.take) { oi->r_prim = ro.R.rp; oi->r_dual = ro.R.rd; oi->obj = ro.R.obj; }
-            oi->status_refine = -1;
-            in.fb_list[1 + atomicAdd(in.fb_list, 1)] = b;  // newton_fallback_kernel takes it from here
-        }
-        return;
-    }
-    fx.output_pass(st);  // (the warm start left them to this kernel: DevBatch::nw_follows)
+    bool standard = st.clsc == kStdClsCtl;
+#pragma unroll
+    for (int q = 0; q < SPL; ++q) standard = standard && st.cls[q] == kStdClsLoc;
+    const bool all = __all(standard) != 0;
     if (fx.tid == 0) {
-        oi->iters = lo_it + ro.it; oi->n_refactor = lo_nref + ro.nfac;
-        if (ro.take) { oi->r_prim = ro.R.rp; oi->r_dual = ro.R.rd; oi->obj = ro.R.obj; }
-        oi->status_refine = ro.stop ? 1 : -1;
+        const StdLists sl = std_lists(in.nw_keys, in.B);
+        (all ? sl.order : sl.left1)[blockIdx.x] = b;
+        sl.flag[b] = all ? 1 : 0;  // (no count here: 4 096 atomic adds on one word made this launch 60 us instead of 18, DESIGN.md section 36 — po_debug_get sums the flags)
     }
 }
 

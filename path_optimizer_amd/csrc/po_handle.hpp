@@ -119,12 +119,18 @@ struct po_handle_s {
     PO_GUARDED_BY(mu) int host_threads = 0;      // pack / unpack threads (0: min(8, hardware threads); po_debug_set "host_threads")
     PO_GUARDED_BY(mu) DevBuf pol_buf;  // per-lane ADMM state handed from the solve kernels to newton_kernel / polish_kernel (po_params.refine / polish)
     PO_GUARDED_BY(mu) DevBuf fb_buf;   // refine = 2: the work list of newton_fallback_kernel
-    PO_GUARDED_BY(mu) DevBuf nw_state_buf, nw_idx_buf;  // sliced Newton launches: the parked paths' blocks; keys [B] + list [B + 1]
+    PO_GUARDED_BY(mu) DevBuf nw_state_buf, nw_idx_buf;  // sliced Newton launches: the parked paths' blocks; keys [B] + list [B + 1] (+ the constant-class kernels' lists)
     PO_GUARDED_BY(mu) bool nw_slice_forced = false;
     PO_GUARDED_BY(mu) int nw_last_B = 0;  // ... and the batch size of the last sliced solve (po_debug_get "newton_parked")
     int wave_slots = 1024;  // paths the device runs at a time (one wave per SIMD: 4 per CU); batches below two rounds of that are not sliced (no queueing tail to remove)
     PO_GUARDED_BY(mu) bool fixed_length = true;  // take the length-specialised kernels where the batch has one (po_debug_set "fixed_length"; 0: always the generic kernels).  Same results.
     PO_GUARDED_BY(mu) int fixed_used = 0;        // ... and whether the last solve ran them (po_debug_get "fixed_length_used")
+    // ... with the standard row classes as compile-time constants in their Newton launches, for the paths that have those classes (po_debug_set "fixed_classes"; 0: the
+    // kernels without the constants for every path).  Same results.  Their lists live in nw_idx_buf behind keys and list (std_lists, po_device.hpp); std_flag_at: where
+    // in that block the last solve flagged the std_B paths they took (-1: it did not run them; po_debug_get "fixed_classes_used")
+    PO_GUARDED_BY(mu) bool fixed_classes = true;
+    PO_GUARDED_BY(mu) int std_B = 0;
+    PO_GUARDED_BY(mu) long std_flag_at = -1, std_left2_at = -1;  // (std_left2_at: where the second list of parked paths starts, sliced solves; -1: there is one list)
     PO_GUARDED_BY(mu) int dp_waves_used = 0;     // waves per instance of the last DP lattice search: 8 or 1 (0: none yet; po_debug_get "dp_waves_used")
     PO_GUARDED_BY(mu) int smooth_variant_used = 0;  // instantiation of the last smoothing launch: 100 * kind + 10 * waves per QP + WPE, e.g. 143 = <TENSION, 4, 3> (0: none yet; po_debug_get "smooth_variant_used")
     PO_GUARDED_BY(mu) int nw_slice = 8;  // steps of the first of the two Newton launches (po_debug_set "newton_slice"; 0: one launch).  Scheduling only.

@@ -128,6 +128,26 @@ static hipError_t launch_two_level(int form, int launch, const po::SolveShape *s
     return call(form, kind, launch, *s, in, P, st);
 }
 extern "C" hipError_t po_launch_newton(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchNewton, s, in, P, st); }
+// The Newton launch of a listed length as a pair (phase by DevBatch::nw_phase, like po_launch_newton): the constant-class kernel over the paths
+// whose row classes are the standard ones, then the kernel without the constants over the others.  The first (or only) phase is preceded by the launch that decides
+// which are which (newton_std_select_kernel) and gives each kernel its paths as its `order` (-1: that workgroup leaves); the second phase takes the two lists the
+// caller has sorted the parked paths into (po_launch_nw_sort by StdLists::flag: in->nw_list and StdLists::left2).  The caller has set in->nw_keys to the block that
+// holds the lists (std_lists) and scale_kernel has reset them.  Only for a batch po_launch_newton would run fixed.
+extern "C" hipError_t po_launch_newton_std(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
+    using namespace po;
+    if (!s->two || !fixed(*s, in) || !in->nw_keys) return hipErrorInvalidValue;
+    const bool second = in->nw_phase == 2;
+    const StdLists sl = std_lists(in->nw_keys, in->B);
+    hipError_t e;
+    DevBatch std_ = *in, rest = *in;
+    if (second) rest.nw_list = sl.left2;
+    else {
+        if ((e = call(form, kObjFixNewtonStd1, kLaunchStdSelect, *s, in, P, st)) != hipSuccess) return e;
+        std_.order = sl.order; rest.order = sl.left1;
+    }
+    if ((e = call(form, second ? kObjFixNewtonStd2 : kObjFixNewtonStd1, kLaunchNewtonStd, *s, &std_, P, st)) != hipSuccess) return e;
+    return call(form, second ? kObjFixNewton2 : kObjFixNewton1, kLaunchNewton, *s, &rest, P, st);
+}
 extern "C" hipError_t po_launch_newton_fallback(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchFallback, s, in, P, st); }
 // OSQP's polish (po_params.polish) on the paths the two solve launches reported solved; same stream, after them (a shape without a polish kernel: nothing to do)
 extern "C" hipError_t po_launch_polish(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) { return launch_two_level(form, po::kLaunchPolish, s, in, P, st); }
@@ -135,7 +155,12 @@ namespace po {
 // the parked paths (keys[b] >= 0) in descending key order, ties in path order (a stable counting sort: deterministic): list[0] = count, list[1 ..] = path ids.
 // One workgroup of kNwSortThreads threads, thread t owns the contiguous range of paths [t * per, (t + 1) * per).
 constexpr int kNwSortThreads = 256;  // (kNwKeys = 32 keys x 257 counters = 33 KB of LDS)
-__global__ __launch_bounds__(kNwSortThreads) void nw_sort_kernel(const int *keys, int B, int *list) {
+// flag != nullptr (the split between the constant-class second launch and the one without the constants, po_launch_newton_std): TWO workgroups, the first lists the
+// paths with flag[b] == 1 in list, the second those with flag[b] == 0 in list2 — side by side, in the time of one
+__global__ __launch_bounds__(kNwSortThreads) void nw_sort_kernel(const int *keys, int B, int *list, const int *flag, int *list2) {
+    const int want = blockIdx.x == 0 ? 1 : 0;
+    if (blockIdx.x != 0) list = list2;
+    auto key = [&](int b) { return (flag == nullptr || flag[b] == want) ? keys[b] : -1; };
     // (round 6) a thread's counters live in its own COLUMN of the LDS table (no conflicts, one read-modify-write per path instead of a 32-way compare over registers), its
     // first 16 keys are loaded at once and kept for the scatter pass, and the rows are scanned by whole waves: 22 -> ~10 us for 4 096 paths
     __shared__ int cnt[kNwKeys][kNwSortThreads + 1];
@@ -144,14 +169,14 @@ __global__ __launch_bounds__(kNwSortThreads) void nw_sort_kernel(const int *keys
     constexpr int kCache = 16;
     int kc[kCache];
 #pragma unroll
-    for (int i = 0; i < kCache; ++i) kc[i] = (lo + i < hi) ? keys[lo + i] : -1;
+    for (int i = 0; i < kCache; ++i) kc[i] = (lo + i < hi) ? key(lo + i) : -1;
 #pragma unroll
     for (int k = 0; k < kNwKeys; ++k) cnt[k][t] = 0;
 #pragma unroll
     for (int i = 0; i < kCache; ++i)
         if (kc[i] >= 0) cnt[kc[i] < kNwKeys ? kc[i] : kNwKeys - 1][t] += 1;
     for (int b = lo + kCache; b < hi; ++b) {
-        const int k = keys[b];
+        const int k = key(b);
         if (k >= 0) cnt[k < kNwKeys ? k : kNwKeys - 1][t] += 1;
     }
     __syncthreads();
@@ -191,15 +216,15 @@ __global__ __launch_bounds__(kNwSortThreads) void nw_sort_kernel(const int *keys
     for (int i = 0; i < kCache; ++i)
         if (kc[i] >= 0) place(lo + i, kc[i]);
     for (int b = lo + kCache; b < hi; ++b) {
-        const int k = keys[b];
+        const int k = key(b);
         if (k >= 0) place(b, k);
     }
 }
 
 }  // namespace po
 // sliced Newton launches: the parked paths ordered by expected remaining work (one small workgroup; ~10 us)
-extern "C" hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipStream_t st) {
-    hipLaunchKernelGGL(po::nw_sort_kernel, dim3(1), dim3(po::kNwSortThreads), 0, st, keys, B, list);
+extern "C" hipError_t po_launch_nw_sort(const int *keys, int B, int *list, const int *flag, int *list2, hipStream_t st) {
+    hipLaunchKernelGGL(po::nw_sort_kernel, dim3(flag ? 2 : 1), dim3(po::kNwSortThreads), 0, st, keys, B, list, flag, list2);
     return hipGetLastError();
 }
 // ---- the resolution of a batch's shape, and the queries that read it: functions of the resolved shape and of class constants of its table row; no object is asked
@@ -242,13 +267,15 @@ extern "C" int po_newton_park_doubles(int form, int N, int C, int keep) { return
 extern "C" int po_has_polish_kernel(int form, int N, int C, int keep) { return resolved(form, N, C, keep).polish; }
 extern "C" int po_has_fixed_length(int form, int N, int C, int keep) { return resolved(form, N, C, keep).fixed; }
 
-// nw_keys ([B]) / fb_count (one int), when set: reset by the same launch (scale_kernel) — the solve needs no fill of its own between its launches
-extern "C" hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, int *nw_keys, int *fb_count, hipStream_t st) {
+// nw_keys ([B]) / fb_count (one int) / std_block (the lists of the constant-class Newton kernels: std_lists, po_device.hpp), when set: reset by the same launch
+// (scale_kernel) — the solve needs no fill of its own between its launches
+extern "C" hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, int *nw_keys, int *fb_count, int *std_block,
+                                      hipStream_t st) {
     using namespace po;
     const int bs = 64, gs = (in->B + bs - 1) / bs;
-    if (form == F_KP) hipLaunchKernelGGL(scale_kernel<F_KP>, dim3(gs), dim3(bs), 0, st, *in, *P, passes, sc, nw_keys, fb_count);
-    else if (form == F_KPC) hipLaunchKernelGGL(scale_kernel<F_KPC>, dim3(gs), dim3(bs), 0, st, *in, *P, passes, sc, nw_keys, fb_count);
-    else hipLaunchKernelGGL(scale_kernel<F_K>, dim3(gs), dim3(bs), 0, st, *in, *P, passes, sc, nw_keys, fb_count);
+    if (form == F_KP) hipLaunchKernelGGL(scale_kernel<F_KP>, dim3(gs), dim3(bs), 0, st, *in, *P, passes, sc, nw_keys, fb_count, std_block);
+    else if (form == F_KPC) hipLaunchKernelGGL(scale_kernel<F_KPC>, dim3(gs), dim3(bs), 0, st, *in, *P, passes, sc, nw_keys, fb_count, std_block);
+    else hipLaunchKernelGGL(scale_kernel<F_K>, dim3(gs), dim3(bs), 0, st, *in, *P, passes, sc, nw_keys, fb_count, std_block);
     return hipGetLastError();
 }
 

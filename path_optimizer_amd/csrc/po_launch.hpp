@@ -11,9 +11,12 @@ namespace po {
 struct DevBatch; struct DevParams;                                                   // po_device.hpp
 struct Shape;                                                                        // po_solve_common.hpp
 // what an object of the solve kernels holds: the uniform-row-class / general variant of the solve kernels (the general object: also the polish kernels), the Newton
-// kernels (both phases and the fallback), or the length-specialised uniform warm start / first / second Newton launch
-enum { kObjUni, kObjGen, kObjNewton, kObjFixUni, kObjFixNewton1, kObjFixNewton2 };
-enum { kLaunchSolve, kLaunchNewton, kLaunchFallback, kLaunchPolish };  // what an entry is asked to launch (Newton: phase 1 or 2 by DevBatch::nw_phase)
+// kernels (both phases and the fallback), or the length-specialised uniform warm start / first / second Newton launch / the two Newton launches with the standard row
+// classes as compile-time constants
+enum { kObjUni, kObjGen, kObjNewton, kObjFixUni, kObjFixNewton1, kObjFixNewton2, kObjFixNewtonStd1, kObjFixNewtonStd2 };
+// what an entry is asked to launch (Newton: phase 1 or 2 by DevBatch::nw_phase; NewtonStd: the constant-class kernel of a fixed length; StdSelect: the kernel that
+// decides which paths that kernel gets)
+enum { kLaunchSolve, kLaunchNewton, kLaunchFallback, kLaunchPolish, kLaunchNewtonStd, kLaunchStdSelect };
 // the groups the shapes are dealt to the objects in (KP's two-level shapes: one lane per chunk / role-split / multi-group / the wide role-split shapes by SPL; the single-level mapping)
 enum { kGrpLane = 1, kGrpSplit = 2, kGrpMulti = 4, kGrpW56 = 8, kGrpW7 = 16, kGrpW8 = 32, kGrpOne = 64 };
 // Everything the host asks about the shape of a batch (formulation, N, C, keep), filled ONCE per call by po_resolve_solve and handed to the launches.  A plain struct
@@ -38,12 +41,13 @@ extern "C" {
 int po_resolve_solve(int form, int N, int C, int keep, po::SolveShape *s);
 hipError_t po_launch_solve(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
 hipError_t po_launch_newton(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
+hipError_t po_launch_newton_std(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
 hipError_t po_launch_newton_fallback(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
 hipError_t po_launch_polish(int form, const po::SolveShape *s, const po::DevBatch *in, const po::DevParams *P, hipStream_t st);
 hipError_t po_launch_finalize_status(po_info *info, int B, hipStream_t st);
 hipError_t po_launch_mark_unavailable(po_info *info, int B, int refine, int polish, hipStream_t st);
-hipError_t po_launch_nw_sort(const int *keys, int B, int *list, hipStream_t st);
-hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, int *nw_keys, int *fb_count, hipStream_t st);
+hipError_t po_launch_nw_sort(const int *keys, int B, int *list, const int *flag, int *list2, hipStream_t st);
+hipError_t po_launch_scale(int form, const po::DevBatch *in, const po::DevParams *P, int passes, double *sc, int *nw_keys, int *fb_count, int *std_block, hipStream_t st);
 hipError_t po_launch_assemble(int form, const po::DevBatch *in, const po::DevParams *P, double *l, double *u, double *dyn, hipStream_t st);
 size_t po_lds_bytes(int form, int N, int C, int keep);
 int po_shape_threads(int form, int N, int C, int keep);
@@ -79,7 +83,9 @@ int po_plan_solve(int form, int N, int keep, int B, int ragged, int refine, int 
     X(po_newton_k, F_K, kObjNewton, kGrpLane)                                   \
     X(po_solve_kp_fix_uni, F_KP, kObjFixUni, kGrpLane)                          \
     X(po_newton_kp_fix1, F_KP, kObjFixNewton1, kGrpLane)                        \
-    X(po_newton_kp_fix2, F_KP, kObjFixNewton2, kGrpLane)
+    X(po_newton_kp_fix2, F_KP, kObjFixNewton2, kGrpLane)                        \
+    X(po_newton_kp_fixstd1, F_KP, kObjFixNewtonStd1, kGrpLane)                  \
+    X(po_newton_kp_fixstd2, F_KP, kObjFixNewtonStd2, kGrpLane)
 #if defined(PO_DEV_HEADLINE) && !defined(PO_ENTRY)  // `make dev` links three of the KP objects: the dispatcher built for it answers hipErrorNotSupported for the others
 #define PO_OBJECT_ATTR __attribute__((weak))
 #else

@@ -124,11 +124,16 @@ template <int F> __device__ void class_scaling(const DevParams &P, int N, int ke
 
 // one thread per path.  It runs first in every solve and visits every path, so it also resets what the Newton launches of the solve count in (both optional): the park
 // keys — nw_keys[b] = -1: a path that no workgroup of the first sliced launch reaches (a malformed caller-side order) is not parked — and the count of the fall-back work list.
-template <int F> __global__ void scale_kernel(DevBatch in, DevParams P, int passes, double *sc, int *nw_keys, int *fb_count) {
+template <int F> __global__ void scale_kernel(DevBatch in, DevParams P, int passes, double *sc, int *nw_keys, int *fb_count, int *std_block) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= in.B) return;
     if (nw_keys) nw_keys[b] = -1;
     if (fb_count && b == 0) *fb_count = 0;
+    if (std_block) {  // the lists of the constant-class Newton kernels (std_lists, po_device.hpp): empty, no path flagged
+        const StdLists sl = std_lists(std_block, in.B);
+        sl.left1[b] = -1; sl.order[b] = -1; sl.flag[b] = 0;
+        if (b == 0) sl.left2[0] = 0;
+    }
     const double *s = in.ref_s + (size_t)b * in.N;
     int N = in.N, C = in.C;
     if (in.n_points) { N = in.n_points[b]; N = N < 2 ? 2 : (N > in.N ? in.N : N); C = (F == F_K) ? N - 1 : (N + in.keep - 2) / in.keep; }

@@ -101,11 +101,12 @@ struct SolveSchedule {
     bool state;               // the solve kernels leave the ADMM state in pol_buf: OSQP's polish (opt-in) and the Newton refinement pick it up there
     bool split, sliced;       // refine = 2: plain warm-start launches, the Newton refinement as its own launch (sliced: as two, below), then the fallback launch for the later rounds
     bool polish, fixed;       // the polish launch follows / the length-specialised kernels run the batch
+    bool std_classes;         // ... and their Newton launches are the constant-class pair, each followed by the kernel without the constants over what it left
     bool no_refine, no_polish;  // asked for, but this shape has no kernel for it: status_refine / status_polish = PO_NOT_AVAILABLE on every path instead of the "off" value 0
     bool read_back;           // the fallback launch is issued only when the count read back says that a path is on its list (refine_chain = 3: always issued, asynchronous)
     int warm_decades;         // the warm start stops where round 0 of the rounds stops: at 10^warm_decades x eps
 };
-SolveSchedule plan_solve(const po_params &p, const po::SolveShape &s, int B, bool ragged, int nw_slice, bool slice_forced, bool fixed_on, int wave_slots) {
+SolveSchedule plan_solve(const po_params &p, const po::SolveShape &s, int B, bool ragged, int nw_slice, bool slice_forced, bool fixed_on, int wave_slots, bool classes_on) {
     SolveSchedule q{};
     const int rounds = p.refine_rounds > 1 ? p.refine_rounds : 1;
     const int rounds_total = rounds + ((p.refine && p.refine_extra_rounds > 0) ? p.refine_extra_rounds : 0);
@@ -119,6 +120,7 @@ SolveSchedule plan_solve(const po_params &p, const po::SolveShape &s, int B, boo
     // per path (NT = 64: 4 x CUs paths at a time) and at least two rounds of them (config 3 4.76 -> 4.06 ms; two-wave shapes and batches of one round gain nothing or lose).
     q.sliced = q.split && nw_slice > 0 && (slice_forced || (B >= 2 * wave_slots && s.nt == 64));
     q.fixed = fixed_on && !ragged && s.fixed;  // the switch is on, every path has the batch's length and the length is a listed one
+    q.std_classes = q.fixed && q.split && classes_on;  // (a launch of the solve tests every path's classes: no property of the batch is asked here)
     q.no_refine = p.refine == 2 && !q.split;
     q.no_polish = p.polish && !q.polish;
     q.read_back = p.refine_chain != 3;
@@ -132,15 +134,25 @@ int provision(po_handle h, const po::SolveShape &s, size_t B, SolveSchedule *q) 
     if (h->env_cycles) PO_TRY(h->dbg_buf.ensure(sizeof(long long) * 16 * B));
     PO_TRY(h->scale_buf.ensure(sizeof(double) * 64 * B));
     if (q->state) PO_TRY(h->pol_buf.ensure(sizeof(double) * (size_t)s.state_doubles * B));
+    h->std_B = 0; h->std_flag_at = h->std_left2_at = -1;  // (what the read-backs of po_debug_get look at: nothing yet from THIS solve)
     if (!q->split) return PO_OK;
     PO_TRY(h->fb_buf.ensure(sizeof(int) * (B + 1)));
     PO_TRY(h->fb_host.ensure(64));
-    if (q->sliced && (h->nw_state_buf.ensure(sizeof(double) * (size_t)s.park_doubles * B) || h->nw_idx_buf.ensure(sizeof(int) * (2 * B + 1)))) {
+    // (keys [B] and list [B + 1]; the constant-class kernels keep their lists behind them and need the block on an unsliced solve too — without it they are not run)
+    const size_t idx_bytes = sizeof(int) * (q->std_classes ? po::std_lists_ints(B) : 2 * B + 1);
+    if (q->sliced && (h->nw_state_buf.ensure(sizeof(double) * (size_t)s.park_doubles * B) || h->nw_idx_buf.ensure(idx_bytes))) {
         (void)hipGetLastError();
         h->nw_state_buf.release();
         q->sliced = false;
     }
+    if (q->std_classes && h->nw_idx_buf.ensure(idx_bytes)) {
+        (void)hipGetLastError();
+        q->std_classes = false;
+    }
     h->nw_last_B = q->sliced ? (int)B : 0;
+    h->std_flag_at = q->std_classes ? (long)po::std_flag_index(B) : -1;
+    h->std_B = q->std_classes ? (int)B : 0;
+    h->std_left2_at = q->std_classes && q->sliced ? (long)po::std_left2_index(B) : -1;
     return PO_OK;
 }
 
@@ -157,8 +169,10 @@ int enqueue(po_handle h, int form, const po::SolveShape &s, const SolveSchedule 
     h->timed_phases = false;
     // per-path equilibration (h->params.scaling class-level Ruiz passes; 0 -> identity), then the fused solve.  The same launch resets what the Newton launches count in:
     // the fall-back work list's count, and the park keys to -1 (a path no workgroup of the first sliced launch reaches — a malformed caller-side order — is not parked)
-    HIP_TRY(po_launch_scale(form, &D, &P, h->params.scaling, static_cast<double *>(h->scale_buf.p), q.sliced ? static_cast<int *>(h->nw_idx_buf.p) : nullptr,
-                            q.split ? static_cast<int *>(h->fb_buf.p) : nullptr, h->stream));
+    // ... and the lists and the count of the constant-class Newton kernels
+    int *const nw_block = static_cast<int *>(h->nw_idx_buf.p);
+    HIP_TRY(po_launch_scale(form, &D, &P, h->params.scaling, static_cast<double *>(h->scale_buf.p), q.sliced ? nw_block : nullptr,
+                            q.split ? static_cast<int *>(h->fb_buf.p) : nullptr, q.std_classes ? nw_block : nullptr, h->stream));
     if (q.split) {
         po::DevParams P1 = P;  // the warm start: the plain solve kernels, stopped where round 0 of the rounds stops (10^(R-1) x eps)
         for (int r = 0; r < q.warm_decades; ++r) { P1.eps_abs *= 10.0; P1.eps_rel *= 10.0; }
@@ -167,18 +181,25 @@ int enqueue(po_handle h, int form, const po::SolveShape &s, const SolveSchedule 
         D.nw_follows = 0;
         HIP_TRY(hipEventRecord(h->evp[0], h->stream));
         D.fb_list = static_cast<int *>(h->fb_buf.p);  // (its count: zeroed by scale_kernel)
+        // every Newton launch below is ONE launch, or — the constant-class kernels — a pair: that kernel over the paths with the standard row classes, then the kernel
+        // without the constants over the others (po_launch_newton_std; the lists live behind nw_keys)
+        const auto launch_newton = q.std_classes ? &po_launch_newton_std : &po_launch_newton;
+        if (q.std_classes) D.nw_keys = nw_block;
         if (q.sliced) {
             D.nw_state = static_cast<double *>(h->nw_state_buf.p); D.nw_stride = s.park_doubles;
-            D.nw_keys = static_cast<int *>(h->nw_idx_buf.p); D.nw_list = D.nw_keys + B;
+            D.nw_keys = nw_block; D.nw_list = D.nw_keys + B;
             P.ref_nw_slice = h->nw_slice;
             D.nw_phase = 1;
-            HIP_TRY(po_launch_newton(form, &s, &D, &P, h->stream));
-            HIP_TRY(po_launch_nw_sort(D.nw_keys, B, D.nw_list, h->stream));
+            HIP_TRY(launch_newton(form, &s, &D, &P, h->stream));
+            if (q.std_classes) {  // the parked paths in two lists: the standard ones for the constant-class kernel, the others for the kernel without the constants
+                const po::StdLists sl = po::std_lists(D.nw_keys, B);
+                HIP_TRY(po_launch_nw_sort(D.nw_keys, B, D.nw_list, sl.flag, sl.left2, h->stream));
+            } else HIP_TRY(po_launch_nw_sort(D.nw_keys, B, D.nw_list, nullptr, nullptr, h->stream));
             D.nw_phase = 2;
-            HIP_TRY(po_launch_newton(form, &s, &D, &P, h->stream));
+            HIP_TRY(launch_newton(form, &s, &D, &P, h->stream));
             D.nw_phase = 0;
         } else {
-            HIP_TRY(po_launch_newton(form, &s, &D, &P, h->stream));
+            HIP_TRY(launch_newton(form, &s, &D, &P, h->stream));
         }
         HIP_TRY(hipEventRecord(h->evp[1], h->stream));
         h->timed_phases = true;
@@ -252,7 +273,7 @@ int po_plan_solve(int form, int N, int keep, int B, int ragged, int refine, int 
     if (s.lds > po::kLdsLimit) return PO_ERR_UNSUPPORTED;
     po_params p{};
     p.refine = refine; p.refine_rounds = refine_rounds; p.refine_extra_rounds = refine_extra_rounds; p.refine_chain = refine_chain; p.polish = polish;
-    const SolveSchedule q = plan_solve(p, s, B, ragged != 0, nw_slice, slice_forced != 0, fixed_on != 0, wave_slots);
+    const SolveSchedule q = plan_solve(p, s, B, ragged != 0, nw_slice, slice_forced != 0, fixed_on != 0, wave_slots, /* classes_on: the handle's default */ true);
     for (int v : {(int)q.split, (int)q.state, (int)q.polish, (int)q.sliced, (int)q.fixed, (int)q.no_refine, (int)q.no_polish, (int)q.read_back, q.warm_decades}) *out++ = v;
     return PO_OK;
 }
@@ -268,7 +289,7 @@ int po_solve_batch_device(po_handle h, const po_batch_in *in, const po_batch_out
     po::DevParams P = make_dev_params(h->params, in->formulation, in->keep);
     po::DevBatch D = fill_dev_batch(h, in, out, d);
     const po::SolveShape &s = d.shape;
-    SolveSchedule q = plan_solve(h->params, s, in->B, in->n_points != nullptr, h->nw_slice, h->nw_slice_forced, h->fixed_length, h->wave_slots);
+    SolveSchedule q = plan_solve(h->params, s, in->B, in->n_points != nullptr, h->nw_slice, h->nw_slice_forced, h->fixed_length, h->wave_slots, h->fixed_classes);
     h->fixed_used = D.fixed_len = q.fixed;  // (the one place "fixed" is decided: the launchers read it from D, po_debug_get "fixed_length_used" from the handle)
     PO_TRY(provision(h, s, (size_t)in->B, &q));
     PO_TRY(enqueue(h, in->formulation, s, q, D, P));
@@ -434,7 +455,7 @@ int po_scaling_batch(po_handle h, const po_batch_in *in, double *out) {
         din.ref_s = rs;
         const po::DevParams P = make_dev_params(h->params, in->formulation, in->keep);
         const po::DevBatch D = fill_dev_batch(h, &din, nullptr, d);
-        HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, sc, nullptr, nullptr, h->stream));  // (diagnostic: no solve follows, nothing to reset)
+        HIP_TRY(po_launch_scale(in->formulation, &D, &P, h->params.scaling, sc, nullptr, nullptr, nullptr, h->stream));  // (diagnostic: no solve follows, nothing to reset)
         return PO_OK;
     });
 }

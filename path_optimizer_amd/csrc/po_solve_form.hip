@@ -2,7 +2,8 @@
 // formulation and group the object holds, in the kind of kernel it holds —
 //   kObjUni / kObjGen    the solve kernels, uniform-row-class / general loop variant (the general object also holds the polish kernels);
 //   kObjNewton           the Newton refinement (po_params.refine = 2): newton_kernel + newton_fallback_kernel, nothing else (built with -DPO_REF=3: po_device.hpp);
-//   kObjFix...           KP only: the length-specialised kernels of the headline shape (Makefile: PO_FIXED_N) — the uniform warm start / the first / the second Newton launch.
+//   kObjFix...           KP only: the length-specialised kernels of the headline shape (Makefile: PO_FIXED_N) — the uniform warm start / the first / the second Newton launch,
+//                        and the two Newton launches with the standard row classes as compile-time constants (kObjFixNewtonStd1 / 2: newton_kernel_std; the first also holds newton_std_select_kernel).
 // Each object exports ONE entry, named like the object.  The dispatcher (po_kernels.hip) has resolved the shape and its LDS bytes and calls the one object that holds the
 // row; the entry launches the instance that EQUALS the shape, and answers hipErrorNotSupported when it has none.  -DPO_DEV_HEADLINE (dev builds only) keeps just one shape.
 #include "po_solve_common.hpp"
@@ -24,10 +25,11 @@ constexpr Object me() {
     return {-1, -1, 0};
 }
 static_assert(me().form >= 0, "PO_ENTRY names no object of PO_SOLVE_OBJECTS");
+constexpr bool newton_object(int kind) { return kind == kObjNewton || kind == kObjFixNewton1 || kind == kObjFixNewton2 || kind == kObjFixNewtonStd1 || kind == kObjFixNewtonStd2; }
 #ifdef PO_REF
-static_assert(me().kind == kObjNewton || me().kind == kObjFixNewton1 || me().kind == kObjFixNewton2, "-DPO_REF=3 is for the Newton objects");
+static_assert(newton_object(me().kind), "-DPO_REF=3 is for the Newton objects");
 #else
-static_assert(me().kind != kObjNewton && me().kind != kObjFixNewton1 && me().kind != kObjFixNewton2, "the Newton objects build with -DPO_REF=3");
+static_assert(!newton_object(me().kind), "the Newton objects build with -DPO_REF=3");
 #endif
 // does an object of groups G instantiate this row?  (dev builds: the one shape of -DPO_DEV_SPL / NT / NWX — default BASELINE config 3 — whatever its group)
 [[maybe_unused]] constexpr bool holds(int G, bool two, int spl, int nt, int nwx, int g) {
@@ -78,10 +80,16 @@ template <int F, int G, bool FB> hipError_t launch_newton(const Shape &s, size_t
     return hipErrorNotSupported;
 }
 // the length-specialised kernels: the dispatcher has checked is_fixed_shape; a length that is not on the list is an error
-template <int F, int KIND> hipError_t launch_fixed(const DevBatch *in, const DevParams *P, size_t lds, hipStream_t st) {
+template <int F, int KIND> hipError_t launch_fixed(int launch, const DevBatch *in, const DevParams *P, size_t lds, hipStream_t st) {
 #define PO_X(N_)                                                                                                                                \
     if (in->N == N_) {                                                                                                                          \
         if constexpr (KIND == kObjFixUni) return launch1(&solve_kernel_fast<F, kFixSpl, kFixNt, true, true, 1, N_>, in, P, kFixNt, lds, st);    \
+        else if constexpr (KIND == kObjFixNewtonStd1) {                                                                                         \
+            /* (no LDS: the kernel touches none, and with the solve's 38 KB only four of its short workgroups fit a CU) */               \
+            if (launch == kLaunchStdSelect) return launch1(&newton_std_select_kernel<F, kFixSpl, kFixNt, N_>, in, P, kFixNt, 0, st);            \
+            return launch1(&newton_kernel_std<F, kFixSpl, kFixNt, 1, 1, N_>, in, P, kFixNt, lds, st);                                           \
+        }                                                                                                                                       \
+        else if constexpr (KIND == kObjFixNewtonStd2) return launch1(&newton_kernel_std<F, kFixSpl, kFixNt, 1, 2, N_>, in, P, kFixNt, lds, st);    \
         else return launch1(&newton_kernel<F, kFixSpl, kFixNt, 1, KIND == kObjFixNewton2 ? 2 : 1, N_>, in, P, kFixNt, lds, st);                 \
     }
     PO_FIXED_LIST(PO_X)
@@ -94,7 +102,7 @@ template <int F, int KIND, int G> hipError_t entry(int launch, const Shape &s, s
         if (launch == kLaunchNewton) return launch_newton<F, G, false>(s, lds, in, P, st);
         if (launch == kLaunchFallback) return launch_newton<F, G, true>(s, lds, in, P, st);
         return hipErrorNotSupported;
-    } else return launch_fixed<F, KIND>(in, P, lds, st);
+    } else return launch_fixed<F, KIND>(launch, in, P, lds, st);
 }
 }  // namespace
 extern "C" hipError_t PO_ENTRY(int launch, const po::Shape &s, size_t lds, const po::DevBatch *in, const po::DevParams *P, hipStream_t st) {
