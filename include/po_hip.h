@@ -303,7 +303,9 @@ int po_debug_set(po_handle h, const char *key, int value);
  * address of the handle's map layer — layer 0 of the stack (0: no map; does not synchronise — po_set_map_occupancy_device / po_set_map_stack_occupancy_device with
  * an unchanged size and layer count must leave it where it is); "map_layers" = M, the number of layers the handle holds (0: no map; does not synchronise); "fixed_length_used" = 1 when the last solve ran the
  * length-specialised kernels, 0 when it ran the generic ones (does not synchronise); "fixed_classes_used" = how many paths of the last solve the constant-class Newton
- * kernels took (0: it did not run them); "dp_waves_used" = 8 or 1, the waves per instance of the handle's last DP lattice
+ * kernels took (0: it did not run them), "fixed_classes_flag:<b>" = whether they took path b of it (1 yes, 0 no, -1 it did not run them; b outside the last batch:
+ * PO_ERR_INVALID), "newton_list_ok" = 1 when the work lists of the second sliced Newton launch are what the sort promises — every parked path exactly once, keys
+ * descending, ties in path order, and with the constant-class kernels each path on the list of the kernel its flag names (0 not, -1 not sliced); "dp_waves_used" = 8 or 1, the waves per instance of the handle's last DP lattice
  * search — po_dp_search_batch* or the search inside po_plan_batch* (0: none yet; does not synchronise): one wave above 512 instances, under "dp_one_wave", and when
  * the eight-wave reduction scratch does not fit in LDS beside the spline; "smooth_variant_used" = 100 * kind + 10 * waves + WPE, the instantiation of the smoothing kernel
  * that the handle's last po_smooth_batch* call launched: kind 0 .. 2, 1 / 4 / 8 waves per QP, WPE the occupancy bound it was compiled for (11, 42, 43 or 82; 0: no call

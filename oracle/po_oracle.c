@@ -1805,6 +1805,19 @@ int po_oracle_solve_batch(const po_params *p, const po_batch_in *in, const po_ba
         double *xb = out->x ? out->x + (size_t)b * (size_t)n : NULL;
         if (out->states) memset(out->states + o * 5, 0, sizeof(double) * (size_t)N * 5);
         if (xb) memset(xb, 0, sizeof(double) * (size_t)n);
+        /* A NaN among the inputs the QP is built from (Fast::load, csrc/po_fast.inc, reads the same ones): never "solved", nothing computed, zero outputs.  A NaN
+         * BOUND would otherwise vanish — fmin / fmax drop a NaN operand, the row acts as unbounded and the path comes back solved with an obstacle ignored. */
+        int nan_in = isnan(in->goal_z[b]) || isnan(in->ref_z[o + (size_t)Nb - 1]) || isnan(in->x0[(size_t)b * 3]) || isnan(in->x0[(size_t)b * 3 + 1]) ||
+                     isnan(in->x0[(size_t)b * 3 + 2]);
+        for (int j = 0; j < Nb && !nan_in; ++j) {
+            nan_in = isnan(in->ref_s[o + j]) || (j + 1 < Nb && isnan(in->ref_k[o + j])) || (in->formulation == PO_KPC && in->max_k && isnan(in->max_k[o + j])) ||
+                     (in->formulation == PO_KPC && in->max_kp && j < Cb && isnan(in->max_kp[o + j]));
+            for (int c = 0; c < 8 && !nan_in; ++c) nan_in = isnan(in->bounds[(o + j) * 8 + c]);
+        }
+        if (nan_in) {
+            if (out->info) { memset(&out->info[b], 0, sizeof(po_info)); out->info[b].status = PO_STATUS_NON_FINITE; }
+            continue;
+        }
         int r = po_oracle_solve_path(in->formulation, p, Nb, in->keep, in->ref_x + o, in->ref_y + o, in->ref_z + o,
                                      in->ref_k + o, in->ref_s + o, in->bounds + o * 8, in->x0 + (size_t)b * 3,
                                      in->goal_z[b], in->max_k ? in->max_k + o : NULL, in->max_kp ? in->max_kp + o : NULL,

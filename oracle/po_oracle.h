@@ -82,7 +82,8 @@ int po_oracle_solve_path(int form, const po_params *p, int N, int keep,
                          double *out_states /*[N][5]*/, double *out_x /*[n] or NULL*/,
                          double *out_y /*[m] or NULL*/, po_info *info);
 
-/* Batch driver over po_oracle_solve_path (sequential; used by tests and the CPU baseline). */
+/* Batch driver over po_oracle_solve_path (sequential; used by tests and the CPU baseline).  Like the device engine it does not solve a path with a NaN among the
+ * inputs the QP is built from (bounds, ref_k, ref_s, x0, goal_z, the last ref_z, KPC's limits): status PO_STATUS_NON_FINITE, every other po_info field and the outputs 0. */
 int po_oracle_solve_batch(const po_params *p, const po_batch_in *in, const po_batch_out *out);
 
 /* Solver-independent KKT certificate of (x,y) for the assembled QP:

@@ -401,7 +401,7 @@ class Engine:
 
     def debug_set(self, key: str, value: int):
         """po_debug_set: developer A/B switches (identity_order, debug_cycles, host_threads, smooth_seq, smooth_waves, smooth_nopad, smooth_debug, dp_one_wave, newton_slice, fixed_length, fixed_classes).
-        Read-only keys go through debug_get: fixed_length_used, fixed_classes_used (paths of the last solve the constant-class Newton kernels took), dp_waves_used (8 or 1: the variant of the last DP lattice search; dp_one_wave = 1 forces 1), smooth_variant_used (100 * kind + 10 * waves + WPE of the last smoothing launch), fallback_paths,
+        Read-only keys go through debug_get: fixed_length_used, fixed_classes_used (paths of the last solve the constant-class Newton kernels took), "fixed_classes_flag:<b>" (did they take path b of it: 1 / 0, -1 when they did not run, PoError for a b outside the batch), newton_list_ok (the second sliced launch's lists: 1 in order, complete and — two lists — split as the flags say), dp_waves_used (8 or 1: the variant of the last DP lattice search; dp_one_wave = 1 forces 1), smooth_variant_used (100 * kind + 10 * waves + WPE of the last smoothing launch), fallback_paths,
         newton_parked, map_ptr, map_layers."""
         _check(lib().po_debug_set(self._h, key.encode(), int(value)))
 

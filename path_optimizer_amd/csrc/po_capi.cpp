@@ -18,6 +18,7 @@
 #include "../../include/po_hip.h"
 #include "po_handle.hpp"
 #include "po_launch.hpp"
+#include "po_list_check.hpp"
 #include "po_map.hpp"
 #include "po_smooth.hpp"
 
@@ -224,6 +225,22 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
         for (int f : flag) *value += f != 0;
         return PO_OK;
     }
+    if (k.rfind("fixed_classes_flag:", 0) == 0) {  // "fixed_classes_flag:<b>": was path b of the last solve flagged standard (1) or not (0)?  -1: it did not run the
+        // constant-class kernels; a path that is none of the last solve's: PO_ERR_INVALID.  (A count hides two wrong flags that cancel: tests/test_fixed_classes_edges.py)
+        const char *const num = key + sizeof("fixed_classes_flag:") - 1;
+        char *end = nullptr;
+        const long long b = std::strtoll(num, &end, 10);
+        if (end == num || *end != '\0' || *num < '0' || *num > '9' || b < 0) return PO_ERR_INVALID;
+        *value = -1;
+        if (!h->nw_idx_buf.p || h->std_flag_at < 0 || h->std_B <= 0) return PO_OK;
+        if (b >= h->std_B) return PO_ERR_INVALID;
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        int f = 0;
+        HIP_TRY(hipMemcpy(&f, static_cast<int *>(h->nw_idx_buf.p) + h->std_flag_at + b, sizeof(int), hipMemcpyDeviceToHost));
+        *value = f != 0;
+        return PO_OK;
+    }
     if (k == "newton_parked") {  // sliced Newton launches: how many paths of the last solve went on into the second launch (-1: the last solve was not sliced)
         *value = -1;
         if (!h->nw_idx_buf.p || h->nw_last_B <= 0) return PO_OK;
@@ -245,28 +262,12 @@ int po_debug_get(po_handle h, const char *key, long long *value) {
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->stream));
         const int B = h->nw_last_B;
-        // (the constant-class kernels ran: two lists, each ordered like that, which hold every parked path exactly once between them)
-        const bool two_lists = h->std_left2_at >= 0;
-        std::vector<int> kl(two_lists ? (size_t)h->std_left2_at + (size_t)B + 1 : 2 * (size_t)B + 1);
+        // (the constant-class kernels ran: two lists, each ordered like that, which hold every parked path exactly once between them — the first only paths flagged
+        // standard, the second only the others: po_list_check.hpp)
+        const bool two_lists = h->std_left2_at >= 0 && h->std_flag_at >= 0;
+        std::vector<int> kl(two_lists ? (size_t)h->std_flag_at + (size_t)B : 2 * (size_t)B + 1);
         HIP_TRY(hipMemcpy(kl.data(), h->nw_idx_buf.p, sizeof(int) * kl.size(), hipMemcpyDeviceToHost));
-        const int *keys = kl.data();
-        int parked = 0, listed = 0;
-        for (int b = 0; b < B; ++b) parked += keys[b] >= 0;
-        bool ok = true;
-        std::vector<char> seen((size_t)B, 0);
-        for (const int *list : {kl.data() + B, two_lists ? kl.data() + h->std_left2_at : nullptr}) {
-            if (!list) continue;
-            const int n = list[0];
-            ok = ok && n >= 0 && n <= B;
-            for (int i = 0; ok && i < n; ++i) {
-                const int b = list[1 + i];
-                ok = b >= 0 && b < B && keys[b] >= 0 && !seen[(size_t)b];
-                if (ok) seen[(size_t)b] = 1;
-                if (ok && i > 0) { const int a = list[i]; ok = keys[a] > keys[b] || (keys[a] == keys[b] && a < b); }
-            }
-            listed += n;
-        }
-        ok = ok && listed == parked;
+        const bool ok = po::newton_list_ok(kl.data(), kl.data() + B, two_lists ? kl.data() + h->std_left2_at : nullptr, two_lists ? kl.data() + h->std_flag_at : nullptr, B);
         *value = ok ? 1 : 0;
         return PO_OK;
     }
