@@ -301,9 +301,6 @@ template <int F> __device__ __forceinline__ double p_diag_node(int comp, int j, 
 }
 
 __device__ __forceinline__ int ctl_index(int i, int keep) { return keep == 4 ? (i >> 2) : (i / keep); }
-__device__ __forceinline__ bool last_of_group(int i, int N, int keep) {
-    return (i == N - 2) || (keep == 4 ? (((i + 1) & 3) == 0) : ((i + 1) % keep == 0));
-}
 
 // Bit-mixing bijection of a workgroup index onto [0, B): workgroup i runs on XCD i mod 8 (a static partition of every launch), so kernels
 // whose work per instance varies take instance perm_index(blockIdx.x, ...) instead of blockIdx.x.  bits = ceil(log2 B), 0 = identity.
@@ -322,7 +319,7 @@ __device__ __forceinline__ int perm_index(unsigned i, int bits, int B) {
 // rows of 16 lanes (row_shr 1, 2, 4, 8: lane 15 of a row ends up with the row's total), then the four row totals through v_readlane.  Every lane returns the same bits.
 // Measured per kernel (A/B in one run, BASELINE config 3): newton_kernel 6.60 -> 5.92 ms per launch with the DPP form, the ADMM hot kernel 1.04 -> 1.10 ms (its
 // residual passes run every 25 iterations only, and the allocation at the 512-register limit does not like the change): the DPP form in the Newton objects only.
-#if defined(PO_REF) && PO_REF == 3 && !defined(PO_SHFL_REDUCE)
+#if defined(PO_REF) && PO_REF == 3
 #define PO_DPP_REDUCE 1
 #endif
 #ifdef PO_DPP_REDUCE
@@ -398,9 +395,6 @@ __device__ __forceinline__ double wave_max(double v) {
 // -------------------------------------------------------------------------------------------------------
 // Every functor carries the per-path equilibration of the row kind it is visiting: W[r] = E_r^2 / c (step
 // multiplier) and E[r] (bounds are classified on the SCALED problem, like OSQP's set_rho_vec).
-__device__ __forceinline__ double row_rho(double l, double u, double e, double w, double rho, double rho_eq) {
-    return rho_of(l * e, u * e, rho, rho_eq) * w;
-}
 // The class of a row (0 inequality, 1 equality, 2 free) depends only on its scaled bounds, i.e. it is fixed for the
 // whole solve: it is computed once per path and packed 2 bits per row; the passes decode instead of re-deriving it.
 __device__ __forceinline__ unsigned row_class(double l, double u, double e) {
@@ -473,10 +467,6 @@ template <bool UNI, bool FIRST, int NR, bool NWT = false> struct RhsFnX {  // NW
     const double *W;
     unsigned cls;
     double rr[NR];
-    __device__ __forceinline__ void prepare(unsigned pat, int nrows) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r) rr[r] = r < nrows ? class_rho(pat, r, W[r], rho, rho_eq) : 0.0;
-    }
     template <int MASK, class TL, class TU> __device__ __forceinline__ void row(int r, double c0, double c1, double c2, double c3, double c4, TL l, TU u) {
         const double rw = UNI ? rr[r] : class_rho(cls, r, W[r], rho, rho_eq);
         const double vv = v[r * stride];

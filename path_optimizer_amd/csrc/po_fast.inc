@@ -1,25 +1,82 @@
-// po_fast.inc — v2 "register-resident" fused solve kernel (included by po_kernels.hip inside namespace po).
+// po_fast.inc — the fused, register-resident solve of one path per workgroup (included by po_solve_common.hpp inside namespace po).  This comment is the MAP of the
+// file: its sections, each under a banner `==== [name] ====` (search for the bracketed name) that says what the section reads, writes and serves.
 //
-// Same mathematics as the generic kernel above (same rows, same block LDL', same ADMM), different mapping:
-//   * thread t owns the SPL consecutive stages j = t*SPL .. t*SPL+SPL-1 and control t; ALL of their
-//     state (x, v, bounds, transition coefficients, slack-elimination data) lives in VGPRs for the whole
-//     solve — inputs are read from HBM exactly once, coalesced, at the start of the kernel;
-//   * LDS holds only what is indexed across lanes: the block-LDL' factor (18 doubles/stage + 4/control),
-//     the right-hand side / solution of the linear solve, and small exchange buffers  (~37 KB at N=200
-//     => 4 paths per CU, one per SIMD);
-//   * the sequential substitution runs on lanes 0..3 of wave 0, one matrix ROW per lane (3 FMAs per step),
-//     operands broadcast with v_readlane (no LDS round trip on the dependent chain), factor rows
-//     prefetched one step ahead.
-// Valid when N <= NT*SPL and C <= NT (host picks NT, SPL); otherwise the generic kernel is used.
+// One struct, Fast<F, SPL, NT, TWO, NWX, NFIX>, is the per-lane view of a path: every lane keeps the state of its own stages (x, the one-number-per-row v, bounds,
+// transition coefficients, slack-elimination data: LaneState) in registers for the whole kernel — the inputs are read from HBM once, coalesced — and LDS (LayoutF) holds
+// only what is indexed across lanes: the block-LDL' factor, the scan tables and small exchange buffers.  Every member is forced inline; the kernels are what the compiler sees.
+//
+//   F     formulation (F_KP, F_KPC, F_K: FormTraits, po_device.hpp)
+//   SPL   stage slots per lane
+//   NT    threads per workgroup (64: one wave; 128 / 256: several)
+//   TWO   false: SINGLE-LEVEL mapping — the substitution is one sequential chain over all stages (any keep; the fall-back of the shapes below)
+//         true:  TWO-LEVEL mapping — a lane's stages are a chunk, the chunks are solved in parallel and their boundaries by a scan over lanes
+//   NWX   lane layout of the two-level mapping: 1 one lane per chunk; 2 role-split (a chunk on two lanes), 3 role-split of an odd keep; 4 / 5 multi-group (keep 1 / 2:
+//         several control groups per lane).  The details are at the top of [fast_core]
+//   NFIX  path length at compile time for the LDS layout and the global offsets (0: at run time); KP, NWX 1 only ([fast_core], DESIGN.md section 19)
+//
+// Kernels ([kernels]; instantiated by po_solve_form.hip from the table of po_solve_common.hpp, launched by po_kernels.hip):
+//   solve_kernel_fast<F, SPL, NT, TWO, UNI, NWX, NFIX>   load, ADMM loop (UNI: the variant for wave-uniform row classes), output — also the warm start of the Newton launches
+//   newton_kernel / newton_kernel_std<..., PH, NFIX>     the Newton refinement (po_params.refine = 2), single or sliced in two phases; _std: standard row classes as constants
+//   newton_std_select_kernel                             which paths of a fixed-length batch have the standard classes
+//   newton_fallback_kernel                               later rounds of the paths a Newton launch handed back
+//   polish_kernel                                        OSQP's polish (po_params.polish)
+//
+// THE ORDER IS PART OF THE CODE.  The sections from [fast_core] to [output] are ONE struct body: a member function may be used before its definition, a nested type
+// (Cert, Tr, ChunkEl, ChunkRun, FwdGroup, ...) may not, so a section that is ever cut out into a file of its own is cut where it stands and included there.  The
+// shipped kernels are verified for the register allocation they have, so an edit that only moves or documents text is gated by the device code itself:
+// tools/device_text_diff.py against a build of the parent must report 0 differ (DESIGN.md section 38).
+//
+//   before the struct   [layout]            dev macros; LaneState, LayoutF, lds_bytes_fast; bcast, path_n, path_c        (all the host dispatcher uses)
+//                       [row_fns]           row functors of the polish and of the reclassification
+//   the struct          [fast_core]         parameters, lane geometry, row-class and scale accessors, load(); then:
+//                         [single_level]      !TWO: factor_blocks, factor_chain, rhs_pass, chain_solve, update_pass (Cert), residual_pass, rescale_pass
+//                         [two_prims]         TWO:  chunk geometry, 9-records, factor accessors, DPP moves, xchg / wshfl, apply_E*, mul_G*
+//                         [two_factor]              factor_blocks_two, transition (Tr)
+//                         [two_pivot_scan]          the pivot chain as a scan over chunks: factor_pivots_scan (NW 1), factor_pivots_scan2 (NW 2)
+//                         [two_factor_chain]        factor_chain_two: scan or sequential recursion, then the scan tables of the solve
+//                         [two_sweeps]              chunk-local sweeps, the role-split hand-off, the one-wave boundary scans, solve_split (NW 2)
+//                         [two_rhs]                 rhs_pass_two, classify
+//                         [two_solve]               solve_two (NW 1)
+//                         [two_update]              update_pass_two, nbr_x, residual_pass_two
+//                         [newton_passes]           state_io / park_io, block reductions, reclass_pass, the Newton passes nw_*
+//                         [polish_passes]           pol_init, pol_reset, pol_eval
+//                         [output]                  output_pass
+//   after the struct    [loops]             admm_loop, refine_phase_newton
+//                       [kernels]           the kernels above (newton_kernel's text: po_newton_kernel.inc, included twice)
 
+// ==================== [layout] ====================
+// what exists before the struct Fast, and all of po_fast.inc that the host dispatcher (po_kernels.hip) uses: the dev macros, the per-lane state
+// (LaneState), the map of the workgroup's dynamic LDS (LayoutF; lds_bytes_fast is its host-side size, used by lds_of) and three free helpers.  Live for every instantiation.
+//
+// LaneState is plain registers: nothing here is indexed at run time (every loop over it is unrolled), which is what lets the compiler split it.  Who writes what:
+//   load()                          lb, ub, maxk, kin / dsin / kout / dsout, trin / trout, bin0, mkp, cls / clse / clsc (bound_classes); zeroes the rest
+//   rhs passes                      bx, bxu (right-hand side), gs / gsu;   the solves: bx, bxu (solution), bnext, bprev
+//   update passes                   x, u, su, vl, vd, vdo, vend, vc
+//   factor_blocks / _two            hi, hv, hiu, hus (general variant; the UNI variant reads them from LDS, rrb)
+//   reclass_pass                    cls / clse / clsc (refinement);   the polish and a parked Newton path: pc / pce / pcc
+// LayoutF, in doubles from the LDS base S.  SINGLE-LEVEL (!two): bz, bu, tk (rhs / solution), fac, facu (factor); wt = bz (factor scratch, idle while factorising).
+// TWO-LEVEL: fac, facu (factor, 9-records: idx9(), [two_prims]), phi (scan tables, one 9-record region per level), ex (multi-wave mailboxes and reduction scratch),
+// rseg, mail (segmented scan, NT > 64 and one lane per chunk), hx0 / hx1 (role-split hand-off slots).  ALIASES THAT MATTER: wt = bz = phi — the (k, ds, trig) table of
+// the sequential factorisation and the [N][2] + [N] scratch of output_pass lie on the scan tables, which are rebuilt by every factor_chain_two and dead once the last
+// solve has run; role-split: ex = hx1 — a block reduction (block_any, block_sum2, the residual passes) overwrites hand-off slot 1, so it never runs inside solve_split.
+// Both mappings: cst (LDS copy of the path's equilibration block, scale_to_lds) and rrb (per-factorisation uniform row steps and, UNI, slack-elimination data).
+// Before the kernel zeroes its LDS, the first words at S also carry the block votes of inputs_have_nan() and classify().
+//
+// The dev macros are defined HERE, once, for every section: none relies on a macro that another happens to define (function-local helper macros are #undef'd where they end).
 #ifndef PO_KERNEL_ATTR  // dev: an occupancy attribute on every solve kernel of a build (e.g. -DPO_KERNEL_ATTR='__attribute__((amdgpu_waves_per_eu(2,2)))')
 #define PO_KERNEL_ATTR
 #endif
+// the lane id through an empty asm: what derives from it is recomputed after this point, not hoisted (admm_loop, [loops])
 #define PO_FRESH_LANE_ID(fx) asm volatile("" : "+v"((fx).tid))
 #ifdef PO_MARKS  // dev: phase markers in the assembly listing (hipcc -S -DPO_MARKS)
 #define PO_MARK(name) asm volatile("; PO_MARK " name)
 #else
 #define PO_MARK(name)
+#endif
+#ifdef PO_NW_TRACE  // dev: cycles of the parts of a factorisation into Fast::dbgc (factor_chain_two, which declares tf_; printed by refine_phase_newton)
+#define PO_FC_TICK(i) { const long long n_ = __builtin_readcyclecounter(); dbgc[i] += n_ - tf_; tf_ = n_; }
+#else
+#define PO_FC_TICK(i)
 #endif
 
 // G: control groups per lane (1, or — multi-group mapping of keep 1 / 2, KP only — SPL / keep)
@@ -97,6 +154,8 @@ template <int F> struct LayoutF {
         total = o;
     }
 };
+// nwx: 1 one lane per chunk, 2 role-split (chunk = 2 spl stages), 3 role-split of an odd keep (chunk = 2 spl - 1 stages), 4 / 5 multi-group (spl / 1, spl / 2 groups per lane)
+template <int F> size_t lds_bytes_fast(int N, int C, int spl, bool two, int nt, int nwx = 1) { return sizeof(double) * (size_t)LayoutF<F>(N, C, spl, two, nt, (nwx == 2 || nwx == 3) ? 2 : 1, (nwx == 2 || nwx == 3) ? 2 * spl - (nwx == 3 ? 1 : 0) : 0, nwx == 4 ? spl : (nwx == 5 ? spl / 2 : 1)).total; }
 
 __device__ __forceinline__ double bcast(double v, int k) {  // value of lane k (k uniform) to every lane
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -117,6 +176,13 @@ template <int F> __device__ __forceinline__ int path_c(const DevBatch &in, int b
     return (path_n(in, b) + in.keep - 2) / in.keep;
 }
 
+// ==================== [row_fns] ====================
+// the row functors that belong to Fast's later phases (the ones of the ADMM iteration itself are in po_device.hpp): handed to local_rows / end_rows /
+// ctl_rows, which call row<MASK>(r, coefficients, l, u) once per constraint row of a stage or control.  They touch no LDS: they read and write the lane-state words they
+// are pointed at (st.vl / vend / vc, the packed codes st.pc*) and their own accumulators.  TWO only (the phases that use them exist on the two-level mapping only).
+//   PolWrap, PolInitFn, PolResetFn, PolEvalFn, PolRes    the polish: [polish_passes], and PolWrap around the inner functors of the <POL> passes
+//                                                        (factor_blocks_two, rhs_pass_two, update_pass_two); polish_kernel
+//   ReclassFn                                            reclass_pass ([newton_passes]): refine_phase_newton, at every step (mode 3) and on leaving the phase (mode 2)
 // ---- polish (OSQP polish.c, po_params.polish) ----------------------------------------------------------------------------------
 // The reduced KKT system of the polish, [[P + dI, Aa'], [Aa, -dI]] on the rows Aa of the active set, is in condensed form
 // (P + dI + Aa' Aa / d) x = -q + Aa' b / d: the SAME block-tridiagonal matrix the ADMM iteration factorises, with sigma -> delta, the row step of an
@@ -213,6 +279,14 @@ struct ReclassFn {
     }
 };
 
+// ==================== [fast_core] ====================
+// the struct Fast opens here, with what every mapping and phase uses; the sections up to [output] are the rest of its body, and the struct closes after [output].
+// Live for every instantiation.  Here: the template parameters and what derives from them (NW, ODD, CH, HW, GK, NG, kFixC), the lane geometry (clane, wrole, stage, cs,
+// cidx, has_ctl, the group predicates, psel), the accessors of the uniform row data (rrb: uhi, uhv, uhi_at, k_rr*; cls_of, kpc_c3) and of the equilibration block
+// (sc -> global, then LDS cst after scale_to_lds: Wloc .. cD, eq_row_step / eq_row_scale), stage_in / dyn_in / dyn_out, and the one-time load().
+//   LDS     scale_to_lds writes cst; inputs_have_nan votes through the first words at S (NT > 64; before the kernel zeroes its LDS); the rrb accessors only read
+//   lanes   load() fills the inputs' part of LaneState from HBM, zeroes the iterate and sets cls / clse / clsc (bound_classes) and nan_in
+//   called  by every kernel of [kernels] right after constructing the object: load(), [inputs_have_nan()], scale_to_lds(); the accessors by every pass
 // NW = 1: lane t owns the whole chunk t (SPL stages = one control group, or K's SPL nodes).
 // NW = 2: ROLE-SPLIT mapping (round 5; keep_control_steps_ 5 .. 8, where one lane per group spills hundreds of registers): chunk t = control group t = CH = 2 SPL - ODD stages
 //         lives on TWO lanes — role A (lane t of the first half of the block) owns chunk stages 0 .. SPL-1, role B (lane t of the second half) owns chunk stages SPL .. CH-1 in
@@ -267,9 +341,6 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
     mutable double nw_req = 0.0;
 #ifdef PO_NW_TRACE
     mutable long long dbgc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // dev: cycles of the parts of a factorisation
-#define PO_FC_TICK(i) { const long long n_ = __builtin_readcyclecounter(); dbgc[i] += n_ - tf_; tf_ = n_; }
-#else
-#define PO_FC_TICK(i)
 #endif
     __device__ __forceinline__ double eq_step(double rho) const { return nw_req > 0.0 ? nw_req : kRhoEqOverIneq * rho; }
 
@@ -308,8 +379,6 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
     // does the transition INTO / OUT OF own stage q belong to the own chunk's control group?  (the transition into chunk stage 0 is the previous group's)
     __device__ __forceinline__ bool in_own_group(int q) const { return cs(q) > 0; }
     __device__ __forceinline__ bool out_own_group(int q) const { return cs(q) == CH - 1; }
-    // is the stage before own slot q on this lane?  (slot 0 never; slot 1 of role B of an odd keep neither: its slot 0 is empty)
-    __device__ __forceinline__ bool prev_is_own(int q) const { return q > qoff(); }
     // own (the value at slot q - 1) or nbr (the neighbouring lane's): a compile-time choice except for slot 1 of the role-split mapping of an odd keep
     __device__ __forceinline__ double psel(int q, double own, double nbr) const {
         if constexpr (NW == 2 && ODD) return q == 0 ? nbr : (q == 1 ? (wrole() == 1 ? nbr : own) : own);
@@ -461,7 +530,19 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         } else return wave_bad;
     }
 
-    // ---- factor step A: per-stage blocks into LDS (same slot layout as the generic kernel) ----
+// ==================== [single_level] ====================
+// members of Fast, part 1: the SINGLE-LEVEL mapping (TWO == false; NWX 1, NFIX 0).  Every lane owns SPL consecutive stages and control `tid`
+// for any keep; the linear solve is ONE sequential substitution over all N stages on lanes 0..3 of wave 0 (one matrix row per lane, operands through v_readlane,
+// factor rows prefetched).  The shapes the two-level mapping does not cover run here.  Nothing in this section is instantiated when TWO, except rescale_pass at its end,
+// which both mappings use (registers only).
+//   LDS     fac [N][18] = (G -> Ginv 0..5 | E -> L 6..14 | ws -> l_u 15..17), facu [C][4] = (1 / p_u, l_x): written by factor_blocks, replaced in place by factor_chain;
+//           wt (= bz: idle while factorising) and tk: factor_blocks' hand-over to factor_chain; bz, bu, tk: right-hand side (rhs_pass) -> solution (chain_solve),
+//           read back by update_pass; residual_pass publishes x through bz / bu (publish_x); the cross-wave reductions (NT > 64) go through wt = bz as well
+//   lanes   reads the inputs load() left; factor_blocks writes hi, hv, hiu, hus; rhs_pass gs, gsu; update_pass x, u, su and every v; rescale_pass every v
+//   called  admm_loop<UNI = false> ([loops]) from solve_kernel_fast<.., TWO = false, ..>: factor_blocks + factor_chain per factorisation, then per iteration
+//           rhs_pass -> chain_solve -> update_pass<CERT>, residual_pass at the checks, rescale_pass when rho changes
+// Cert (declared here) is also the return type of update_pass_two: this section stays ahead of [two_update].
+    // ---- factor step A: per-stage blocks into LDS (18 doubles per stage: G 0..5 | E 6..14 | ws 15..17; the control's pivot in facu) ----
     __device__ __forceinline__ void factor_blocks(LS &st, double rho) const {
         const double rho_eq = kRhoEqOverIneq * rho;
 #pragma unroll
@@ -1184,6 +1265,14 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
     }
 
 
+// ==================== [two_prims] ====================
+// members of Fast, part 2: the primitives of the TWO-LEVEL mapping, shared by all of its lane layouts (NWX 1 .. 5) and by every later section.
+// TWO only.  Chunk geometry (nq_* / nst_*: the transitions / stages of the own chunk, and of the own lane's share of it, that exist); the 9-record layout of fac and
+// phi (idx9, load9 / store9: four 16-byte pairs + a single per lane) with the accessors FA / FAt (fac), FU / FUg / FUc (facu), PL (phi), RS (rseg); lane moves of a
+// double (dpp_mov / dpp_mov0, xchg, wshfl); the regenerated coupling block (apply_E, apply_Et) and Ginv products (mul_Gr, mul_G).
+//   LDS     the accessors address fac, facu, phi, rseg; xchg uses the mailboxes at ex (NT > 64 only: one barrier); nothing else is touched
+//   lanes   no LaneState field is read or written here
+//   called  from every two-level section below ([two_*], [newton_passes], [polish_passes])
     // =====================================================================================================
     // TWO-LEVEL MODE (keep == SPL, or no held controls): thread t's chunk == control group t.
     //
@@ -1228,7 +1317,6 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
     __device__ __forceinline__ double &FUc(int c, int i) const { return S[L.facu + ((c % NG) * 4 + i) * L.TP + c / NG]; }  // control c of the path
     __device__ __forceinline__ double &PL(int lvl, int t, int i) const { return S[idx9(L.phi + lvl * 9 * L.TP, t, i)]; }
 
-    // value(s) held by thread tid+delta (out of range: own value).  One barrier per call; callers alternate buf.
     // DPP lane moves of a double (two 32-bit halves).  Lanes without a source keep `keep`.
     template <int CTRL> static __device__ __forceinline__ double dpp_mov(double v, double keep) {
         const int lo = __builtin_amdgcn_update_dpp(__double2loint(keep), __double2loint(v), CTRL, 0xf, 0xf, false);
@@ -1243,9 +1331,9 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
     }
     static constexpr int kDppRowShl = 0x100, kDppRowShr = 0x110, kDppWaveShl1 = 0x130, kDppWaveShr1 = 0x138;
     // neighbour exchange: out = v of lane tid + delta (own value at the ends).  One wave and |delta| == 1: a DPP wave shift (VALU latency);
-    // one wave otherwise: LDS crossbar permute; several waves: through LDS with a barrier.
+    // one wave otherwise: LDS crossbar permute; several waves: the wave shift, and the lane at a wave boundary through mailbox `buf` (0 / 1) of L.ex with ONE barrier —
+    // callers alternate buf, so that a call never overwrites what a slower wave still reads from the call before.
     template <int CNT> __device__ __forceinline__ void xchg(const double *v, int delta, double *out, int buf) const {
-#ifndef PO_NO_DPP_XCHG
         if constexpr (NT == 64) {
             if (__builtin_constant_p(delta) && (delta == 1 || delta == -1)) {
 #pragma unroll
@@ -1253,7 +1341,6 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
                 return;
             }
         }
-#endif
         if constexpr (NT == 64) {  // one wave: LDS crossbar permute, no memory traffic, no barrier
             const int p = tid + delta;
             const int src = (p >= 0 && p < 64 ? p : tid) << 2;
@@ -1326,6 +1413,15 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         mul_Gr(g, y, z);
     }
 
+// ==================== [two_factor] ====================
+// members of Fast, part 3: factorisation step A of the two-level mapping, and the coupling block of one transition.  TWO only, every NWX.
+//   factor_blocks_two<UNI, POL>   every lane condenses the rows of its own stages (slacks eliminated) into (H_q | ws_q) and its controls' pivots: what the pivot
+//                                 chain ([two_pivot_scan], [two_factor_chain]) starts from.  POL: the rows of the polish's active set (PolWrap)
+//   transition (Tr)               E and the control column of the transition out of own stage q, regenerated from the lane's (k, ds, trig): used by both pivot scans
+//   LDS     writes fac (one 9-record per own stage), facu element 0 (the pivot before elimination), rrb (lane 0: the uniform row steps of this factorisation; UNI: the
+//           slack-elimination data too); role-split: the other role's share of the pivot goes through hx1 (= ex), one barrier
+//   lanes   reads the inputs, cls / clse / clsc (general variant) or pat_* (UNI), pc* (POL); writes hi, hv (general variant only), hiu, hus
+//   called  admm_loop and refine_phase_newton ([loops]) and polish_kernel, always followed by factor_chain_two
     template <bool UNI = false, bool POL = false> __device__ __forceinline__ void factor_blocks_two(LS &st, double rho) const {
         const double rho_eq = eq_step(rho);
         double huu_dyn[NG];
@@ -1427,29 +1523,6 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         }
         __syncthreads();
     }
-
-
-    // ---------------------------------------------------------------------------------------------------------------------------------
-    // The pivot chain of the block LDL' as a SCAN over chunks (one-wave-per-chunk mappings, NW == 1).
-    //
-    // The sequential recursion  G_{j+1} = H_{j+1} - E_j G_j^-1 E_j' (- the rank-one term of the group's control)  walks N - 1 dependent 3 x 3 steps
-    // (215 k cycles at N = 200: 14 iterations' worth, paid at every refactorisation).  It is a linear-fractional map of the pivot, and such maps
-    // compose: for chunk t, eliminating its interior stages and its control from the chunk's own terms, with its first stage x_a and the first stage of
-    // the next chunk x_b RETAINED, leaves a quadratic [[A, B], [B', D]] on (x_a, x_b); the correction the chunk passes on is
-    //       Delta_{t+1} = D - B' (A + Delta_t)^-1 B                       (G of stage 4 t = H + Delta_t),
-    // and two consecutive chunks combine by eliminating the shared stage:  K = (A2 + D1)^-1 (an SPD pivot: a Schur complement of a principal
-    // submatrix),  A12 = A1 - B1 K B1',  B12 = -B1 K B2,  D12 = D2 - B2' K B2.  So: (1) every lane reduces its own chunk (SPL - 1 eliminations + the
-    // control), (2) Kogge-Stone over the chunks (log2 levels, 21 doubles per element, through LDS), (3) every lane runs the ordinary recursion over its
-    // own SPL stages from G = H + Delta_t and stores exactly what the sequential loop stored (Ginv_j | w_j per stage, 1 / p_u | l_x per control).
-    // Same factorisation in a different elimination order.  MEASURED (config 3): 31 k cycles instead of 215 k.  What the scan hands chunk t and what chunk
-    // t - 1's own recursion passes on are the same quantity computed two ways; they agree to rounding (2e-15 relative), i.e. the stored factors are those of M
-    // plus a symmetric block-diagonal perturbation of that size, which moves the QP's solution by ~3 x as much — harmless.  Step (4) checks exactly that
-    // agreement at every factorisation and falls back to the sequential recursion when it fails (never observed to trigger: tools/scan_fallbacks.py).  The check
-    // is not decoration: while this function was developed, two builds of it (3-stage chunks, then 5-stage chunks after a restructuring) produced factors that
-    // cost the refinement 10 - 20 extra iterations per path and moved its result by 1e-2, on every path of the shape and only in builds that did not consume
-    // the chunk's outgoing correction — a code-generation problem, not rounding (the same source with the value consumed matches the oracle to 1e-11, and
-    // so does every variant since the check consumes it).  tests/test_refine.py::test_device_refine_every_keep_value_matches_oracle pins every chunk shape.
-    // ---------------------------------------------------------------------------------------------------------------------------------
     struct Tr { double E[9], wn0[3]; };  // transition j -> j + 1:  E = M[x_{j+1}, x_j],  wn0 = M[x_{j+1}, u] (the part this transition contributes)
     __device__ __forceinline__ Tr transition(const LS &st, int q, const double re[T::NDYN]) const {
         const int qn = q + 1 < SPL ? q + 1 : q;
@@ -1470,6 +1543,38 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         if constexpr (F == F_K) { if (stage(q) + 1 <= N - 2) tr.E[8] += -P.w_cr; }
         return tr;
     }
+
+// ==================== [two_pivot_scan] ====================
+// members of Fast, part 4: factorisation step B of the two-level mapping as a scan over chunks.  TWO only.  3 x 3 helpers (sym_full, mul33,
+// mul33t, sym_sub_abt), the chunk element and its composition (ChunkEl, combine_el), and the two scans: factor_pivots_scan (NW 1: NWX 1, 4, 5) and
+// factor_pivots_scan2 (NW 2: NWX 2, 3; ChunkRun is its hand-over between the roles).  TWINS: the two functions are the same four steps written twice — scan2 splits
+// steps (1) and (3) over the two roles of a chunk; a change to the arithmetic of one belongs in the other.
+//   LDS     reads fac / facu as factor_blocks_two left them; double-buffers the scan elements (2 x 21 x TP doubles; scan2: its hand-over in the second buffer) in phi,
+//           whose tables are dead here and rebuilt by factor_chain_two right after; commits fac / facu (Ginv | w, 1 / p_u | l_x) only when the cross-check passed;
+//           the vote goes through block_any (ex, NT > 64)
+//   lanes   reads the transition inputs (kin, dsin, kout, dsout, trin, trout) through transition(); writes nothing
+//   called  factor_chain_two ([two_factor_chain]) only; false sends it down the sequential recursion
+    // ---------------------------------------------------------------------------------------------------------------------------------
+    // The pivot chain of the block LDL' as a SCAN over chunks (one lane per chunk, NW == 1).
+    //
+    // The sequential recursion  G_{j+1} = H_{j+1} - E_j G_j^-1 E_j' (- the rank-one term of the group's control)  walks N - 1 dependent 3 x 3 steps
+    // (215 k cycles at N = 200: 14 iterations' worth, paid at every refactorisation).  It is a linear-fractional map of the pivot, and such maps
+    // compose: for chunk t, eliminating its interior stages and its control from the chunk's own terms, with its first stage x_a and the first stage of
+    // the next chunk x_b RETAINED, leaves a quadratic [[A, B], [B', D]] on (x_a, x_b); the correction the chunk passes on is
+    //       Delta_{t+1} = D - B' (A + Delta_t)^-1 B                       (G of chunk t's first stage = H + Delta_t),
+    // and two consecutive chunks combine by eliminating the shared stage:  K = (A2 + D1)^-1 (an SPD pivot: a Schur complement of a principal
+    // submatrix),  A12 = A1 - B1 K B1',  B12 = -B1 K B2,  D12 = D2 - B2' K B2.  So: (1) every lane reduces its own chunk (SPL - 1 eliminations + the
+    // control), (2) Kogge-Stone over the chunks (log2 levels, 21 doubles per element, through LDS), (3) every lane runs the ordinary recursion over its
+    // own SPL stages from G = H + Delta_t and stores exactly what the sequential loop stored (Ginv_j | w_j per stage, 1 / p_u | l_x per control).
+    // Same factorisation in a different elimination order.  MEASURED (config 3): 31 k cycles instead of 215 k.  What the scan hands chunk t and what chunk
+    // t - 1's own recursion passes on are the same quantity computed two ways; they agree to rounding (2e-15 relative), i.e. the stored factors are those of M
+    // plus a symmetric block-diagonal perturbation of that size, which moves the QP's solution by ~3 x as much — harmless.  Step (4) checks exactly that
+    // agreement at every factorisation and falls back to the sequential recursion when it fails (never observed to trigger: tools/scan_fallbacks.py).  The check
+    // is not decoration: while this function was developed, two builds of it (3-stage chunks, then 5-stage chunks after a restructuring) produced factors that
+    // cost the refinement 10 - 20 extra iterations per path and moved its result by 1e-2, on every path of the shape and only in builds that did not consume
+    // the chunk's outgoing correction — a code-generation problem, not rounding (the same source with the value consumed matches the oracle to 1e-11, and
+    // so does every variant since the check consumes it).  tests/test_refine.py::test_device_refine_every_keep_value_matches_oracle pins every chunk shape.
+    // ---------------------------------------------------------------------------------------------------------------------------------
     static __device__ __forceinline__ void sym_full(const double s[6], double f[9]) {
         f[0] = s[0]; f[1] = s[1]; f[2] = s[2]; f[3] = s[1]; f[4] = s[3]; f[5] = s[4]; f[6] = s[2]; f[7] = s[4]; f[8] = s[5];
     }
@@ -1515,10 +1620,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         for (int i = 0; i < 9; ++i) o.B[i] = -o.B[i];
         return o;
     }
-#ifndef PO_SCAN_TOL
-#define PO_SCAN_TOL 1e-11
-#endif
-    static constexpr double kScanTol = PO_SCAN_TOL;
+    static constexpr double kScanTol = 1e-11;  // step (4): largest relative disagreement between the scan's and the recursion's correction that still commits the scan
     __device__ __forceinline__ bool factor_pivots_scan(LS &st, const double re[T::NDYN]) const {
         static_assert(NW == 1, "one lane per chunk");
         const int nst = nst_own(), nq = nq_own();  // own stages / own outgoing transitions
@@ -2061,6 +2163,16 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         return !any_bad;
     }
 
+// ==================== [two_factor_chain] ====================
+// members of Fast, part 5: factor_chain_two, factorisation step B of the two-level mapping and the tables of its solve.  TWO only, every NWX.
+// Three parts (the PO_FC_TICK buckets of a PO_NW_TRACE build): (0) the pivot chain as a scan ([two_pivot_scan]); when its cross-check fails, the sequential block
+// LDL' over all stages, every lane running the same recursion on broadcast reads; (1) Phi_t of every full chunk, column by column through the homogeneous forward sweep
+// (sweep_forward<2> / split_forward<2>, [two_sweeps]); (2) the prefix tables of the boundary scans: one wave — in-row levels 0..3, Q^incl (4), Q^suf (5) of the
+// 16-lane DPP rows; SEG (NT > 64, one lane per chunk) — levels 0..2 inside 8-lane segments, Q^incl (3), Q^suf (4) and the segment products R^(l) in rseg.
+//   LDS     reads fac / facu as factor_blocks_two left them and replaces them by the factor (Ginv | w, 1 / p_u | l_x); the fall-back's (k, ds, trig) table [N][4] lies
+//           on phi (LayoutF's wt alias), which is rebuilt right after; writes phi (every level) and rseg; role-split: the Phi columns cross the roles through hx0 / hx1
+//   lanes   reads the transition inputs; writes nothing (the homogeneous sweeps take no right-hand side and store nothing)
+//   called  after every factor_blocks_two: admm_loop, refine_phase_newton ([loops]), polish_kernel
     // sequential block LDL' (every lane of every wave runs the same scalar recursion on broadcast reads — no
     // cross-wave hand-off needed; thread 0 stores).  The coupling blocks are regenerated from the owner's registers.
     __device__ __forceinline__ void factor_chain_two(LS &st, double rho) const {
@@ -2068,16 +2180,12 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         double re[T::NDYN];
 #pragma unroll
         for (int r = 0; r < T::NDYN; ++r) re[r] = eq_row_step(rho_eq, r);
-#ifndef PO_SEQ_FACTOR  // the pivot chain as a scan over chunks (factor_pivots_scan); -DPO_SEQ_FACTOR: the sequential recursion everywhere (A/B)
-        constexpr bool kScanPivots = true;
-#else
-        constexpr bool kScanPivots = false;
-#endif
         bool scanned = false;
 #ifdef PO_NW_TRACE
         long long tf_ = __builtin_readcyclecounter();
 #endif
-        if constexpr (kScanPivots) { if constexpr (NW == 1) scanned = factor_pivots_scan(st, re); else scanned = factor_pivots_scan2(st, re); }
+        // the pivot chain as a scan over chunks ([two_pivot_scan]); false: its cross-check failed, the sequential recursion below runs instead
+        if constexpr (NW == 1) scanned = factor_pivots_scan(st, re); else scanned = factor_pivots_scan2(st, re);
         PO_FC_TICK(0)
         if (!scanned) {
             // publish per-stage (k, ds) of the outgoing transitions so that every lane can rebuild E_j
@@ -2342,6 +2450,19 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         PO_FC_TICK(2)
     }
 
+// ==================== [two_sweeps] ====================
+// members of Fast, part 6: the chunk-local substitution sweeps of the two-level solve, and the whole solve of the role-split mapping.  TWO only.
+//   sweep_forward<MODE> / sweep_backward<STORE>     NW 1 (NWX 1, 4, 5): the own chunk on the own lane — called by solve_two ([two_solve]) and, MODE 2, by factor_chain_two
+//   hx_put / hx_get, load_fu, split_forward<MODE> / split_backward<STORE>, scan_forward_wave / scan_backward_wave, solve_split
+//                                                   NW 2 (NWX 2, 3): a chunk across its two lanes — solve_split is called by admm_loop and refine_phase_newton in
+//                                                   solve_two's place, split_forward<2> by factor_chain_two
+//   LDS     reads fac (one 9-record per stage, requested a stage ahead), facu (once per solve, by the caller), phi (the scans); role-split: the 3-vector (+ control
+//           accumulator) that crosses the role boundary goes through hx0 (A -> B forward, B -> next chunk's A backward, role A's scan result)
+//           and hx1 (B -> A backward, role B's scan result), one barrier each; hx1 is also ex — no block reduction may run between these barriers
+//   lanes   in: st.bx, st.bxu (right-hand side, rhs_pass_two), st.bnext (NW 1: the next chunk's first right-hand side); out: st.bx, st.bxu (solution), st.bnext / st.bprev
+//           (the neighbouring chunks' boundary values, for update_pass_two)
+// TWINS: scan_forward_wave / scan_backward_wave are the one-wave PO_FWD_LEVEL / PO_BWD_LEVEL scans of solve_two ([two_solve]) with the lane taken from clane() and
+// the row totals read at lane_base; a change to one belongs in the other.
     // Local forward sweep over the first nq transitions of the own chunk.
     //   MODE 0: rhs from st.bx, nothing stored (zero-inflow pass); MODE 1: as 0 but stores z_q = Ginv_q y_q into st.bx;
     //   MODE 2: homogeneous (rhs = 0), used to build Phi.
@@ -2541,6 +2662,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
     }
     // one-wave boundary scans on the chunk lanes of the calling role (the DPP row scans of solve_two; tables of chunks that are not full are zero).  NT = 64: the role's lanes
     // are one half of the wave (two DPP rows); the row totals are read with v_readlane at the role's lane offset.
+    // (twin: the one-wave branches of solve_two's F2 / B2, [two_solve] — calling these from there changes solve_two's device code, so the text stands twice)
     __device__ __forceinline__ void scan_forward_wave(double s[3], int lane_base) const {
         const int tfull = (N - 1) / CH;
         const int tp_ = clane() < L.TP ? clane() : tfull;
@@ -2647,6 +2769,17 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         if (wrole() == 1) { hx_get(L.hx1, clane(), st.bprev); st.bprev[3] = st.bxu[0]; }
     }
 
+// ==================== [two_rhs] ====================
+// members of Fast, part 7: the right-hand side pass of the two-level mapping, and the vote on uniform row classes.  TWO only, every NWX.
+//   rhs_pass_two<UNI, FIRST, POL, NWT>   the first of an iteration's three passes: sigma x + A' rho (2 clip(v) - v) per own stage and control, slacks eliminated (gs / gsu
+//                                        keep the slacks' part for update_pass_two).  POL: rows of the polish's active set; NWT: minus the gradient (Newton direction)
+//   classify                             are the row classes of the bounds one pattern on every lane?  Sets pat_loc / pat_ctl / pat_last (the only non-const member)
+//   LDS     rhs_pass_two reads rrb (UNI: row steps, uhi / uhv) and uses the xchg mailboxes at ex (NT > 64); classify votes through the first words at S (NT > 64), which
+//           the kernel zeroes afterwards
+//   lanes   reads x, u, su, every v, cls* (general variant), pc* (POL), hi / hv / hiu / hus (general variant); writes bx, bxu, gs, gsu and, NW 1, bnext (the next chunk's
+//           first right-hand side; role-split: the receiver adds its own, and the other role's share of the control's rhs rides in bxu[0])
+//   called  rhs_pass_two by admm_loop (every iteration), refine_phase_newton (<.., NWT>, every step) and polish_kernel (<.., POL>); classify once, by solve_body right
+//           after load(), to choose between the UNI kernel and deferring the path to the general one
     // UNI: all lanes share the row-class patterns (pat_loc / pat_ctl, set by classify()); FIRST: cold-start iteration.
     // NWT (Newton refinement, refine = 2; general variant only): the right-hand side is MINUS THE GRADIENT of the augmented Lagrangian at (x, v = a.x + y / rho),
     //   -g = -(P x + A' rho (v - clip(v))),   so that the solve returns the Newton direction: "2 clip(v) - v" -> "clip(v) - v", "sigma x" -> "-P x".
@@ -2817,6 +2950,17 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         } else return __all(same ? 1 : 0) != 0;
     }
 
+// ==================== [two_solve] ====================
+// members of Fast, part 8: solve_two, the linear solve of one iteration on the two-level mapping with ONE LANE PER CHUNK (NW 1: NWX 1, 4, 5; the
+// role-split mapping runs solve_split, [two_sweeps]).  TWO only.  Five phases, the PO_TICK buckets and PO_MARK labels: F1 every chunk's outflow with zero inflow
+// (sweep_forward<0>), F2 forward scan of the chunk boundaries s_t = beta_t + Phi_t s_{t-1}, F3 the true forward sweep and B1 the backward sweep with zero inflow, B2
+// the suffix scan X_t = gamma_t + Phi_t' X_{t+1}, B3 the true backward sweep.  The scans: one wave — DPP row shifts inside rows of 16 lanes, row totals through
+// v_readlane, no barrier; SEG (NT > 64) — 8-lane segments on DPP, segment totals through LDS with the scan's one barrier, carried back through in-wave permutes.
+//   LDS     reads fac, facu, phi (levels 0..5 / SEG 0..4), rseg; writes mail (SEG: segment totals, forward [0], backward [1]) and, NT > 64, the xchg mailboxes at ex
+//   lanes   in: st.bx, st.bxu, st.bnext (rhs_pass_two); out: st.bx, st.bxu = the solution at the own stages / controls, st.bnext = the next chunk's first stage,
+//           st.bprev = the previous chunk's last stage and its last control
+//   called  once per iteration by admm_loop, once per Newton step by refine_phase_newton ([loops]), and by polish_kernel; ph_: cycles per phase (dev) or nullptr
+// PO_TICK is local to solve_two and #undef'd at its end.
     __device__ __forceinline__ void solve_two(LS &st, double rho, long long *ph_) const {
         const bool prof = ph_ != nullptr;
         long long tt = prof ? __builtin_readcyclecounter() : 0;
@@ -2925,7 +3069,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         } else {
             // one wave: Kogge-Stone inside rows of 16 lanes on DPP row shifts (VALU latency instead of an LDS round trip per level), then the
             // row totals carried from row to row through readlane broadcasts.  No predicates: lanes without a source get o = 0, entries of
-            // chunks that are not full are zero (entry tfull always is), see factor_chain_two.
+            // chunks that are not full are zero (entry tfull always is), see factor_chain_two.  (twin: scan_forward_wave, [two_sweeps])
             const int tp_ = tid < L.TP ? tid : tfull;
             // straight-line code, the table of level l + 1 requested before level l is computed (its load does not depend on s)
             double pa[9], pb[9];
@@ -3055,7 +3199,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
                 }
             }
         } else {
-            // suffix scan, same structure: DPP row shifts to the left inside the rows, then the first lane of row r + 1 carried into row r
+            // suffix scan, same structure: DPP row shifts to the left inside the rows, then the first lane of row r + 1 carried into row r  (twin: scan_backward_wave)
             double pa[9], pb[9];
             load9(L.phi, tid < L.TP ? tid : tfull, pa);
 #define PO_BWD_LEVEL(LVL, PC, PN) \
@@ -3100,6 +3244,17 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
 #undef PO_TICK
     }
 
+// ==================== [two_update] ====================
+// members of Fast, part 9: the row passes that FOLLOW a solve on the two-level mapping.  TWO only, every NWX.
+//   update_pass_two<CERT, FIRST, UNI, POL>   the last of an iteration's three passes: slacks back-substituted from gs / gsu, then x, u, su and every v relaxed towards the
+//                                            solve's result (alpha); CERT: also the ingredients of OSQP's infeasibility certificate (Cert, [single_level])
+//   nbr_x<NEXT>                              x of the stages next to the own ones and the own chunk's control, for passes that run on the ITERATE (no solve just before)
+//   residual_pass_two<UNI>                   primal / dual residuals and their norms, scaled and unscaled, objective, non-finite flag (Resid)
+//   LDS     no table is read: what a pass needs from other lanes arrives in st.bnext / st.bprev (update) or through nbr_x — xchg (NW 1; mailboxes at ex when NT > 64) or
+//           the hand-off slots hx0 / hx1 (role-split, two or four barriers); UNI reads rrb; the cross-wave reductions (NT > 64) go through ex
+//   lanes   update_pass_two reads bx, bxu, bnext, bprev, gs, gsu, hi / hv (general variant) and writes x, u, su, vl, vd, vdo, vend, vc; residual_pass_two writes nothing
+//   called  update_pass_two by admm_loop (every iteration) and polish_kernel (<.., POL>); residual_pass_two by admm_loop at the checks and by refine_phase_newton at every
+//           step; nbr_x by residual_pass_two and nw_reexpress_pass ([newton_passes])
     // CERT: also evaluate the ingredients of OSQP's primal infeasibility certificate on this iteration's delta_y.
     // FIRST is the compile-time cold-start flag of the plain variant; the CERT variant (rare) takes it at run time.
     template <bool CERT, bool FIRST, bool UNI = false, bool POL = false> __device__ __forceinline__ Cert update_pass_two(LS &st, double rho, bool first_rt) const {
@@ -3424,11 +3579,18 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         return R;
     }
 
-    // =====================================================================================================
-    // POLISH (two-level mapping; opt-in, po_params.polish).  The solve kernels leave every lane's ADMM state (x and the one-number-per-row
-    // v) in an HBM block; polish_kernel reloads it with the same (SPL, NT) shape.  See PolWrap above for how the reduced KKT solve maps
-    // onto the passes of the ADMM iteration.
-    // =====================================================================================================
+// ==================== [newton_passes] ====================
+// members of Fast, part 10: what the phases AFTER the ADMM loop add to the two-level mapping.  TWO only, every NWX.
+//   state_io / park_io <STORE>      the lane's ADMM state (x and every v; park_io: + the classes of the factorisation in use, kept in st.pc*) to / from a block in HBM,
+//                                   [k][NT] so that a wave's access is coalesced: the hand-over between the solve, Newton, fallback and polish launches ([kernels])
+//   block_any, block_sum2           block-wide OR / pair of sums: one wave — DPP / __any only; NT > 64 — through ex with three barriers (role-split: ex is hand-off slot 1)
+//   reclass_pass                    row classes st.cls* from the rows' activity (ReclassFn, [row_fns]) and v re-expressed for the new steps
+//   nw_reexpress_pass, nw_dir_of, nw_dir_pass<MODE>, nw_ls_eval01, nw_ls_eval      the Newton refinement's own passes (the banner below): w = a.x + y / rho from the
+//                                   iterate; the direction's slope terms / the step applied; the merit function and its derivative along the direction (exact line search)
+//   LDS     nothing but ex (NT > 64) and what nbr_x uses ([two_update])
+//   lanes   reclass_pass writes cls*, vl, vd, vdo, vend, vc; nw_reexpress_pass every v; nw_dir_pass<1> x, u, su and every v; the direction is read where the solve left
+//           it (bx, bxu, bnext, bprev; slacks from gs / gsu, hi, hv, hiu, hus); the others write nothing
+//   called  the passes by refine_phase_newton ([loops]) only; block_any also by the pivot scans; state_io / park_io by the kernels
     static constexpr int kStateDoubles = SPL * (3 + T::NS) + SPL * T::NLOC + SPL * T::NDYN + T::NDYN + 2 + 1 + 4 * NG;  // x, vl, vd, vdo, vend, su, (u, vc) per control
     template <bool STORE> __device__ __forceinline__ void state_io(LS &st, double *base) const {  // [k][NT]: coalesced
         int k = 0;
@@ -3533,7 +3695,7 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         return block_any(fn.changes != 0);
     }
     // =====================================================================================================
-    // NEWTON REFINEMENT (po_params.refine = 2; two-level mapping, one lane per chunk): semismooth Newton on the augmented Lagrangian
+    // NEWTON REFINEMENT (po_params.refine = 2; two-level mapping, every lane layout): semismooth Newton on the augmented Lagrangian
     //     phi_y(x) = 1/2 x'Px + sum_i rho_i / 2 dist^2(a_i x + y_i / rho_i, [l_i, u_i])
     // with an exact line search (po_hip.h; oracle/po_oracle.c `refine == 2`).  The one-number-per-row state holds w_i = a_i x + y_i / rho_i, so that
     // z = clip(w), y = rho (w - z) and the gradient of phi is the dual residual of (x, y): residual_pass_two serves as it is.  The Newton matrix is the
@@ -3781,6 +3943,20 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         f = a0; fp = a1;
     }
 
+// ==================== [polish_passes] ====================
+// members of Fast, part 11: the passes only OSQP's polish has.  TWO only, one lane per chunk (NWX 1, 4, 5: polish_kernel's static_assert).
+//   pol_init    the active set of the ADMM point into st.pc / pce / pcc (2 bits per row), from v against the bounds (PolInitFn, [row_fns])
+//   pol_reset   start of a reduced KKT solve: x = 0, v = the bound every active row is held at (PolResetFn)
+//   pol_eval    residuals, objective and implied active set of the polished point (PolEvalFn -> PolRes)
+// The solve itself is the ADMM iteration's: factor_blocks_two / rhs_pass_two / update_pass_two instantiated with POL wrap their row functors in PolWrap.
+//   LDS     pol_eval: the xchg mailboxes and the cross-wave reduction at ex (NT > 64); the others touch none
+//   lanes   pol_init reads vl, vend, vc, cls* and writes pc*; pol_reset writes x, u, su and every v; pol_eval writes nothing (the new codes go to the caller's pcn*)
+//   called  polish_kernel ([kernels]) only
+    // =====================================================================================================
+    // POLISH (two-level mapping; opt-in, po_params.polish).  The solve kernels leave every lane's ADMM state (x and the one-number-per-row
+    // v) in an HBM block (state_io, [newton_passes]); polish_kernel reloads it with the same (SPL, NT) shape.  See PolWrap ([row_fns]) for how the
+    // reduced KKT solve maps onto the passes of the ADMM iteration.
+    // =====================================================================================================
     // active set of the ADMM solution (st.cls* still hold the row classes of the bounds)
     __device__ __forceinline__ void pol_init(LS &st) const {
         st.pce = st.pcc = 0;
@@ -3965,6 +4141,13 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
         return R;
     }
 
+// ==================== [output] ====================
+// members of Fast, part 12 and last: output_pass, the map from the solution to what the caller gets (the reference's getOptimizedPath): per point
+// x, y, heading, curvature / steering and the running arc length into in.out_states [N][5], and the raw QP solution into in.out_x when asked.  Every instantiation.
+//   LDS     the [N][2] points and [N] segment lengths lie at bz: the rhs / solution region of the single-level mapping, the scan tables (phi) of the two-level one —
+//           both dead once the last solve has run, so this is the LAST thing a kernel does with its LDS
+//   lanes   reads st.x, st.u, st.su; writes nothing
+//   called  by solve_body (unless a Newton launch follows and writes the outputs itself: DevBatch::nw_follows), the Newton kernels and polish_kernel ([kernels])
     // ---- output pass: getOptimizedPath ----
     __device__ __forceinline__ void output_pass(const LS &st) const {
         double *out = in.out_states + po * 5;
@@ -4042,8 +4225,21 @@ template <int F, int SPL, int NT, bool TWO, int NWX = 1, int NFIX = 0> struct Fa
             }
         }
     }
+
 };
 
+// ==================== [loops] ====================
+// after the struct, part 1: the two drivers that sequence Fast's passes for one path.  Free function templates on a Fast object and its lane state (not
+// members: each kernel instantiates the one loop variant it needs).  They touch LDS and the lane state only through the passes; what they own are the wave-uniform
+// scalars of the iteration (rho, counters, thresholds), kept in scalar registers with uni().
+//   admm_loop<UNI, RESUME>                  every instantiation: factor, then per iteration rhs -> solve -> update (PO_FRESH_LANE_ID before each), residuals and OSQP's
+//                                           termination / infeasibility tests every check_every, rho adaptation with rescale + refactorisation.  Called by solve_body
+//   refine_phase_newton<.., PH, NFIX, CK>   TWO only: the semismooth Newton refinement — per step reclass, residuals, [refactorise], Newton right-hand side, solve,
+//                                           exact line search, step; multiplier updates outside.  Called by the Newton kernels (PH 1 / 2: parks / resumes a path
+//                                           through park[] and st.pc*) and by solve_body<REF = 2> (PH 0).  Sets fx.nw_req for its duration (Fast::eq_step)
+// Dev switches that live here: PO_MARK labels (PO_MARKS builds), PO_NW_TRACE / PO_NW_TRACE_QUIET (cycle buckets through PO_NW_TICK, local to refine_phase_newton and
+// #undef'd at its end; the factorisation's buckets come from Fast::dbgc).
+//
 // The ADMM loop of one path.  UNI (two-level mapping only): every lane's rows have the same class pattern — the passes then take the per-row
 // steps and the slack-elimination data as wave-uniform numbers from LDS, and the per-lane copies (st.cls, st.hi, st.hv) are dead for the
 // whole loop, which takes ~30 VGPRs off a kernel that sits at the 512-register limit.
@@ -4158,8 +4354,8 @@ constexpr int kNwParkScalars = 12;
 // ends uncertified like one out of steps, the rounds go on.  Without it such an attempt burns refine_newton_max = 300 steps in every round (oracle: PO_NW_STAGNATION).
 constexpr int kNwStagnation = 8;
 // Refinement, po_params.refine = 2: semismooth Newton on the augmented Lagrangian with an exact line search (Fast: NEWTON REFINEMENT; the oracle's
-// `refine == 2` block is the same sequence of operations).  Same contract as refine_phase: st is a second lane state filled from the stored solved
-// point, on return st.cls* hold the row classes of the bounds and v is expressed for the type-based step vector at rho_solve.
+// `refine == 2` block is the same sequence of operations).  Contract: st is a lane state filled from the stored solved
+// point (load() + state_io), on return st.cls* hold the row classes of the bounds and v is expressed for the type-based step vector at rho_solve.
 // PH: 0 the whole phase; 1 first of the two sliced launches (parks); 2 second (resumes) — compile-time, each with its own register allocation (one body with both
 // at run time: 77 -> 207 spilled VGPRs, the launch 3.8 -> 4.9 ms)
 // CK (fixed lengths only; DESIGN.md section 36): the row classes BY TYPE that every pass of the phase decodes are compile-time constants — all stage-local rows
@@ -4378,10 +4574,22 @@ __device__ __forceinline__ RefineOut refine_phase_newton(Fast<F, SPL, NT, true, 
     return o;
 }
 
+// ==================== [kernels] ====================
+// after the struct, part 2: the kernels.  Each builds one Fast object per workgroup (= per path), load()s the lane state, zeroes its LDS, copies the
+// equilibration block (scale_to_lds) and runs a loop of [loops]; po_solve_form.hip instantiates them per shape, po_kernels.hip launches them.
+//   solve_kernel_fast (solve_body<REF = 0>)    every F / TWO / NWX / NFIX; load -> [classify] -> admm_loop -> state block (when a Newton / polish launch follows) -> outputs
+//   newton_kernel, newton_kernel_std           TWO; the text is po_newton_kernel.inc, included twice below; refine_phase_newton on the state block the warm start left
+//   newton_std_select_kernel                   NFIX > 0, NT 64: sorts the paths of a batch between those two by their row classes; reads the inputs only
+//   newton_fallback_kernel (solve_body<REF = 2>)   TWO, general variant: the later rounds of what a Newton launch handed back (DevBatch::fb_list)
+//   polish_kernel                              TWO, NWX 1 / 4 / 5: OSQP's polish on the state block
+// Global memory: in.out_info (po_info per path: status, counters, residuals — also the hand-over between the launches), in.pol_state (state_io), in.nw_state (park_io),
+// in.out_states / in.out_x (output_pass, zero_outputs), in.dbg_cycles (dev).  LDS: only through the Fast object, except polish_kernel's rescaling of cst (sigma -> delta).
+//
 // One launch = one loop variant.  The two-level mapping is launched twice on the same stream: UNI = true solves every path whose row
 // classes are uniform (all of them on BASELINE's corridors) and marks the others kStatusDeferred in out_info; UNI = false picks exactly
 // those up (its other blocks leave after one 4-byte read).  Two loop variants inside ONE kernel cost more registers than either needs
 // (measured: 114 -> 82 M path-iterations/s), a kernel with only the uniform variant spills 14 instead of 53 VGPRs (114 -> 122 M).
+
 // a path that is reported without a solution (non-finite inputs): defined outputs — zeros — instead of whatever the buffers held
 __device__ __forceinline__ void zero_outputs(const DevBatch &in, int b, int nt) {
     double *os = in.out_states + (size_t)b * in.N * 5;
@@ -4565,13 +4773,8 @@ template <int F, int SPL, int NT, int NWX = 1> __global__ PO_KERNEL_ATTR __launc
     }
 }
 
-// po_params.refine = 2 with refine_chain = 2 ("split" scheduling): the Newton refinement of round 0 as a KERNEL OF ITS OWN.  The plain solve kernels (no refinement
-// phase in them: their own register allocation) run the short type-based warm start of every path — all paths take the same 25 .. 50 iterations, so that launch has no
-// tail — and leave state and po_info as for a polish; this kernel picks every solved path up, runs refine_phase_newton, and either finishes it (outputs, po_info,
-// status_refine) or hands it back exactly as the kernels with the phase do (status kStatusDeferred - 1, iterate in the state block, counters in po_info): the per-round
-// launches of those kernels (`_nw` objects, po_launch_solve_round) then take the rare path that was not certified through the later rounds.  Same arithmetic, same
-// results as the chained single launch; what changes is that the phase is compiled alone (no ADMM hot loop sharing its registers) and that nothing waits on a queue.
-// The later rounds of the paths whose round-0 Newton attempt was not certified (rare: no path of the BASELINE batches).  newton_kernel appends such a path to a
+// newton_fallback_kernel: the later rounds of the paths whose round-0 Newton attempt was not certified (rare: no path of the BASELINE batches).
+// newton_kernel appends such a path to a
 // device-side work list (DevBatch::fb_list: count, then path ids); this kernel is launched with a SMALL fixed grid (kFallbackGrid workgroups) that walks the list, each
 // path through its rounds one after the other in the general-variant body of the kernels with the phase (solve_body<..., REF = 2>, non-chained: it picks the path up by
 // its hand-back status).  Why not B workgroups that look at their own path's status and leave: a kernel's launch cost grows with its private segment, and the loops
@@ -4596,6 +4799,11 @@ template <int F, int SPL, int NT, int NWX = 1> __global__ PO_KERNEL_ATTR __launc
     }
 }
 
+// newton_kernel — po_params.refine = 2: the Newton refinement of round 0 as a KERNEL OF ITS OWN.  The plain solve kernels (no refinement phase in them: their own
+// register allocation) run the short type-based warm start of every path — all paths take the same 25 .. 50 iterations, so that launch has no tail — and leave state
+// and po_info as for a polish; this kernel picks every solved path up, runs refine_phase_newton, and either finishes it (outputs, po_info, status_refine) or hands it
+// back (status kStatusDeferred - 1, iterate in the state block, counters in po_info, the path appended to DevBatch::fb_list) to newton_fallback_kernel above, which
+// takes the rare path that was not certified through the later rounds.  The phase is compiled alone: no ADMM hot loop shares its registers.
 // The kernel's text is po_newton_kernel.inc: newton_kernel, and newton_kernel_std — the Newton launches of a fixed length with the STANDARD row classes as compile-time
 // constants (DESIGN.md section 36): every stage-local row an inequality, KP's control row free, which is every path with positive margin and kmax and non-degenerate
 // corridors.  Which paths those are is decided by newton_std_select_kernel (below) in a launch of its own; the engine hands newton_kernel_std the standard paths and
@@ -4634,6 +4842,3 @@ template <int F, int SPL, int NT, int NFIX> __global__ PO_KERNEL_ATTR __launch_b
         sl.flag[b] = all ? 1 : 0;  // (no count here: 4 096 atomic adds on one word made this launch 60 us instead of 18, DESIGN.md section 36 — po_debug_get sums the flags)
     }
 }
-
-// nwx: 1 one lane per chunk, 2 role-split (chunk = 2 spl stages), 3 role-split of an odd keep (chunk = 2 spl - 1 stages), 4 / 5 multi-group (spl / 1, spl / 2 groups per lane)
-template <int F> size_t lds_bytes_fast(int N, int C, int spl, bool two, int nt, int nwx = 1) { return sizeof(double) * (size_t)LayoutF<F>(N, C, spl, two, nt, (nwx == 2 || nwx == 3) ? 2 : 1, (nwx == 2 || nwx == 3) ? 2 * spl - (nwx == 3 ? 1 : 0) : 0, nwx == 4 ? spl : (nwx == 5 ? spl / 2 : 1)).total; }
