@@ -933,7 +933,8 @@ int po_dynamic_batch_device(po_handle h, const po_dynamic_params *p, const po_dy
  *       vp = v0 for k = 1, else v(j - u, u');  acc = (v(j, u) - vp) / dt;  dv = c(j, u) - v(j, u);  e = (w_acc * acc) * acc + (w_slow * dv) * dv.
  *       The edge is feasible iff the predecessor is reachable and has not ARRIVED (j - u != M - 1), (j, u) is drivable and clear in window k - 1,
  *       acc <= a_max and acc >= -b_max, and, for k > 1, u' == 0 implies u == 0: a speed profile over arc length cannot express stop, wait, go — po_dynamic_batch's
- *       own statement about stops — so a vehicle that has stopped stays stopped to the horizon.
+ *       own statement about stops — so a vehicle that has stopped stays stopped to the horizon.  (po_stgo_batch*, below, is this search without that clause:
+ *       its plans stop, wait and go, and leave sampled in time, not as a v_limit row.)
  *   Choice.  The candidates are the states (k, M - 1, u), k = 1 .. K (arrived), and every state of layer K.  Scan k ascending, then j, then u, and take a
  *       candidate when its value < the best so far (starting at DBL_MAX).  None: status = 3 and the outputs of "not planned" except that the cells row is the map.
  *       Otherwise n_layers = the chosen k, cost = its value, station[0 .. n_layers] = the stations along the back pointers (station[0] = 0) and -1 behind them,
@@ -1237,6 +1238,101 @@ typedef struct po_agentsets_out {
 int po_agentsets_batch(po_handle h, const po_agentsets_params *p, const po_agentsets_in *in, const po_agentsets_out *out);         /* host pointers, synchronous */
 int po_agentsets_batch_device(po_handle h, const po_agentsets_params *p, const po_agentsets_in *in, const po_agentsets_out *out);  /* device pointers, on the stream, no synchronisation */
 
+/* ---- stop, wait, go: station-time plans that resume, sampled in time (csrc/po_stgo.hip, csrc/po_stsearch.hpp) ----
+ * po_stplan_batch* may not resume after a stop, only because its one product is a v_limit row over arc length, which cannot carry a wait.  This stage runs the
+ * same station-time search with resuming allowed and hands the plan over sampled at uniform TIME steps, in the layouts of po_trajectory_out: stop for a
+ * pedestrian, let them clear, drive on.  out->states has the layout of every states array with N := Q, and with out->t it is a timed path po_dynamic_batch*
+ * reads — intervals of positive duration and zero displacement included, so it checks the vehicle while it waits — and with out->v a profiled path
+ * po_trajectory_batch* turns into agent records.  It writes no v_limit; po_stplan_batch* stays the stage for that.  The stage reads no map and works on a handle
+ * without one.  The reference has no such stage.
+ *
+ * Definition (the bar is BIT equality).  The conventions are po_dynamic_batch's: every operation is one rounded IEEE double operation in the order written,
+ * nothing contracted; sqrt and / are the correctly rounded ones; a comparison with a NaN is false; min and max as defined there.  n, row i, integer division:
+ * as in po_stplan_batch.  The first ten fields of po_stgo_params are po_stplan_params' with the same ranges; t0, dts and Q are the sample times:
+ * sample q < Q is at T_q = t0 + (double)q * dts.
+ *   Not planned: status = 0 on po_stplan_batch's triggers (ok[b] == 0, or n < 2, or v0[b] not a finite value >= 0, or a non-finite x, y, z or s of rows < n, or
+ *       M < 2), AND ADDITIONALLY when s_{i+1} < s_i for some i < n - 1: the sampler looks a state up by s, and a row that is not non-decreasing would make the
+ *       answer depend on the search method.  (po_stplan_batch plans such a path; this is the one difference in what the two stages plan.)  The plan fields are
+ *       as there (ok_out = 0, n_layers = 0, cost = DBL_MAX, station and cells rows -1); n_resumes = 0; every entry of the path's sample rows (states, v, a, t)
+ *       is 0, every index -1, first_held = -1, end = 0.
+ *   Stations, blocked cells, step table, search, choice, status, station, cells: the text of po_stplan_batch with the one clause "for k > 1, u' == 0 implies
+ *       u == 0" deleted.  A predecessor at rest may have any successor: vp = v(j - u, 0) = 0, so acc = v(j, u) / dt <= a_max already bounds the pull-away, and
+ *       waiting is costed by w_slow * c^2 like any slow edge.  Nothing else in the search changes.  No plan: status = 3, the samples are those of a path that
+ *       is not planned, and the cells row is the map.
+ *   n_resumes = the number of k in 2 .. n_layers with u_{k-1} == 0 and u_k > 0.
+ *   Samples of a planned path, nl = n_layers.  V_0 = v0;  V_k = v(station[k], u_k) for k = 1 .. nl (0 when u_k == 0);  A_k = (V_k - V_{k-1}) / dt, the acc the
+ *       search costed.  S_m is the s of station m.  For sample q, T = T_q, in this order:
+ *       T < 0: the sample is row 0, with v = v0, a = 0, index = 0.
+ *       Else kk = the largest k in 0 .. nl with (double)k * dt <= T: a T exactly on a layer time belongs to the later window.
+ *       kk == nl: HELD.  The sample is the row of state station[nl] * stride, with v = V_nl, a = 0, index = that state.
+ *       Else the edge is p = station[kk], j = station[kk+1], and tau = T - (double)kk * dt.
+ *       j == p (standing): the sample is row p * stride, with v = 0, a = A_{kk+1}, index = p * stride.
+ *       Else (moving):  sig = V_{kk+1} * tau;  sx = S_p + sig, then sx = sx > S_j ? S_j : sx;  i = the largest state index in [p * stride, j * stride - 1]
+ *           with s_i <= sx (s is non-decreasing and s_{p * stride} = S_p <= sx, so the search method cannot change i);  ds = s_{i+1} - s_i;
+ *           lam = ds > 0 ? (sx - s_i) / ds : 0, then lam = lam < 0 ? 0 : lam, then lam = lam > 1 ? 1 : lam;
+ *           x = x_i + lam * (x_{i+1} - x_i), the same for y and k, and s = s_i + lam * ds;
+ *           dz = z_{i+1} - z_i;  if dz > PI: dz = dz - TWO_PI, else if dz < -PI: dz = dz + TWO_PI  (the doubles 3.141592653589793 and 6.283185307179586);
+ *           z = z_i + lam * dz, not wrapped again  (po_trajectory_batch's interpolation, character for character, with its own lam);
+ *           v = V_{kk+1}, a = A_{kk+1}, index = i.
+ *       out->t[b][q] = T for every sample of a planned path.
+ *   first_held = the smallest q with kk == nl, Q when there is none (T_q is non-decreasing in q).
+ *   end = 1 when first_held == Q: the samples end inside the plan.  Otherwise 2 when station[nl] is the path's last station (arrived), else 3 when u_nl == 0
+ *       (the vehicle stands there), else 4: the plan ends AT SPEED before the samples do and the samples from first_held on repeat its last station — a vehicle
+ *       that freezes where its plan ends, as po_trajectory_batch's status 3.
+ *   Known and stated, not fixed: the speed is constant per window, which is the plan's own model, so v jumps at the layer times and a is the step the search
+ *       costed, not a derivative of the samples.  po_stplan_batch's conservative sweep and the uncovered ground between two stations are inherited.  Feeding
+ *       the samples to po_trajectory_batch* needs dts <= dt: further apart, two standing samples can have ground between them, which is that stage's end-state
+ *       rule.  T = +inf (q * dts overflows) is held like any T >= nl * dt; T is never NaN because t0 and dts are finite.
+ *   Decided while building: "aliasing" is po_trajectory_batch's overlap of byte ranges, every output array given over its full extent ([B], [B][17],
+ *       [B][K][PO_ST_MAX_STATIONS], [B][Q][5], [B][Q]) against every input array given over its own (the agent lists are not among them); with B = 0 every
+ *       extent is empty.  The extents are formed from K and Q only after their ranges are checked.
+ * Return codes, both entries.  PO_ERR_INVALID: what po_stplan_batch refuses (NULL handle, struct or required pointer: states, v0, status, agents with B > 0;
+ *   negative B, N, S, n_agents; S = 0 with B > 0; the ranges of the ten shared fields); t0 not finite; dts not finite or not > 0; Q < 1; with B > 0 a NULL
+ *   out->states; an output that aliases an input.  The HOST entry refuses the lists po_dynamic_batch refuses; the DEVICE entry reads them clamped and never
+ *   reads outside the buffers.  B = 0: PO_OK after those checks, nothing launched, nothing written.
+ * `p`, `in->agents` (the struct) are host pointers in both entries.  Deterministic: no atomics, no scratch, and a path's results depend neither on the batch
+ * size nor on its position in the batch.
+ * po_default_stgo_params: po_default_stplan_params' values, then {0, 0.1, 81} — 81 samples at 10 Hz span the 8 s of K * dt.  A starting point nobody has tuned. */
+typedef struct po_stgo_params {
+    double dt;                   /* the ten fields of po_stplan_params, same meaning and ranges */
+    int K;
+    int stride;
+    int U;
+    double margin;
+    double a_max, b_max;
+    double v_max;
+    double w_acc, w_slow;
+    double t0, dts;              /* sample q is at T_q = t0 + (double)q * dts; t0 finite, dts > 0 and finite */
+    int Q;                       /* >= 1 samples per path */
+} po_stgo_params;
+void po_default_stgo_params(po_stgo_params *p);
+typedef struct po_stgo_in {      /* po_stplan_in without v_limit_in */
+    int B, N;                    /* paths, rows per path (stride of the arrays) */
+    const double *states;        /* [B][N][5] x, y, heading, k, s; s non-decreasing */
+    const int    *n_states;      /* optional [B] (NULL: N) */
+    const int    *ok;            /* optional [B] (NULL: all 1) */
+    const double *v0;            /* [B] */
+    const double *v_cap;         /* optional [B][N]: a per-state speed cap; negative or NaN: none */
+    const int    *set_of;        /* optional [B] (NULL: set 0) */
+    const po_agent_lists *agents;
+} po_stgo_in;
+typedef struct po_stgo_out {
+    int    *status;              /* [B] 0 not planned, 1 planned and no cell blocked, 2 planned around blocked cells, 3 no plan */
+    int    *ok_out;              /* optional [B]: status 1 or 2 */
+    int    *n_layers;            /* optional [B] */
+    double *cost;                /* optional [B] */
+    int    *station;             /* optional [B][PO_ST_MAX_LAYERS + 1] */
+    int    *cells;               /* optional [B][K][PO_ST_MAX_STATIONS] */
+    int    *n_resumes;           /* optional [B]: times the plan pulls away after a window at rest */
+    double *states;              /* [B][Q][5]: the states layout with N := Q */
+    double *v, *a, *t;           /* optional [B][Q] */
+    int    *index;               /* optional [B][Q]: the state a sample is anchored at; -1 without a plan */
+    int    *first_held;          /* optional [B]: Q when no sample is held; -1 without a plan */
+    int    *end;                 /* optional [B]: 0 no plan, 1 inside the plan, 2 held arrived, 3 held at rest, 4 held at speed */
+} po_stgo_out;
+int po_stgo_batch(po_handle h, const po_stgo_params *p, const po_stgo_in *in, const po_stgo_out *out);         /* host pointers, synchronous */
+int po_stgo_batch_device(po_handle h, const po_stgo_params *p, const po_stgo_in *in, const po_stgo_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -1272,7 +1368,8 @@ const char *po_last_hip_error(void);
  * po_default_dynamic_params, po_dynamic_batch*) and the station-time entries (po_stplan_params, po_stplan_in, po_stplan_out, po_default_stplan_params,
  * po_stplan_batch*) and the corridor-nudge entries (po_nudge_params, po_nudge_in, po_nudge_out, po_default_nudge_params, po_nudge_batch*) and the timed-trajectory
  * entries (po_trajectory_params, po_trajectory_in, po_trajectory_out, po_default_trajectory_params, po_trajectory_batch*) and the agent-set
- * entries (po_agentsets_params, po_agentsets_in, po_agentsets_out, po_default_agentsets_params, po_agentsets_batch*) were added under 7 by
+ * entries (po_agentsets_params, po_agentsets_in, po_agentsets_out, po_default_agentsets_params, po_agentsets_batch*) and the stop-wait-go entries (po_stgo_params, po_stgo_in, po_stgo_out,
+ * po_default_stgo_params, po_stgo_batch*) were added under 7 by
  * the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7

@@ -253,3 +253,19 @@ class PoAgentsetsIn(C.Structure):
 class PoAgentsetsOut(C.Structure):
     _fields_ = [("capacity", C.c_int), ("agents", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p), ("status", C.c_void_p), ("set_of", C.c_void_p),
                 ("src_index", C.c_void_p), ("total", C.c_void_p)]
+
+
+# ---- stop, wait, go: station-time plans that resume, sampled in time (po_stgo_batch*) ----
+class PoStgoParams(C.Structure):
+    _fields_ = PoStplanParams._fields_ + [("t0", C.c_double), ("dts", C.c_double), ("Q", C.c_int)]
+
+
+class PoStgoIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("v0", C.c_void_p), ("v_cap", C.c_void_p),
+                ("set_of", C.c_void_p), ("agents", C.POINTER(PoAgentLists))]
+
+
+class PoStgoOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("ok_out", C.c_void_p), ("n_layers", C.c_void_p), ("cost", C.c_void_p), ("station", C.c_void_p), ("cells", C.c_void_p),
+                ("n_resumes", C.c_void_p), ("states", C.c_void_p), ("v", C.c_void_p), ("a", C.c_void_p), ("t", C.c_void_p), ("index", C.c_void_p),
+                ("first_held", C.c_void_p), ("end", C.c_void_p)]

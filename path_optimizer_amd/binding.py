@@ -37,7 +37,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_default_stplan_params", "po_stplan_batch", "po_stplan_batch_device",
            "po_default_nudge_params", "po_nudge_batch", "po_nudge_batch_device",
            "po_default_trajectory_params", "po_trajectory_batch", "po_trajectory_batch_device",
-           "po_default_agentsets_params", "po_agentsets_batch", "po_agentsets_batch_device"]
+           "po_default_agentsets_params", "po_agentsets_batch", "po_agentsets_batch_device",
+           "po_default_stgo_params", "po_stgo_batch", "po_stgo_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -128,6 +129,10 @@ def lib():
         L.po_default_agentsets_params.restype = None
         L.po_agentsets_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_agentsets_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_default_stgo_params.argtypes = [C.c_void_p]
+        L.po_default_stgo_params.restype = None
+        L.po_stgo_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_stgo_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -180,6 +185,15 @@ def default_stplan_params():
 
     p = PoStplanParams()
     lib().po_default_stplan_params(C.byref(p))
+    return p
+
+
+def default_stgo_params():
+    """po_default_stgo_params: the knobs of po_stgo_batch*, po_stplan_batch*'s and the sample times (a starting point nobody has tuned)."""
+    from .abi import PoStgoParams
+
+    p = PoStgoParams()
+    lib().po_default_stgo_params(C.byref(p))
     return p
 
 
@@ -1085,6 +1099,46 @@ class Engine:
         so = PoStplanOut(*[p(out, k) for k in self.STPLAN_KEYS])
         sp = params if params is not None else default_stplan_params()
         _check(lib().po_stplan_batch_device(self._h, C.byref(sp), C.byref(si), C.byref(so)))
+
+    # ---- stop, wait, go: station-time plans that resume, sampled in time ----
+    STGO_KEYS = ("status", "ok_out", "n_layers", "cost", "station", "cells", "n_resumes", "states", "v", "a", "t", "index", "first_held", "end")
+
+    def stgo_batch(self, states, v0, agents, n_states=None, ok=None, v_cap=None, set_of=None, params=None, want_rows=True):
+        """Host-pointer entry of po_stgo_batch.  states [B,N,5], v0 [B], agents: what pack_agents takes; optional n_states [B], ok [B], v_cap [B,N], set_of [B]
+        (None: set 0).  Returns a dict: status, ok_out, n_layers, n_resumes, first_held, end [B] i32, cost [B], station [B,17] i32, cells [B,K,128] i32 (None
+        without want_rows), and the samples: states [B,Q,5], v, a, t [B,Q], index [B,Q] i32 (what dynamic_batch and trajectory_batch read)."""
+        from .abi import PO_ST_MAX_LAYERS, PO_ST_MAX_STATIONS, PoStgoIn, PoStgoOut
+
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        B, N = states.shape[0], states.shape[1]
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        vv, cap = f(v0), f(v_cap)
+        ns, okk, so = _i32(n_states), _i32(ok), _i32(set_of)
+        lists, ag, first = _agent_lists(agents)
+        gi = PoStgoIn(B, N, _np(states), _np(ns), _np(okk), _np(vv), _np(cap), _np(so), C.pointer(lists))
+        gp = params if params is not None else default_stgo_params()
+        K, Q = max(int(gp.K), 0), max(int(gp.Q), 0)
+        i32 = lambda *shape: np.zeros(shape, dtype=np.int32)
+        r = {"status": i32(B), "ok_out": i32(B), "n_layers": i32(B), "cost": np.zeros(B), "station": i32(B, PO_ST_MAX_LAYERS + 1),
+             "cells": i32(B, K, PO_ST_MAX_STATIONS) if want_rows else None, "n_resumes": i32(B), "states": np.zeros((B, Q, 5)), "v": np.zeros((B, Q)),
+             "a": np.zeros((B, Q)), "t": np.zeros((B, Q)), "index": i32(B, Q), "first_held": i32(B), "end": i32(B)}
+        go = PoStgoOut(*[_np(r[k]) for k in self.STGO_KEYS])
+        _check(lib().po_stgo_batch(self._h, C.byref(gp), C.byref(gi), C.byref(go)))
+        return r
+
+    def stgo_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: states [B,N,5] f64, v0 [B] f64, agents (a uint8 tensor over AGENT_DTYPE records, or None when there are none), first [S+1] i32
+        (+ n_states, ok, set_of i32 [B], v_cap [B,N]); out: status [B] i32, states [B,Q,5] f64 (+ any of STGO_KEYS: station [B,17] i32, cells [B,K,128] i32,
+        v, a, t [B,Q] f64, index [B,Q] i32).  Q is params.Q.  Enqueued on the handle's stream, no synchronisation."""
+        from .abi import PoStgoIn, PoStgoOut
+
+        B, N = t["states"].shape[0], t["states"].shape[1]
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        lists = _agent_lists_device(t)
+        gi = PoStgoIn(B, N, p(t, "states"), p(t, "n_states"), p(t, "ok"), p(t, "v0"), p(t, "v_cap"), p(t, "set_of"), C.pointer(lists))
+        go = PoStgoOut(*[p(out, k) for k in self.STGO_KEYS])
+        gp = params if params is not None else default_stgo_params()
+        _check(lib().po_stgo_batch_device(self._h, C.byref(gp), C.byref(gi), C.byref(go)))
 
     # ---- corridor nudge: carve predicted agents out of the corridor bounds, pass left or right (DESIGN.md section 31) ----
     NUDGE_KEYS = ("status", "ok_out", "bounds", "side", "first_blocked_state", "first_blocked_agent", "width_min")

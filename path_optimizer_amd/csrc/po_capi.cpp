@@ -1180,6 +1180,85 @@ int po_trajectory_batch(po_handle h, const po_trajectory_params *p, const po_tra
     });
 }
 
+// ---- stop, wait, go: station-time plans that resume, sampled in time (po_stgo.hip) ---------------
+void po_default_stgo_params(po_stgo_params *p) {
+    if (!p) return;
+    po_stplan_params s;
+    po_default_stplan_params(&s);
+    *p = po_stgo_params{s.dt, s.K, s.stride, s.U, s.margin, s.a_max, s.b_max, s.v_max, s.w_acc, s.w_slow, 0.0, 0.1, 81};  // a starting point nobody has tuned
+}
+
+// What both entries can check without reading through a pointer of the structs (testable without a GPU)
+static bool stgo_args_ok(po_handle h, const po_stgo_params *p, const po_stgo_in *in, const po_stgo_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0) return false;
+    auto pos = [](double v) { return std::isfinite(v) && v > 0; };
+    auto wgt = [](double v) { return std::isfinite(v) && v >= 0; };
+    if (!pos(p->dt) || !pos(p->a_max) || !pos(p->b_max) || !pos(p->v_max) || !wgt(p->w_acc) || !wgt(p->w_slow) || !std::isfinite(p->margin)) return false;
+    if (p->K < 1 || p->K > PO_ST_MAX_LAYERS || p->stride < 1 || p->U < 1 || p->U > PO_ST_MAX_STEP) return false;
+    if (!std::isfinite(p->t0) || !pos(p->dts) || p->Q < 1) return false;
+    if (!agent_lists_shape_ok(in->agents, in->B)) return false;
+    const size_t B = in->B, bn = B * (size_t)in->N, bq = B * (size_t)p->Q;
+    if (B > 0 && (!in->states || !in->v0 || !out->status || !out->states)) return false;
+    // no output may overlap an input: byte ranges over the full extent of each array (B = 0: every extent is empty)
+    struct Range { const void *p; size_t bytes; };
+    const Range ins[] = {{in->states, 5 * bn * sizeof(double)}, {in->n_states, B * sizeof(int)}, {in->ok, B * sizeof(int)}, {in->v0, B * sizeof(double)},
+                         {in->v_cap, bn * sizeof(double)}, {in->set_of, B * sizeof(int)}};
+    const Range outs[] = {{out->status, B * sizeof(int)}, {out->ok_out, B * sizeof(int)}, {out->n_layers, B * sizeof(int)}, {out->cost, B * sizeof(double)},
+                          {out->station, B * (PO_ST_MAX_LAYERS + 1) * sizeof(int)}, {out->cells, B * (size_t)p->K * PO_ST_MAX_STATIONS * sizeof(int)},
+                          {out->n_resumes, B * sizeof(int)}, {out->states, 5 * bq * sizeof(double)}, {out->v, bq * sizeof(double)}, {out->a, bq * sizeof(double)},
+                          {out->t, bq * sizeof(double)}, {out->index, bq * sizeof(int)}, {out->first_held, B * sizeof(int)}, {out->end, B * sizeof(int)}};
+    for (const Range &o : outs)
+        for (const Range &i : ins) {
+            if (!o.p || !i.p || !o.bytes || !i.bytes) continue;
+            const uintptr_t ob = (uintptr_t)o.p, ib = (uintptr_t)i.p;
+            if (ob < ib + i.bytes && ib < ob + o.bytes) return false;
+        }
+    return true;
+}
+
+int po_stgo_batch_device(po_handle h, const po_stgo_params *p, const po_stgo_in *in, const po_stgo_out *out) {
+    if (!stgo_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing to plan: no launch, whatever the handle holds
+    Lock g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    po::DevStgo D{};
+    D.B = in->B; D.N = in->N; D.S = in->agents->S; D.n_agents = in->agents->n_agents;
+    D.states = in->states; D.n_states = in->n_states; D.ok = in->ok; D.v0 = in->v0; D.v_cap = in->v_cap; D.set_of = in->set_of;
+    D.agents = in->agents->agents; D.first = in->agents->first;
+    D.dt = p->dt; D.K = p->K; D.stride = p->stride; D.U = p->U; D.margin = p->margin; D.a_max = p->a_max; D.b_max = p->b_max; D.v_max = p->v_max;
+    D.w_acc = p->w_acc; D.w_slow = p->w_slow; D.t0 = p->t0; D.dts = p->dts; D.Q = p->Q;
+    const int mb = in->N > 0 ? (in->N - 1) / p->stride + 1 : 1;  // no path of the call has more stations: the LDS is sized from it
+    D.Mb = mb > PO_ST_MAX_STATIONS ? PO_ST_MAX_STATIONS : mb;
+    D.status = out->status; D.ok_out = out->ok_out; D.n_layers = out->n_layers; D.cost = out->cost; D.station = out->station; D.cells = out->cells;
+    D.n_resumes = out->n_resumes; D.o_states = out->states; D.o_v = out->v; D.o_a = out->a; D.o_t = out->t; D.index = out->index;
+    D.first_held = out->first_held; D.end = out->end;
+    const po::DevCar car = make_car(h->params);
+    HIP_TRY(po_launch_stgo(&car, &D, h->stream));
+    return PO_OK;
+}
+
+int po_stgo_batch(po_handle h, const po_stgo_params *p, const po_stgo_in *in, const po_stgo_out *out) {
+    if (!stgo_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
+    if (!agent_lists_host_ok(in->agents, in->set_of, in->B)) return PO_ERR_INVALID;
+    const size_t B = in->B, bn = B * (size_t)in->N, bq = B * (size_t)p->Q;
+    Stage S;
+    const Slot<double> states = S.in(in->states, 5 * bn), v0 = S.in(in->v0, B), cap = S.in(in->v_cap, bn);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), set_of = S.in(in->set_of, B);
+    StagedAgents ag;
+    stage_agent_lists(S, in->agents, &ag);
+    const Slot<int> status = S.out(out->status, B), ok_out = S.out_opt(out->ok_out, B), nl = S.out_opt(out->n_layers, B), nres = S.out_opt(out->n_resumes, B);
+    const Slot<int> station = S.out_opt(out->station, B * (PO_ST_MAX_LAYERS + 1)), cells = S.out_opt(out->cells, B * (size_t)p->K * PO_ST_MAX_STATIONS);
+    const Slot<int> index = S.out_opt(out->index, bq), fh = S.out_opt(out->first_held, B), end = S.out_opt(out->end, B);
+    const Slot<double> cost = S.out_opt(out->cost, B), os = S.out(out->states, 5 * bq), ov = S.out_opt(out->v, bq), oa = S.out_opt(out->a, bq), ot = S.out_opt(out->t, bq);
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+        const po_agent_lists dl = ag.dev(in->agents);
+        const po_stgo_in d{in->B, in->N, states, ns, ok, v0, cap, set_of, &dl};
+        const po_stgo_out o{status, ok_out, nl, cost, station, cells, nres, os, ov, oa, ot, index, fh, end};
+        return po_stgo_batch_device(h, p, &d, &o);
+    });
+}
+
 // ---- agent sets (po_agentsets.hip) ----------------------------------------------------------------
 void po_default_agentsets_params(po_agentsets_params *p) {
     if (!p) return;

@@ -31,7 +31,7 @@ struct SolveShape {
 constexpr size_t kLdsLimit = 160 * 1024;
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
 struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic; struct DevStplan; struct DevNudge;
-struct DevTrajectory; struct DevAgentSets;
+struct DevTrajectory; struct DevAgentSets; struct DevStgo;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
 
@@ -149,6 +149,10 @@ hipError_t po_launch_dynamic(const po::DevCar *c, const po::DevDynamic *a, hipSt
 // ---- po_stplan.hip: station-time speed planning (one workgroup per path: blocked cells over the lanes with the agent set through LDS in chunks, then the layered
 // search in LDS; dynamic LDS sized from K, a->Mb and U; device pointers) ----
 hipError_t po_launch_stplan(const po::DevCar *c, const po::DevStplan *a, hipStream_t st);
+
+// ---- po_stgo.hip: station-time plans that resume, sampled in time (one workgroup per path: the phases of po_stplan.hip's search from po_stsearch.hpp with a stopped
+// predecessor free to pull away, then lanes over the Q samples, each with a binary search on the path's s row; the same dynamic LDS; device pointers) ----
+hipError_t po_launch_stgo(const po::DevCar *c, const po::DevStgo *a, hipStream_t st);
 
 // ---- po_nudge.hip: corridor nudge (one wave per path, lanes own fixed (state, circle) pairs of the corridor, which lives in the output; the path's agent set through
 // LDS in chunks; device pointers) ----

@@ -131,14 +131,24 @@ struct DevDynamic {
 
 // station-time planning launch arguments (po_stplan.hip): po_stplan_in / po_stplan_out with the lists of po_agent_lists flattened, the fields
 // of po_stplan_params, and Mb = min((N - 1) / stride + 1, PO_ST_MAX_STATIONS), the bound on the stations of a path that sizes the LDS.  Every output but status
-// may be null.
-struct DevStplan {
+// may be null.  DevStSearch is what the phases of po_stsearch.hpp read and write: the part po_stplan.hip and po_stgo.hip share.
+struct DevStSearch {
     int B, N, S, n_agents;
     const double *states; const int *n_states, *ok; const double *v0, *v_cap; const int *set_of;
     const po_agent *agents; const int *first;
-    const double *v_limit_in;
     double dt; int K, stride, U, Mb; double margin, a_max, b_max, v_max, w_acc, w_slow;
-    int *status, *ok_out, *n_layers; double *cost; int *station, *cells; double *v_limit;
+    int *status, *ok_out, *n_layers; double *cost; int *station, *cells;
+};
+struct DevStplan : DevStSearch {
+    const double *v_limit_in;
+    double *v_limit;
+};
+
+// stop-wait-go launch arguments (po_stgo.hip): the search's, the sample times of po_stgo_params (sample q at t0 + q * dts, q < Q) and the
+// sample outputs of po_stgo_out.  Every output but status and o_states may be null.
+struct DevStgo : DevStSearch {
+    double t0, dts; int Q;
+    int *n_resumes; double *o_states, *o_v, *o_a, *o_t; int *index, *first_held, *end;
 };
 
 // corridor-nudge launch arguments (po_nudge.hip): po_nudge_in / po_nudge_out with the lists of po_agent_lists flattened, the fields of
