@@ -1333,6 +1333,112 @@ typedef struct po_stgo_out {
 int po_stgo_batch(po_handle h, const po_stgo_params *p, const po_stgo_in *in, const po_stgo_out *out);         /* host pointers, synchronous */
 int po_stgo_batch_device(po_handle h, const po_stgo_params *p, const po_stgo_in *in, const po_stgo_out *out);  /* device pointers, on the stream, no synchronisation */
 
+/* ---- speed QP: a jerk-limited s(t) inside a station-time plan's free tunnel (csrc/po_speedqp.hip) ----
+ * po_stgo_batch* and po_stplan_batch* decide — pass, yield, stop, wait, go — on windows of dt with constant speed per window, which no controller can track.
+ * This stage takes the plan (station, n_layers) and the cell map (cells) they leave, turns the plan's gaps into a tunnel lo_q <= s(T_q) - S_0 <= hi_q at the
+ * sample times, and solves a piecewise-jerk QP inside it per path: the search keeps the decision, the QP makes the motion.  The result leaves in the layouts of
+ * po_stgo_out / po_trajectory_out, so stgo -> speed QP -> dynamic and stgo -> speed QP -> trajectory -> agent sets stay on one stream.  No agents and no map
+ * are read; the stage works on a handle without a map.  The reference has no such stage.
+ *
+ * Definition (the bar is BIT equality).  The conventions are po_dynamic_batch's: every operation is one rounded IEEE double operation in the order written,
+ * nothing contracted; sqrt and / are the correctly rounded ones; a comparison with a NaN is false; min(a, b) = b < a ? b : a; max(a, b) = b > a ? b : a.
+ * n, row i, M, S_m, Vc_m: as in po_stplan_batch (from dt, K, stride, v_max and v_cap).  T_q = (double)q * dts, q < Q; h = dts; i1 = 1 / h, i2 = i1 / h, i3 = i2 / h.
+ *   Not run: status = 0 on po_stgo_batch's "not planned" triggers (ok[b] == 0, n < 2, v0[b] not a finite value >= 0, a non-finite x, y, z or s of rows < n,
+ *       s_{i+1} < s_i for some i < n - 1, M < 2), and when nl = n_layers[b] clamped into [0, K] is < 1, when station[b][k], k = 0 .. nl, each clamped into
+ *       [0, PO_ST_MAX_STATIONS - 1], has station[k+1] < station[k] for some k < nl or station[nl] > M - 1, and when ref_states[b][q][4] is not finite for
+ *       some q < n_q.  Then iters = n_fact = n_q = 0, r_prim = r_dual = 0, every entry of the path's sample rows (states, v, a, jerk, t, lo, hi) is 0, every index -1.
+ *   n_q = the number of q < Q with T_q <= (double)nl * dt (>= 1).  Samples q < n_q are the unknowns x_q = s(T_q) - S_0; write n for n_q below.
+ *   Tunnel.  kk = the largest k in 0 .. nl with (double)k * dt <= T_q.  The windows of sample q are kk - 1 when kk >= 1 and T_q == (double)kk * dt, then kk, each
+ *       only when <= nl - 1.  For a window w, p = station[w], j = station[w+1]: lo_m = 1 + the largest m < p with cells[b][w][m] >= 0, 0 when there is none;
+ *       hi_m = -1 + the smallest m in j + 1 .. M - 1 with cells[b][w][m] >= 0, M - 1 when there is none (cells NULL: there is none).  lo_q = the first window's
+ *       S_{lo_m} - S_0, then max(lo_q, the second's); hi_q likewise with min and S_{hi_m} - S_0.  lo_0 = hi_0 = 0.
+ *       C_q, q < n - 1: w = min(kk, nl - 1); c = Vc_{station[w]}, then c = min(c, Vc_m) for m = station[w] + 1 .. station[w+1], ascending.
+ *   Rows, in four classes.  d_r = x_{r+1} - x_r (r = 0 .. n - 2);  e_r = d_r - d_{r-1} with d_{-1} = 0;  f_r = e_{r+1} - e_r.
+ *       position  r = 0 .. n - 1:  x_r             in [lo_r, hi_r]
+ *       velocity  r = 0 .. n - 2:  d_r * i1        in [0, C_r]
+ *       accel.    r = 0 .. n - 2:  e_r * i2        in [-b_max, a_max], row 0 in [-b_max + c0, a_max + c0] with c0 = v0 * i1 (its constant moved into the bounds)
+ *       jerk      r = 1 .. n - 3:  f_r * i3        in [-j_max, j_max]
+ *       A x is these values.  A^T w, for row values w (0 for a row that does not exist):  pj_r = wj_r * i3;  tj_r = pj_{r-1} - pj_r;  ta_r = wa_r * i2 + tj_r;
+ *       tb_r = ta_r - ta_{r+1} (ta_{n-1} = 0);  tv_r = wv_r * i1 + tb_r, r = 0 .. n - 2;  (A^T w)_q = wp_q + (tv_{q-1} - tv_q) with tv_{-1} = tv_{n-1} = 0.
+ *       A row is an EQUALITY row when its l and u have the same 64 bits; rho_r = 1e3 * rho on those, rho elsewhere (rho: the path's current step).
+ *   Cost.  sum w_s (x_q - r_q)^2 + w_a (e_r * i2 - [r == 0] c0)^2 + w_j (f_r * i3)^2 with r_q = ref_states[b][q][4] - S_0.  In OSQP's form, with
+ *       tws = 2 * w_s, twa = 2 * w_a, twj = 2 * w_j:  P x = tws * x + A^T(0, 0, twa * (A x)_a, twj * (A x)_j);  qv = -(tws * r + A^T(0, 0, (twa * c0 at row 0), 0)).
+ *   Matrix.  Column c of K = P + sigma I + A^T diag(rho) A is A^T(gp * (A u)_p, rho_r * (A u)_v, (rho_r + twa) * (A u)_a, (rho_r + twj) * (A u)_j) for the unit
+ *       vector u of c, with gp = rho_r + (tws + sigma); its entries c .. c + 3 are the lower band K0 .. K3 of column c (0 behind row n - 1).
+ *       Factor, j = 0 .. n - 1 ascending, terms with a negative index left out:  D_j = ((K0_j - (L1_{j-1} * D_{j-1}) * L1_{j-1}) - (L2_{j-2} * D_{j-2}) * L2_{j-2})
+ *       - (L3_{j-3} * D_{j-3}) * L3_{j-3};  c1 = (K1_j - (L2_{j-1} * D_{j-1}) * L1_{j-1}) - (L3_{j-2} * D_{j-2}) * L2_{j-2};  c2 = K2_j - (L3_{j-1} * D_{j-1}) * L1_{j-1};
+ *       L1_j = c1 / D_j, L2_j = c2 / D_j, L3_j = K3_j / D_j  (Lk_j is the entry (j + k, j)).
+ *       Solve K xt = rhs:  yv_q = ((rhs_q - L3_{q-3} * yv_{q-3}) - L2_{q-2} * yv_{q-2}) - L1_{q-1} * yv_{q-1}, ascending;  w_q = yv_q / D_q;
+ *       xt_q = ((w_q - L3_q * xt_{q+3}) - L2_q * xt_{q+2}) - L1_q * xt_{q+1}, descending, terms with an index >= n left out.
+ *   Iteration, from x = 0, z = 0, y = 0, rho = p->rho, n_fact = 1, for it = 1 .. max_iter, om = 1 - alpha:
+ *       rhs = (sigma * x - qv) + A^T(rho_r * z_r - y_r);  xt as above;  zt = A xt;  x = alpha * xt + om * x;  per row zr = alpha * zt_r + om * z_r,
+ *       zc = zr + y_r / rho_r, z_r = min(max(zc, l_r), u_r) (that is: l_r > zc ? l_r : zc, then u_r < that ? u_r : that), y_r = y_r + rho_r * (zr - z_r).
+ *       When it % check_every == 0 or it == max_iter:  a norm |.| is the largest |v| of its entries COMPARED AS 64-BIT PATTERNS, so it depends on no order
+ *       and a NaN outranks every number.  r_prim = |A x - z|, r_dual = |(P x + qv) + A^T y|, mp = max(|A x|, |z|), md = max(max(|P x|, |A^T y|), |qv|),
+ *       ep = eps_abs + eps_rel * mp, ed = eps_abs + eps_rel * md.  r_prim <= ep and r_dual <= ed: status 1, stop.  Else it == max_iter: status 2, stop.
+ *       Else with adaptive_rho: rn = rho * sqrt((r_prim / mp) / (r_dual / md)), rn = 1e-6 > rn ? 1e-6 : rn, rn = 1e6 < rn ? 1e6 : rn; when rn > 5 * rho or
+ *       rn < rho / 5: rho = rn, the matrix is factorised again and n_fact counts it.  iters = the it of the stop; r_prim, r_dual: the last check's.
+ *   n_q == 1: status 1 without iterations (iters = n_fact = 0, residuals 0), x_0 = 0.
+ *   Samples from the iterate x (not z).  sq = S_0 + x_q;  sx = sq < s_0 ? s_0 : sq, then sx = sx > s_{n-1} ? s_{n-1} : sx;  i = the result of the bisection
+ *       lo = 0, hi = n - 1, while hi - lo > 1: mid = lo + (hi - lo) / 2, s_mid <= sx ? lo = mid : hi = mid — the largest i <= n - 2 with s_i <= sx, and state 0
+ *       for a NaN;  ds, lam, x, y, k, s, dz and z: po_stgo_batch's moving sample, character for character;  index = i.
+ *       v_0 = v0, v_q = (x_q - x_{q-1}) / h;  a_q = (v_{q+1} - v_q) / h, 0 at q = n - 1;  jerk_q = (a_{q+1} - a_q) / h, 0 at q >= n - 2.  Samples q >= n_q (HELD)
+ *       repeat sample n_q - 1's row, index, v, lo and hi with a = jerk = 0 — po_stgo_batch's held rule.  t_q = T_q for every sample of a path that ran.
+ *   Known and stated, not fixed: there is no previous acceleration a0 (a_0 is bounded against v0 only), no primal-infeasibility certificate (a tunnel that v0
+ *       cannot meet ends as status 2 with the iterate written), the caps follow the plan's windows and not the smoothed s, no equilibration and no polish,
+ *       agents are po_agent's discs as in the planners, the entries are not meant for graph capture, and po_plan_batch* does not call the stage.
+ *   Decided while building: the norms compare bit patterns (above) so that a NaN cannot make them depend on an order; acceleration row 0 keeps A linear by moving
+ *       c0 into its bounds and into qv; the matrix is DEFINED through the operators on unit vectors, so its bits need no second formula; the held samples
+ *       repeat lo and hi too; "aliasing" is po_stgo_batch's overlap of byte ranges, every output over its full extent ([B], [B][Q][5], [B][Q]) against every
+ *       input over its own ([B][N][5], [B], [B][N], [B][PO_ST_MAX_LAYERS + 1], [B][K][PO_ST_MAX_STATIONS], [B][Q][5]), formed after K and Q are checked.
+ * Return codes, both entries.  PO_ERR_INVALID: a NULL handle, struct or required pointer (with B > 0: states, v0, station, n_layers, ref_states, out->status,
+ *   out->states); negative B or N; dt, v_max, dts, a_max, b_max, j_max, rho, sigma not finite or not > 0; K outside 1 .. PO_ST_MAX_LAYERS; stride < 1; Q outside
+ *   2 .. PO_SQP_MAX_SAMPLES; a weight negative or not finite, or w_s + w_a + w_j not > 0; alpha not inside (0, 2); eps_abs or eps_rel negative or not finite;
+ *   max_iter < 1; check_every < 1; adaptive_rho not 0 or 1; an output that aliases an input.  The HOST entry also refuses an n_layers[b] outside [0, K] and, on a
+ *   path with n_layers[b] >= 1, a station[b][k], k <= n_layers[b], outside [0, PO_ST_MAX_STATIONS - 1]; the DEVICE entry reads them clamped (above) and never
+ *   reads outside the buffers.  B = 0: PO_OK after those checks, nothing launched, nothing written.
+ * `p` is a host pointer in both entries.  Deterministic: no atomics, no scratch, and a path's results depend neither on the batch size nor on its position in it.
+ * po_default_speedqp_params: po_default_stgo_params' dt, K, stride, v_max, dts and Q; limits 2 / 3 / 4; weights 1 / 1 / 1; then 0.1, 1e-6, 1.6, 1e-4, 1e-4,
+ *   2000, 25, 1.  A starting point nobody has tuned. */
+#define PO_SQP_MAX_SAMPLES 256
+typedef struct po_speedqp_params {
+    double dt;                   /* the plan's grid: the planner's dt, K, stride and v_max */
+    int K;
+    int stride;
+    double v_max;
+    double dts;                  /* the sample grid: the planner's dts and Q, with t0 = 0 */
+    int Q;                       /* 2 .. PO_SQP_MAX_SAMPLES */
+    double a_max, b_max, j_max;  /* acceleration in [-b_max, a_max], |jerk| <= j_max */
+    double w_s, w_a, w_j;        /* weights of the distance to the plan's samples, of acceleration and of jerk */
+    double rho, sigma, alpha, eps_abs, eps_rel;
+    int max_iter, check_every, adaptive_rho;
+} po_speedqp_params;
+void po_default_speedqp_params(po_speedqp_params *p);
+typedef struct po_speedqp_in {
+    int B, N;                    /* paths, rows per path (stride of the arrays) */
+    const double *states;        /* [B][N][5] x, y, heading, k, s; s non-decreasing */
+    const int    *n_states;      /* optional [B] (NULL: N) */
+    const int    *ok;            /* optional [B] (NULL: all 1): the planner's ok_out */
+    const double *v0;            /* [B] */
+    const double *v_cap;         /* optional [B][N] */
+    const int    *station;       /* [B][PO_ST_MAX_LAYERS + 1]: the planner's out->station */
+    const int    *n_layers;      /* [B]: the planner's out->n_layers */
+    const int    *cells;         /* optional [B][K][PO_ST_MAX_STATIONS]: the planner's out->cells; NULL: nothing is blocked */
+    const double *ref_states;    /* [B][Q][5]: the planner's samples at the same dts and Q with t0 = 0; column 4 is read */
+} po_speedqp_in;
+typedef struct po_speedqp_out {
+    int    *status;              /* [B] 0 not run, 1 converged, 2 max_iter reached (the iterate is written) */
+    int    *iters, *n_fact;      /* optional [B] */
+    double *r_prim, *r_dual;     /* optional [B]: the residuals of the last check */
+    int    *n_q;                 /* optional [B]: samples in the QP */
+    double *states;              /* [B][Q][5] */
+    double *v, *a, *jerk, *t;    /* optional [B][Q] */
+    double *lo, *hi;             /* optional [B][Q]: the tunnel, relative to S_0 */
+    int    *index;               /* optional [B][Q] */
+} po_speedqp_out;
+int po_speedqp_batch(po_handle h, const po_speedqp_params *p, const po_speedqp_in *in, const po_speedqp_out *out);         /* host pointers, synchronous */
+int po_speedqp_batch_device(po_handle h, const po_speedqp_params *p, const po_speedqp_in *in, const po_speedqp_out *out);  /* device pointers, on the stream, no synchronisation */
+
 /* Test/diagnostic entry: Map::getObstacleDistance at `n` world positions xy[n][2] (host pointers); inside[n] = Map::isInside. */
 int po_map_sample(po_handle h, int n, const double *xy, double *dist, int *inside);
 
@@ -1369,7 +1475,8 @@ const char *po_last_hip_error(void);
  * po_stplan_batch*) and the corridor-nudge entries (po_nudge_params, po_nudge_in, po_nudge_out, po_default_nudge_params, po_nudge_batch*) and the timed-trajectory
  * entries (po_trajectory_params, po_trajectory_in, po_trajectory_out, po_default_trajectory_params, po_trajectory_batch*) and the agent-set
  * entries (po_agentsets_params, po_agentsets_in, po_agentsets_out, po_default_agentsets_params, po_agentsets_batch*) and the stop-wait-go entries (po_stgo_params, po_stgo_in, po_stgo_out,
- * po_default_stgo_params, po_stgo_batch*) were added under 7 by
+ * po_default_stgo_params, po_stgo_batch*) and the speed-QP entries (po_speedqp_params, po_speedqp_in, po_speedqp_out, po_default_speedqp_params,
+ * po_speedqp_batch*, PO_SQP_MAX_SAMPLES) were added under 7 by
  * the same rule.  A binding should compare
  * the number in po_version() with the PO_ABI_VERSION it was written against before it passes a struct (path_optimizer_amd/binding.py does). */
 #define PO_ABI_VERSION 7

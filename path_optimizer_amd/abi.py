@@ -269,3 +269,25 @@ class PoStgoOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("ok_out", C.c_void_p), ("n_layers", C.c_void_p), ("cost", C.c_void_p), ("station", C.c_void_p), ("cells", C.c_void_p),
                 ("n_resumes", C.c_void_p), ("states", C.c_void_p), ("v", C.c_void_p), ("a", C.c_void_p), ("t", C.c_void_p), ("index", C.c_void_p),
                 ("first_held", C.c_void_p), ("end", C.c_void_p)]
+
+
+# ---- speed QP: a jerk-limited s(t) inside a station-time plan's free tunnel (po_speedqp_batch*) ----
+PO_SQP_MAX_SAMPLES = 256
+
+
+class PoSpeedqpParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("K", C.c_int), ("stride", C.c_int), ("v_max", C.c_double), ("dts", C.c_double), ("Q", C.c_int),
+                ("a_max", C.c_double), ("b_max", C.c_double), ("j_max", C.c_double), ("w_s", C.c_double), ("w_a", C.c_double), ("w_j", C.c_double),
+                ("rho", C.c_double), ("sigma", C.c_double), ("alpha", C.c_double), ("eps_abs", C.c_double), ("eps_rel", C.c_double),
+                ("max_iter", C.c_int), ("check_every", C.c_int), ("adaptive_rho", C.c_int)]
+
+
+class PoSpeedqpIn(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("states", C.c_void_p), ("n_states", C.c_void_p), ("ok", C.c_void_p), ("v0", C.c_void_p), ("v_cap", C.c_void_p),
+                ("station", C.c_void_p), ("n_layers", C.c_void_p), ("cells", C.c_void_p), ("ref_states", C.c_void_p)]
+
+
+class PoSpeedqpOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("iters", C.c_void_p), ("n_fact", C.c_void_p), ("r_prim", C.c_void_p), ("r_dual", C.c_void_p), ("n_q", C.c_void_p),
+                ("states", C.c_void_p), ("v", C.c_void_p), ("a", C.c_void_p), ("jerk", C.c_void_p), ("t", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p),
+                ("index", C.c_void_p)]

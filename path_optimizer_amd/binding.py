@@ -38,7 +38,8 @@ EXPORTS = ["po_default_params", "po_problem_dims", "po_keep_control_steps", "po_
            "po_default_nudge_params", "po_nudge_batch", "po_nudge_batch_device",
            "po_default_trajectory_params", "po_trajectory_batch", "po_trajectory_batch_device",
            "po_default_agentsets_params", "po_agentsets_batch", "po_agentsets_batch_device",
-           "po_default_stgo_params", "po_stgo_batch", "po_stgo_batch_device"]
+           "po_default_stgo_params", "po_stgo_batch", "po_stgo_batch_device",
+           "po_default_speedqp_params", "po_speedqp_batch", "po_speedqp_batch_device"]
 
 
 class PoError(RuntimeError):
@@ -133,6 +134,10 @@ def lib():
         L.po_default_stgo_params.restype = None
         L.po_stgo_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_stgo_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_default_speedqp_params.argtypes = [C.c_void_p]
+        L.po_default_speedqp_params.restype = None
+        L.po_speedqp_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_speedqp_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -194,6 +199,16 @@ def default_stgo_params():
 
     p = PoStgoParams()
     lib().po_default_stgo_params(C.byref(p))
+    return p
+
+
+def default_speedqp_params():
+    """po_default_speedqp_params: the knobs of po_speedqp_batch*, po_stgo_batch*'s grids, the limits, the weights and the ADMM settings (a starting point nobody
+    has tuned)."""
+    from .abi import PoSpeedqpParams
+
+    p = PoSpeedqpParams()
+    lib().po_default_speedqp_params(C.byref(p))
     return p
 
 
@@ -1139,6 +1154,46 @@ class Engine:
         go = PoStgoOut(*[p(out, k) for k in self.STGO_KEYS])
         gp = params if params is not None else default_stgo_params()
         _check(lib().po_stgo_batch_device(self._h, C.byref(gp), C.byref(gi), C.byref(go)))
+
+    # ---- speed QP: a jerk-limited s(t) inside a station-time plan's free tunnel ----
+    SPEEDQP_KEYS = ("status", "iters", "n_fact", "r_prim", "r_dual", "n_q", "states", "v", "a", "jerk", "t", "lo", "hi", "index")
+    SPEEDQP_IN_KEYS = ("states", "n_states", "ok", "v0", "v_cap", "station", "n_layers", "cells", "ref_states")
+
+    def speedqp_batch(self, states, v0, station, n_layers, ref_states, n_states=None, ok=None, v_cap=None, cells=None, params=None):
+        """Host-pointer entry of po_speedqp_batch.  states [B,N,5], v0 [B], and the plan as stgo_batch / stplan_batch return it: station [B,17] i32, n_layers [B] i32,
+        ref_states [B,Q,5] (the planner's samples at the same dts and Q, t0 = 0); optional n_states [B], ok [B] (the planner's ok_out), v_cap [B,N], cells
+        [B,K,128] i32 (None: nothing is blocked).  Returns a dict: status, iters, n_fact, n_q [B] i32, r_prim, r_dual [B], states [B,Q,5], v, a, jerk, t, lo, hi
+        [B,Q], index [B,Q] i32."""
+        from .abi import PoSpeedqpIn, PoSpeedqpOut
+
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        B, N = states.shape[0], states.shape[1]
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        vv, cap, ref = f(v0), f(v_cap), f(ref_states)
+        ns, okk, stn, nl, cl = _i32(n_states), _i32(ok), _i32(station), _i32(n_layers), _i32(cells)
+        qi = PoSpeedqpIn(B, N, _np(states), _np(ns), _np(okk), _np(vv), _np(cap), _np(stn), _np(nl), _np(cl), _np(ref))
+        qp = params if params is not None else default_speedqp_params()
+        Q = max(int(qp.Q), 0)
+        i32 = lambda *shape: np.zeros(shape, dtype=np.int32)
+        r = {"status": i32(B), "iters": i32(B), "n_fact": i32(B), "r_prim": np.zeros(B), "r_dual": np.zeros(B), "n_q": i32(B), "states": np.zeros((B, Q, 5)),
+             "v": np.zeros((B, Q)), "a": np.zeros((B, Q)), "jerk": np.zeros((B, Q)), "t": np.zeros((B, Q)), "lo": np.zeros((B, Q)), "hi": np.zeros((B, Q)),
+             "index": i32(B, Q)}
+        qo = PoSpeedqpOut(*[_np(r[k]) for k in self.SPEEDQP_KEYS])
+        _check(lib().po_speedqp_batch(self._h, C.byref(qp), C.byref(qi), C.byref(qo)))
+        return r
+
+    def speedqp_batch_device(self, t: dict, out: dict, params=None):
+        """Device-pointer entry: t: states [B,N,5] f64, v0 [B] f64, station [B,17] i32, n_layers [B] i32, ref_states [B,Q,5] f64 (+ n_states, ok i32 [B], v_cap
+        [B,N] f64, cells [B,K,128] i32); out: status [B] i32, states [B,Q,5] f64 (+ any of SPEEDQP_KEYS).  Q is params.Q.  Enqueued on the handle's stream, no
+        synchronisation."""
+        from .abi import PoSpeedqpIn, PoSpeedqpOut
+
+        B, N = t["states"].shape[0], t["states"].shape[1]
+        p = lambda d, k: None if d.get(k) is None else C.c_void_p(d[k].data_ptr())
+        qi = PoSpeedqpIn(B, N, *[p(t, k) for k in self.SPEEDQP_IN_KEYS])
+        qo = PoSpeedqpOut(*[p(out, k) for k in self.SPEEDQP_KEYS])
+        qp = params if params is not None else default_speedqp_params()
+        _check(lib().po_speedqp_batch_device(self._h, C.byref(qp), C.byref(qi), C.byref(qo)))
 
     # ---- corridor nudge: carve predicted agents out of the corridor bounds, pass left or right (DESIGN.md section 31) ----
     NUDGE_KEYS = ("status", "ok_out", "bounds", "side", "first_blocked_state", "first_blocked_agent", "width_min")

@@ -1259,6 +1259,87 @@ int po_stgo_batch(po_handle h, const po_stgo_params *p, const po_stgo_in *in, co
     });
 }
 
+// ---- speed QP: a jerk-limited s(t) inside a plan's tunnel (po_speedqp.hip) -----------------------
+void po_default_speedqp_params(po_speedqp_params *p) {
+    if (!p) return;
+    po_stgo_params g;
+    po_default_stgo_params(&g);
+    *p = po_speedqp_params{g.dt, g.K, g.stride, g.v_max, g.dts, g.Q, 2.0, 3.0, 4.0, 1.0, 1.0, 1.0, 0.1, 1e-6, 1.6, 1e-4, 1e-4, 2000, 25, 1};  // a starting point nobody has tuned
+}
+
+// What both entries can check without reading through a pointer of the structs (testable without a GPU)
+static bool speedqp_args_ok(po_handle h, const po_speedqp_params *p, const po_speedqp_in *in, const po_speedqp_out *out) {
+    if (!h || !p || !in || !out || in->B < 0 || in->N < 0) return false;
+    auto pos = [](double v) { return std::isfinite(v) && v > 0; };
+    auto wgt = [](double v) { return std::isfinite(v) && v >= 0; };
+    if (!pos(p->dt) || !pos(p->v_max) || !pos(p->dts) || !pos(p->a_max) || !pos(p->b_max) || !pos(p->j_max) || !pos(p->rho) || !pos(p->sigma)) return false;
+    if (p->K < 1 || p->K > PO_ST_MAX_LAYERS || p->stride < 1 || p->Q < 2 || p->Q > PO_SQP_MAX_SAMPLES) return false;
+    if (!wgt(p->w_s) || !wgt(p->w_a) || !wgt(p->w_j) || !(p->w_s + p->w_a + p->w_j > 0)) return false;
+    if (!(p->alpha > 0 && p->alpha < 2) || !wgt(p->eps_abs) || !wgt(p->eps_rel)) return false;
+    if (p->max_iter < 1 || p->check_every < 1 || (p->adaptive_rho != 0 && p->adaptive_rho != 1)) return false;
+    const size_t B = in->B, bn = B * (size_t)in->N, bq = B * (size_t)p->Q;
+    if (B > 0 && (!in->states || !in->v0 || !in->station || !in->n_layers || !in->ref_states || !out->status || !out->states)) return false;
+    // no output may overlap an input: byte ranges over the full extent of each array (B = 0: every extent is empty)
+    struct Range { const void *p; size_t bytes; };
+    const Range ins[] = {{in->states, 5 * bn * sizeof(double)}, {in->n_states, B * sizeof(int)}, {in->ok, B * sizeof(int)}, {in->v0, B * sizeof(double)},
+                         {in->v_cap, bn * sizeof(double)}, {in->station, B * (PO_ST_MAX_LAYERS + 1) * sizeof(int)}, {in->n_layers, B * sizeof(int)},
+                         {in->cells, B * (size_t)p->K * PO_ST_MAX_STATIONS * sizeof(int)}, {in->ref_states, 5 * bq * sizeof(double)}};
+    const Range outs[] = {{out->status, B * sizeof(int)}, {out->iters, B * sizeof(int)}, {out->n_fact, B * sizeof(int)}, {out->r_prim, B * sizeof(double)},
+                          {out->r_dual, B * sizeof(double)}, {out->n_q, B * sizeof(int)}, {out->states, 5 * bq * sizeof(double)}, {out->v, bq * sizeof(double)},
+                          {out->a, bq * sizeof(double)}, {out->jerk, bq * sizeof(double)}, {out->t, bq * sizeof(double)}, {out->lo, bq * sizeof(double)},
+                          {out->hi, bq * sizeof(double)}, {out->index, bq * sizeof(int)}};
+    for (const Range &o : outs)
+        for (const Range &i : ins) {
+            if (!o.p || !i.p || !o.bytes || !i.bytes) continue;
+            const uintptr_t ob = (uintptr_t)o.p, ib = (uintptr_t)i.p;
+            if (ob < ib + i.bytes && ib < ob + o.bytes) return false;
+        }
+    return true;
+}
+
+int po_speedqp_batch_device(po_handle h, const po_speedqp_params *p, const po_speedqp_in *in, const po_speedqp_out *out) {
+    if (!speedqp_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing to solve: no launch, whatever the handle holds
+    Lock g(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    po::DevSpeedQp D{};
+    D.B = in->B; D.N = in->N; D.K = p->K; D.stride = p->stride; D.Q = p->Q;
+    D.dt = p->dt; D.v_max = p->v_max; D.dts = p->dts; D.a_max = p->a_max; D.b_max = p->b_max; D.j_max = p->j_max; D.w_s = p->w_s; D.w_a = p->w_a; D.w_j = p->w_j;
+    D.rho = p->rho; D.sigma = p->sigma; D.alpha = p->alpha; D.eps_abs = p->eps_abs; D.eps_rel = p->eps_rel;
+    D.max_iter = p->max_iter; D.check_every = p->check_every; D.adaptive_rho = p->adaptive_rho;
+    D.states = in->states; D.n_states = in->n_states; D.ok = in->ok; D.v0 = in->v0; D.v_cap = in->v_cap; D.station = in->station; D.n_layers = in->n_layers;
+    D.cells = in->cells; D.ref_states = in->ref_states;
+    D.status = out->status; D.iters = out->iters; D.n_fact = out->n_fact; D.r_prim = out->r_prim; D.r_dual = out->r_dual; D.n_q = out->n_q;
+    D.o_states = out->states; D.o_v = out->v; D.o_a = out->a; D.o_jerk = out->jerk; D.o_t = out->t; D.o_lo = out->lo; D.o_hi = out->hi; D.index = out->index;
+    HIP_TRY(po_launch_speedqp(&D, h->stream));
+    return PO_OK;
+}
+
+int po_speedqp_batch(po_handle h, const po_speedqp_params *p, const po_speedqp_in *in, const po_speedqp_out *out) {
+    if (!speedqp_args_ok(h, p, in, out)) return PO_ERR_INVALID;
+    if (in->B == 0) return PO_OK;  // nothing is staged, launched or written
+    const size_t B = in->B, bn = B * (size_t)in->N, bq = B * (size_t)p->Q, W = PO_ST_MAX_LAYERS + 1;
+    for (size_t b = 0; b < B; ++b) {  // the plan as the host entry takes it: in range (the device entry reads it clamped)
+        const int nl = in->n_layers[b];
+        if (nl < 0 || nl > p->K) return PO_ERR_INVALID;
+        for (int k = 0; nl >= 1 && k <= nl; ++k)
+            if (in->station[b * W + k] < 0 || in->station[b * W + k] > PO_ST_MAX_STATIONS - 1) return PO_ERR_INVALID;
+    }
+    Stage S;
+    const Slot<double> states = S.in(in->states, 5 * bn), v0 = S.in(in->v0, B), cap = S.in(in->v_cap, bn), ref = S.in(in->ref_states, 5 * bq);
+    const Slot<int> ns = S.in(in->n_states, B), ok = S.in(in->ok, B), station = S.in(in->station, B * W), nl = S.in(in->n_layers, B);
+    const Slot<int> cells = S.in(in->cells, B * (size_t)p->K * PO_ST_MAX_STATIONS);
+    const Slot<int> status = S.out(out->status, B), iters = S.out_opt(out->iters, B), nf = S.out_opt(out->n_fact, B), nq = S.out_opt(out->n_q, B);
+    const Slot<int> index = S.out_opt(out->index, bq);
+    const Slot<double> rp = S.out_opt(out->r_prim, B), rd = S.out_opt(out->r_dual, B), os = S.out(out->states, 5 * bq), ov = S.out_opt(out->v, bq);
+    const Slot<double> oa = S.out_opt(out->a, bq), oj = S.out_opt(out->jerk, bq), ot = S.out_opt(out->t, bq), lo = S.out_opt(out->lo, bq), hi = S.out_opt(out->hi, bq);
+    return staged_call(h, S, &po_handle_s::post_buf, false, [&] {
+        const po_speedqp_in d{in->B, in->N, states, ns, ok, v0, cap, station, nl, cells, ref};
+        const po_speedqp_out o{status, iters, nf, rp, rd, nq, os, ov, oa, oj, ot, lo, hi, index};
+        return po_speedqp_batch_device(h, p, &d, &o);
+    });
+}
+
 // ---- agent sets (po_agentsets.hip) ----------------------------------------------------------------
 void po_default_agentsets_params(po_agentsets_params *p) {
     if (!p) return;

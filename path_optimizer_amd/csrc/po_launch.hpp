@@ -31,7 +31,7 @@ struct SolveShape {
 constexpr size_t kLdsLimit = 160 * 1024;
 struct DevMap; struct DevMaps; struct DevCar; struct DevBounds; struct DevSpline; struct DevSearch;  // po_map.hpp
 struct DevResample; struct PlanGate; struct PlanRows; struct DevSelect; struct DevSpeed; struct DevDynamic; struct DevStplan; struct DevNudge;
-struct DevTrajectory; struct DevAgentSets; struct DevStgo;
+struct DevTrajectory; struct DevAgentSets; struct DevStgo; struct DevSpeedQp;
 struct DevSmooth;                                                                    // po_smooth.hpp
 }  // namespace po
 
@@ -153,6 +153,10 @@ hipError_t po_launch_stplan(const po::DevCar *c, const po::DevStplan *a, hipStre
 // ---- po_stgo.hip: station-time plans that resume, sampled in time (one workgroup per path: the phases of po_stplan.hip's search from po_stsearch.hpp with a stopped
 // predecessor free to pull away, then lanes over the Q samples, each with a binary search on the path's s row; the same dynamic LDS; device pointers) ----
 hipError_t po_launch_stgo(const po::DevCar *c, const po::DevStgo *a, hipStream_t st);
+
+// ---- po_speedqp.hip: the speed QP inside a plan's tunnel (one wave per path: lanes over samples and rows for the row operations, lane 0 for the banded
+// factorisation and the two substitutions; dynamic LDS sized from Q; device pointers) ----
+hipError_t po_launch_speedqp(const po::DevSpeedQp *a, hipStream_t st);
 
 // ---- po_nudge.hip: corridor nudge (one wave per path, lanes own fixed (state, circle) pairs of the corridor, which lives in the output; the path's agent set through
 // LDS in chunks; device pointers) ----

@@ -151,6 +151,16 @@ struct DevStgo : DevStSearch {
     int *n_resumes; double *o_states, *o_v, *o_a, *o_t; int *index, *first_held, *end;
 };
 
+// speed-QP launch arguments (po_speedqp.hip): po_speedqp_in / po_speedqp_out and the fields of po_speedqp_params.  Every output but status
+// and o_states may be null; n_states, ok, v_cap and cells may be null.
+struct DevSpeedQp {
+    int B, N, K, stride, Q;
+    double dt, v_max, dts, a_max, b_max, j_max, w_s, w_a, w_j, rho, sigma, alpha, eps_abs, eps_rel;
+    int max_iter, check_every, adaptive_rho;
+    const double *states; const int *n_states, *ok; const double *v0, *v_cap; const int *station, *n_layers, *cells; const double *ref_states;
+    int *status, *iters, *n_fact; double *r_prim, *r_dual; int *n_q; double *o_states, *o_v, *o_a, *o_jerk, *o_t, *o_lo, *o_hi; int *index;
+};
+
 // corridor-nudge launch arguments (po_nudge.hip): po_nudge_in / po_nudge_out with the lists of po_agent_lists flattened, the fields of
 // po_nudge_params, and d and radius as DevBounds carries them.  bounds_in and bounds never alias.  Every output but status and bounds may be null.
 struct DevNudge {
